@@ -2,7 +2,14 @@
 """Benchmark: device-resident D-SGD neighbour mixing (one round = one step) on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config dcliques1000] [--kernel auto]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...      (N > 1, one process per GPU over RCCL)
+
+A plain run sets up, warms up, times the K steps and prints the result line.  Everything else the
+line can hold takes runs of its own and is measured only with --full: the stream-copy ceiling
+(config.stream_copy_GBs), the cold-cache round of graph-replayed configs, the CPU baseline, and
+for N > 1 the single-GPU reference point and the node-shard legs; without --full those fields are
+null or absent.  --dump-outputs DIR writes the last timed step's output (see dump_outputs).
 
 Metric (BASELINE.json): "param-GB/s mixed (device-resident), 1000-node d-cliques, P=1M fp32"
   value = (nodes mixed by all ranks) * P * 4 B / (time per round)   [GB/s, higher is better]
@@ -29,7 +36,7 @@ Multi-GPU (N > 1), two problem sizes:
       --interclique), per-GPU bytes those of the N=1 headline round;
   --config dcliques10000: BASELINE configs[4], the FIXED 10 000-node problem (100 cliques of 100)
       split over N GPUs (STRONG scaling); rank 0 then also times the whole problem alone on its own
-      GPU (--single-ref, default on) and reports speedup_vs_1gpu.
+      GPU (--single-ref, on with --full) and reports speedup_vs_1gpu.
 Two partitions:
   --shard stripes (default): rank r mixes parameter columns [c0, c1) of EVERY node (P/N columns
       each, block-aligned; the round is independent per column): no data-path collective
@@ -79,6 +86,14 @@ def parse():
     ap.add_argument("--interclique", default="fully-connected",
                     choices=["fully-connected", "smallworld", "ring"],
                     help="multi-GPU global d-cliques interclique topology")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the stream-copy "
+                         "ceiling, the cold-cache round, the CPU baseline and, for N > 1, the "
+                         "single-GPU reference point and the node-shard legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="single GPU: after the timed steps write the last step's output slab as "
+                         "DIR/theta_out.npy (float32, node order; a fixed seeded sample of columns "
+                         "when the slab is larger than 32 MiB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-cold-cache", action="store_true",
                     help="skip the cold-cache single-round timing of graph-replayed configs")
@@ -129,12 +144,13 @@ def parse():
     ap.add_argument("--single-ref", default="auto", choices=["auto", "on", "off"],
                     help="multi-GPU: rank 0 also times the N=1 point on its own GPU in the same run "
                          "(--config dcliques10000: the whole fixed problem -> speedup_vs_1gpu; "
-                         "weak line: nodes_per_gpu nodes -> weak_efficiency_vs_1gpu) (auto: on)")
+                         "weak line: nodes_per_gpu nodes -> weak_efficiency_vs_1gpu) (auto: on with "
+                         "--full)")
     ap.add_argument("--node-legs", default="auto",
                     help="multi-GPU with --shard stripes: after the stripes line, also time the "
                          "NODE-SHARD partition (RCCL halo exchange) on the same problem, one leg per "
-                         "interclique in this comma list (auto: --interclique, then smallworld; "
-                         "off: none).  Results go to config.node_shards; a failed or timed-out leg "
+                         "interclique in this comma list (auto: --interclique, then smallworld, with "
+                         "--full only; off: none).  Results go to config.node_shards; a failed or timed-out leg "
                          "records its error there and the stripes line is still printed")
     ap.add_argument("--leg-timeout", type=float, default=240.0,
                     help="multi-GPU: seconds one node-shard leg may take before every rank gives up "
@@ -523,6 +539,31 @@ def e2e_logger_costs(models, reps=3, cpu_sample=50):
     return out
 
 
+DUMP_SAMPLE_BYTES = 32 << 20
+DUMP_SEED = 20240229
+
+
+def dump_outputs(path, last, p, perm=None):
+    """--dump-outputs: the output slab of the last timed step as DIR/theta_out.npy, float32
+    [N, C] with row i = node i (slab row perm[i]) and C columns of the P: all of them when the
+    slab is at most DUMP_SAMPLE_BYTES, else a fixed sample (numpy default_rng(DUMP_SEED), sorted)
+    that depends only on N and P.  `last` is row-major [N, >= P] or column-blocked [K, N, B]."""
+    n = last.shape[-2]
+    ncols = min(p, max(1, DUMP_SAMPLE_BYTES // (4 * n)))
+    cols = np.arange(p) if ncols == p else \
+        np.sort(np.random.default_rng(DUMP_SEED).choice(p, size=ncols, replace=False))
+    cols = torch.from_numpy(cols).to(last.device)
+    rows = torch.arange(n, device=last.device) if perm is None else \
+        torch.from_numpy(np.asarray(perm, np.int64)).to(last.device)
+    if last.dim() == 3:
+        b = last.shape[2]
+        y = last[(cols // b)[None, :], rows[:, None], (cols % b)[None, :]]
+    else:
+        y = last[rows[:, None], cols[None, :]]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "theta_out.npy"), y.cpu().numpy().astype(np.float32, copy=False))
+
+
 def traffic_key(args, kernel, p, slab_layout):
     return f"{args.config}/{args.workload}/{kernel}/p{p}/{slab_layout}"
 
@@ -768,8 +809,8 @@ def node_shard_leg(make, interclique, steps, warmup, dev, dist, backend, seed=0,
     return info, last, sm
 
 
-def node_leg_intercliques(spec, interclique):
-    if spec == "off":
+def node_leg_intercliques(spec, interclique, full=True):
+    if spec == "off" or (spec == "auto" and not full):
         return []
     if spec == "auto":
         return [interclique] + (["smallworld"] if interclique != "smallworld" else [])
@@ -971,6 +1012,8 @@ def main():
     ident = world_identity(dev, dist, world, backend) if world > 1 else None
     if args.workload != "mix" and world > 1:
         raise SystemExit("--workload grad-clique is single-GPU")
+    if args.dump_outputs and world > 1:
+        raise SystemExit("--dump-outputs is single-GPU")
     fixed = world > 1 and args.config == "dcliques10000"       # BASELINE configs[4]: strong scaling
     if world > 1 and args.config not in ("dcliques1000", "dcliques10000"):
         raise SystemExit("multi-GPU: --config dcliques1000 (weak, 1000 nodes per GPU) or dcliques10000")
@@ -1004,6 +1047,7 @@ def main():
         if k0 == "auto":
             k0 = mixer.kernel_for("fast") if args.workload == "mix" else "grad-segment-mean"
         row_order = "rank"
+        row_perm = None                                 # node i lives at slab row row_perm[i]
         if args.layout == "blocked" and args.workload == "mix" and args.kernel in ("auto", "band-fast",
                                                                                  "band-exact"):
             perm, _ = mixer.device_layout() if mixer.plan is None else (None, None)
@@ -1012,6 +1056,7 @@ def main():
                 # band kernel reads them without descriptors (Mixer.device_layout)
                 mixer = mixer.relabeled(perm)
                 row_order = "ring cycle order"
+                row_perm = perm
                 k0 = mixer.kernel_for("fast")
         if (args.layout in ("blocked", "blocked-rank") and not args.hipmalloc_slabs and p % 4 == 0
                 and ((k0 == "clique" and args.workload == "mix" and mixer.plan.max_clique <= 1024)
@@ -1025,6 +1070,7 @@ def main():
                 if perm is not None:
                     mixer = mixer.relabeled(perm)
                     row_order = "clique-contiguous"
+                    row_perm = perm
             xa = memory.empty_blocked(n_local, p, dev, bc)
             xa.normal_(generator=gen)
             xb = memory.empty_blocked(n_local, p, dev, bc)
@@ -1100,6 +1146,10 @@ def main():
                                               use_graph, backend)
     step_s = region_s / args.steps
     value = n_total * p * 4 / step_s / 1e9
+    if args.dump_outputs:
+        # round k reads the slab round k - 1 wrote (ping-pong from xa), graph-replayed or not
+        dump_outputs(args.dump_outputs, xa if (args.steps + args.warmup) % 2 == 0 else xb, p,
+                     row_perm)
     slab_layout = (f"column-blocked [{xa.shape[0]}, {xa.shape[1]}, {xa.shape[2]}], "
                    f"{row_order} rows" if xa.dim() == 3 and (blocked or args.shard == "stripes") else
                    "window-blocked [K, rows_in, w]" if xa.dim() == 3 else
@@ -1107,7 +1157,7 @@ def main():
                                          if xa.dim() == 2 and xa.stride(0) != p else "")
                    + (f", {row_order} rows" if row_order != "rank" else ""))
     single = None
-    if world > 1 and args.single_ref != "off":
+    if world > 1 and (args.single_ref == "on" or (args.single_ref == "auto" and args.full)):
         # the N=1 point of this line, measured in the same run on rank 0's GPU with the same
         # kernel and layout (the other ranks wait): the fixed problem alone (strong scaling), or
         # one GPU's share of the weak line (nodes_per_gpu nodes, the same P)
@@ -1117,9 +1167,9 @@ def main():
             n1 = n_total if fixed else args.nodes_per_gpu
             single = single_gpu_round_ms(n1, p, args.interclique, dev, args.steps, args.warmup)
         dist.barrier()
-    copy_gbs = stream_copy_probe(n_local * cols_local, dev)
+    copy_gbs = stream_copy_probe(n_local * cols_local, dev) if args.full else None
     cold = (cold_cache_rounds(step, xa, xb, dev)
-            if world == 1 and graph is not None and not args.no_cold_cache else None)
+            if args.full and world == 1 and graph is not None and not args.no_cold_cache else None)
 
     out = None
     if rank == 0:
@@ -1180,7 +1230,8 @@ def main():
                 csr, cliques, dev, rounds=args.e2e_rounds,
                 only=set(v for v in args.e2e_variants.split(",") if v) or None)
         cpu = None
-        if world == 1 and not args.no_cpu_baseline and args.config != "dcliques10000":
+        if (args.full and world == 1 and not args.no_cpu_baseline
+                and args.config != "dcliques10000"):
             if args.workload == "grad-clique":
                 cpu = cpu_baseline_grad(cliques, csr.n, p)
             else:
@@ -1201,9 +1252,9 @@ def main():
                        "slab_layout": slab_layout,
                        "lib_sha16": lib_sha, "traffic_source": traffic_src,
                        "traffic_key": traffic_key(args, kernel, p, slab_layout),
-                       "stream_copy_GBs": round(copy_gbs, 1),
+                       "stream_copy_GBs": round(copy_gbs, 1) if copy_gbs else None,
                        "frac_of_stream_copy": (round(roof["achieved"] / copy_gbs, 4)
-                                               if roof["unit"] == "GB/s" else None)},
+                                               if copy_gbs and roof["unit"] == "GB/s" else None)},
             "roofline": roof,
             "cpu_baseline": cpu,
         }
@@ -1225,7 +1276,7 @@ def main():
             else:       # weak: each GPU's work equals the N=1 round's
                 out["config"]["single_gpu_nodes"] = args.nodes_per_gpu
                 out["config"]["weak_efficiency_vs_1gpu"] = round(single / (step_s * 1e3), 3)
-    node_legs = (node_leg_intercliques(args.node_legs, args.interclique)
+    node_legs = (node_leg_intercliques(args.node_legs, args.interclique, args.full)
                  if world > 1 and args.shard == "stripes" else [])
     import threading
     print_lock, printed = threading.Lock(), [False]

@@ -251,6 +251,37 @@ def test_node_leg_intercliques():
         bench.node_leg_intercliques("mesh", "x")
 
 
+def test_dump_outputs_layouts(tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs): row i of theta_out.npy is node i (slab row perm[i]) from
+    a row-major slab on a padded pitch and from a column-blocked one with a ragged last block; a
+    slab above the size limit is cut to the same sorted, seeded columns every time."""
+    import bench
+    from niidmix import memory
+    n, p, b = 7, 50, 16
+    rng = np.random.default_rng(3)
+    y = rng.standard_normal((n, p)).astype(np.float32)
+    perm = rng.permutation(n)
+    slab = np.empty((n, 64), np.float32)
+    slab.fill(np.nan)
+    slab[perm, :p] = y                                  # node i at slab row perm[i]
+    rowmajor = torch.from_numpy(slab)[:, :p]
+    blocked = memory.to_blocked(rowmajor.contiguous(), b)
+    assert blocked.shape == (4, n, b)
+    for k, (last, pm) in enumerate([(rowmajor, perm), (blocked, perm),
+                                    (torch.from_numpy(y), None)]):
+        d = str(tmp_path / f"full{k}")
+        bench.dump_outputs(d, last, p, pm)
+        got = np.load(os.path.join(d, "theta_out.npy"))
+        assert got.dtype == np.float32 and np.array_equal(got, y)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_BYTES", 4 * n * 10)
+    cols = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(p, size=10, replace=False))
+    assert len(set(cols.tolist())) == 10
+    for k, last in enumerate([rowmajor, blocked, blocked]):
+        d = str(tmp_path / f"sample{k}")
+        bench.dump_outputs(d, last, p, perm)
+        assert np.array_equal(np.load(os.path.join(d, "theta_out.npy")), y[:, cols])
+
+
 @pytest.mark.gpu
 def test_world_identity_on_the_gpu():
     """bench.world_identity on a real GPU (the N > 1 line's config.world): the device's UUID and

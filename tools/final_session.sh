@@ -20,7 +20,7 @@ T=$O/traffic_$PART.json
 [ "$PART" = merge ] || [ -f $T ] || cp profiles/traffic.json $T
 one() {   # name kernel-substring alg-bytes bench-args...
   n=$1; k=$2; alg=$3; shift 3
-  timeout -k 10 300 python bench.py --no-cpu-baseline "$@" > $O/bench_$n.json 2> $O/bench_$n.err || { echo "bench $n failed"; tail -5 $O/bench_$n.err; return 1; }
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline "$@" > $O/bench_$n.json 2> $O/bench_$n.err || { echo "bench $n failed"; tail -5 $O/bench_$n.err; return 1; }
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/kt_$n -o kt -- python3 $R/bench.py --no-cpu-baseline --no-cold-cache "$@" > $O/kt_$n.log 2>&1 || { echo "trace $n failed"; tail -5 $O/kt_$n.log; return 1; }
   for c in FETCH_SIZE WRITE_SIZE; do
     timeout -s KILL 300 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $R/$O/pmc_${n}_$c -o p -- python3 $R/bench.py --no-cpu-baseline --no-cold-cache "$@" > $O/pmc_${n}_$c.log 2>&1 || { echo "pmc $n $c failed"; tail -5 $O/pmc_${n}_$c.log; return 1; }
@@ -35,7 +35,7 @@ case $PART in
     [ $rc -ne 0 ] && exit $rc
     timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { echo smoke failed; cat $O/smoke.log; exit 3; }
     tail -1 $O/smoke.log
-    timeout -k 10 600 python bench.py > $O/bench_headline_default.json 2> $O/bench_headline_default.err || { echo bench failed; tail $O/bench_headline_default.err; exit 4; }
+    timeout -k 10 600 python bench.py --full > $O/bench_headline_default.json 2> $O/bench_headline_default.err || { echo bench failed; tail $O/bench_headline_default.err; exit 4; }
     cat $O/bench_headline_default.json ;;
   cfgA)
     one headline k_mix_clique 8388608000 --steps 20 || exit 5
