@@ -22,7 +22,9 @@
  * overlap.  Every entry point that reads one slab and writes another gets the row count and checks
  * the full extents of both (NIIDMIX_EALIAS), each slab with its own strides.
  *
- * ABI 5 (this header): niidmix_dense_split_elems / niidmix_dense_split_w /
+ * ABI 6 (this header): niidmix_sgd_momentum_step_rows_f32 added (the optimizer step of
+ * --learning-momentum on the device).
+ * ABI 5: niidmix_dense_split_elems / niidmix_dense_split_w /
  * niidmix_mix_dense_bf16x6_f32 added (the dense GEMM on the bf16 matrix cores, fp32-accurate by
  * three-term splitting); niidmix_mix_strip_f32 refuses a strip that does not fit the device's LDS.
  * ABI 4: niidmix_mix_band_f32 added (banded low-degree graphs, e.g. a ring in its
@@ -45,7 +47,7 @@
 extern "C" {
 #endif
 
-#define NIIDMIX_ABI_VERSION 5
+#define NIIDMIX_ABI_VERSION 6
 
 enum niidmix_status {
     NIIDMIX_OK = 0,
@@ -384,6 +386,31 @@ int niidmix_grad_segment_mean_blocked_f32(const float *g, float *y, int64_t n_ro
  *   rows [n_rows] int32 rows to step (device) */
 int niidmix_sgd_step_rows_f32(float *p, int64_t ld_p, const float *g, int64_t ld_g, int64_t ncols,
                               const int32_t *rows, int64_t n_rows, float neg_lr, void *stream);
+
+/* SGD step with momentum on the listed rows — torch.optim.SGD(lr, momentum) without dampening,
+ * weight decay or Nesterov, the optimizer the reference builds from --learning-momentum
+ * (d_sgd.py:118-122) and steps at d_sgd.py:52, :65, :80, :92.  Bit for bit ATen's CPU arithmetic:
+ *   first != 0 (a parameter's first step):  buf[row] = g[row]   (a copy: -0.0 stays -0.0; buf is
+ *                                                                not read)
+ *   first == 0:   buf[row] = fl(fl(momentum * buf[row]) + g[row])   (buf.mul_(m).add_(g): the
+ *                                                                multiply and the add round apart)
+ *   then always:  p[row]   = fma(neg_lr, buf[row], p[row])      (p.add_(buf, alpha=-lr): one rounding)
+ * with neg_lr = fp32(-lr) and momentum = fp32(m).  One streaming pass: p, g and buf are read and p
+ * and buf written (20 B per element; 16 B with `first`).  Rows not listed are untouched in p and buf.
+ * The resident drop-in round (niidmix.d_sgd) runs gradient mean -> this step -> mixing with buf
+ * kept in HBM between rounds.
+ *   p   [*, ld_p] parameters (device, updated in place)
+ *   g   [*, ld_g] gradients (device)
+ *   buf [*, ld_b] momentum buffers (device, updated in place)
+ *   rows [n_rows] int32 distinct rows to step (device)
+ * Range checks: the row list is on the device and is not read by the launcher, so each slab's
+ * extent is taken as the least n_rows distinct rows can span, (n_rows - 1) * ld + ncols elements
+ * from its base; any two of p, g, buf that overlap over those extents are refused (NIIDMIX_EALIAS).
+ * NIIDMIX_EINVAL: a null pointer, a negative size, a leading dimension below ncols. */
+int niidmix_sgd_momentum_step_rows_f32(float *p, int64_t ld_p, const float *g, int64_t ld_g,
+                                       float *buf, int64_t ld_b, int64_t ncols,
+                                       const int32_t *rows, int64_t n_rows, float neg_lr,
+                                       float momentum, int first, void *stream);
 
 /* update_models(all_models, avg) after the 'sample' topology's uniform average (d_sgd.py:240-250,
  * :29-35): every row y_i := fl(fl(x_i * 0) + avg) (p.mul_(0.); p.add_(new)) — avg everywhere

@@ -3960,6 +3960,53 @@ __global__ __launch_bounds__(256) void k_sgd_step_rows(float *__restrict__ p, in
 }
 
 // ----------------------------------------------------------------------------------------------
+// SGD step with momentum on listed rows (torch.optim.SGD(momentum=m), no dampening / weight decay /
+// Nesterov; the reference's optimizer, d_sgd.py:118-122).  ATen's CPU kernels give, bit for bit,
+//   FIRST (the parameter's first step):  buf = g                      (clone: keeps a -0.0)
+//   later steps:                         buf = fl(fl(m * buf) + g)    (buf.mul_(m).add_(g): two roundings)
+//   every step:                          p   = fma(neg_lr, buf, p)    (p.add_(buf, alpha=-lr): one)
+// for row in rows; other rows of p and buf are untouched.  One streaming pass: 20 B per element
+// (16 B FIRST, which never reads buf).  g and buf are touched once per round: non-temporal; p is
+// read by the mixing kernel next: plain stores.
+template <int V, bool FIRST>
+__global__ __launch_bounds__(256) void k_sgd_momentum_step_rows(float *__restrict__ p, int64_t ld_p,
+                                                                const float *__restrict__ g, int64_t ld_g,
+                                                                float *__restrict__ buf, int64_t ld_b,
+                                                                int64_t ncols, const int32_t *__restrict__ rows,
+                                                                int64_t n_rows, float neg_lr, float momentum,
+                                                                int64_t n_chunks) {
+#pragma clang fp contract(off)           // the buffer update is a rounded multiply, then a rounded add
+    for (int64_t t = blockIdx.x; t < n_rows * n_chunks; t += gridDim.x) {
+        const int64_t r = rows[t / n_chunks];
+        const int64_t c = (t % n_chunks) * (256 * V) + (int64_t)threadIdx.x * V;
+        if (c >= ncols) continue;
+        float pv[V], bv[V];
+        ldv<V>(p + r * ld_p + c, pv);
+        ldv_nt<V>(g + r * ld_g + c, bv);
+        if constexpr (!FIRST) {
+            float mv[V];
+            ldv_nt<V>(buf + r * ld_b + c, mv);
+#pragma unroll
+            for (int e = 0; e < V; ++e) {
+                const float t = momentum * mv[e];    // rounded (contract off in this function,
+                bv[e] = t + bv[e];                   // whatever the translation unit's flag)
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < V; ++e) pv[e] = __builtin_fmaf(neg_lr, bv[e], pv[e]);
+        if constexpr (V == 4) {
+            typedef float f4 __attribute__((ext_vector_type(4)));
+            const f4 o = {bv[0], bv[1], bv[2], bv[3]};
+            __builtin_nontemporal_store(o, reinterpret_cast<f4 *>(buf + r * ld_b + c));
+            *reinterpret_cast<float4 *>(p + r * ld_p + c) = make_float4(pv[0], pv[1], pv[2], pv[3]);
+        } else {
+            __builtin_nontemporal_store(bv[0], buf + r * ld_b + c);
+            p[r * ld_p + c] = pv[0];
+        }
+    }
+}
+
+// ----------------------------------------------------------------------------------------------
 // Halo pack of the sharded round: out[i, :] = x[rows[i], :] (the rows a peer shard reads), so that
 // one contiguous send per peer carries them.
 template <int V>
@@ -5083,6 +5130,40 @@ int niidmix_sgd_step_rows_f32(float *p, int64_t ld_p, const float *g, int64_t ld
     else
         hipLaunchKernelGGL(k_sgd_step_rows<1>, grid, block, 0, s, p, ld_p, g, ld_g, ncols, rows, n_rows, neg_lr, n_chunks);
     return check_launch("k_sgd_step_rows");
+}
+
+int niidmix_sgd_momentum_step_rows_f32(float *p, int64_t ld_p, const float *g, int64_t ld_g,
+                                       float *buf, int64_t ld_b, int64_t ncols,
+                                       const int32_t *rows, int64_t n_rows, float neg_lr,
+                                       float momentum, int first, void *stream) {
+    if (ncols < 0 || n_rows < 0) return set_error(NIIDMIX_EINVAL, "negative size");
+    if (ncols == 0 || n_rows == 0) return NIIDMIX_OK;
+    if (!p || !g || !buf || !rows) return set_error(NIIDMIX_EINVAL, "null pointer");
+    if (ld_p < ncols || ld_g < ncols || ld_b < ncols)
+        return set_error(NIIDMIX_EINVAL, "leading dimension < ncols");
+    // `rows` lives on the device: n_rows distinct rows reach at least row n_rows - 1
+    const int64_t ext_p = (n_rows - 1) * ld_p + ncols, ext_g = (n_rows - 1) * ld_g + ncols,
+                  ext_b = (n_rows - 1) * ld_b + ncols;
+    if (overlaps(p, ext_p, g, ext_g)) return set_error(NIIDMIX_EALIAS, "p and g overlap");
+    if (overlaps(p, ext_p, buf, ext_b)) return set_error(NIIDMIX_EALIAS, "p and buf overlap");
+    if (overlaps(g, ext_g, buf, ext_b)) return set_error(NIIDMIX_EALIAS, "g and buf overlap");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const bool vec4 = ncols % 4 == 0 && ld_p % 4 == 0 && ld_g % 4 == 0 && ld_b % 4 == 0 &&
+                      aligned16(p) && aligned16(g) && aligned16(buf);
+    const int64_t cols = vec4 ? 1024 : 256;
+    const int64_t n_chunks = (ncols + cols - 1) / cols;
+    const int64_t items = n_rows * n_chunks;
+    const dim3 grid((unsigned)(items < kMaxGrid ? items : kMaxGrid)), block(256);
+#define NIIDMIX_MOMENTUM_LAUNCH(V, FIRST)                                                          \
+    hipLaunchKernelGGL((k_sgd_momentum_step_rows<V, FIRST>), grid, block, 0, s, p, ld_p, g, ld_g,  \
+                       buf, ld_b, ncols, rows, n_rows, neg_lr, momentum, n_chunks)
+    if (vec4) {
+        if (first) NIIDMIX_MOMENTUM_LAUNCH(4, true); else NIIDMIX_MOMENTUM_LAUNCH(4, false);
+    } else {
+        if (first) NIIDMIX_MOMENTUM_LAUNCH(1, true); else NIIDMIX_MOMENTUM_LAUNCH(1, false);
+    }
+#undef NIIDMIX_MOMENTUM_LAUNCH
+    return check_launch("k_sgd_momentum_step_rows");
 }
 
 int niidmix_update_rows_f32(const float *x, int64_t ld_x, float *y, int64_t ld_y, int64_t n_rows,

@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("NIIDMIX_LIB") or os.path.join(_HERE, "libniidmix.so")
 
 OK, EINVAL, EALIAS, EHIP, EUNSUPPORTED = 0, 1, 2, 3, 4
 MODE_EXACT, MODE_FAST = 0, 1
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 _i64, _i32, _vp = ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p
 
@@ -88,6 +88,9 @@ SIGNATURES = {
     "niidmix_update_rows_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _i64, _i64, _vp, _vp]),
     "niidmix_sgd_step_rows_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _i64, _vp, _i64,
                                                  ctypes.c_float, _vp]),
+    "niidmix_sgd_momentum_step_rows_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _vp,
+                                                          _i64, ctypes.c_float, ctypes.c_float,
+                                                          ctypes.c_int, _vp]),
     "niidmix_sharded_create": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.POINTER(_vp)]),
     "niidmix_sharded_destroy": (ctypes.c_int, [_vp]),
     "niidmix_sharded_is_loopback": (ctypes.c_int, [_vp]),

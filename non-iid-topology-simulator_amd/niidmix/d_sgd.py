@@ -189,27 +189,70 @@ _sgd_checked = weakref.WeakKeyDictionary()
 _no_device_step = {}
 
 
+def _momentum(params):
+    """params' --learning-momentum (0.0 when absent)."""
+    return float(params["algorithm"].get("learning-momentum", 0.0) or 0.0)
+
+
+def _no_fit(nodes):
+    hit = _no_device_step.get(id(nodes))
+    return hit is not None and bool(nodes) and hit() is nodes[0]["model"]
+
+
+def _plugin_sgd(opt, lr, mom):
+    """`opt` is the plugin's optimizer (optimizer() below) at this learning rate and momentum:
+    one group, no dampening, weight decay, Nesterov or maximize."""
+    if type(opt) is not torch.optim.SGD or len(opt.param_groups) != 1:
+        return False
+    g = opt.param_groups[0]
+    return not (float(g["lr"]) != lr or float(g["momentum"]) != mom or g["dampening"] != 0 or
+                g["weight_decay"] != 0 or g["nesterov"] or g.get("maximize", False))
+
+
+def _momentum_state(nodes, rows=None):
+    """Which of the nodes' optimizers (rows: the stepped ones, default all) hold torch's
+    momentum_buffer: 'all' (every parameter of every one), 'none', or 'mixed'."""
+    full = empty = 0
+    for nd in (nodes if rows is None else [nodes[r] for r in rows]):
+        opt = nd["optimizer"]
+        ps = opt.param_groups[0]["params"]
+        k = sum(1 for q in ps if opt.state.get(q, {}).get("momentum_buffer") is not None)
+        full += k == len(ps)
+        empty += k == 0
+        if (full and empty) or 0 < k < len(ps):
+            return "mixed"
+    return "none" if not full else "all"
+
+
+def _holds_momentum(nodes, plain):
+    """The node list's live engine keeps momentum state on the device."""
+    eng = _fused_engines.get((id(nodes), plain))
+    return (eng is not None and eng.momentum != 0.0 and bool(nodes)
+            and eng.slab.models[0] is nodes[0]["model"])
+
+
 def _device_step_ok(params, nodes):
     """The plain round's optimizer step may run on the device (_FusedEngine(plain=True)): every
-    node's optimizer is the plugin's plain SGD (optimizer() above, momentum 0: no state, p += -lr g)
-    over exactly its model's parameters, all trainable, at params' learning rate;
-    NIIDMIX_DEVICE_STEP=0 disables it (the CPU steps, as rounds 1-5 did).  The device steps every
-    parameter: one the forward does not use (its gradient stays the -0.0 fill, where torch leaves
-    None and the optimizer skips it) ends the step unchanged except that a -0.0 becomes +0.0."""
+    node's optimizer is the plugin's SGD (optimizer() above: p += -lr g, or with
+    --learning-momentum buf = m buf + g; p += -lr buf) over exactly its model's parameters, all
+    trainable, at params' learning rate and momentum, without dampening, weight decay, Nesterov or
+    maximize; with momentum, either every node's optimizer holds a momentum_buffer for every
+    parameter (the engine adopts them) or none holds any.  NIIDMIX_DEVICE_STEP=0 disables it (the
+    CPU steps, as rounds 1-5 did).  The device steps every parameter: one the forward does not use
+    (its gradient stays the -0.0 fill, where torch leaves None and the optimizer skips it) ends the
+    step unchanged except that a -0.0 becomes +0.0.  The same holds with momentum: that
+    parameter's momentum buffer stays -0.0 (m * -0.0 + -0.0), where torch keeps no state for it."""
     if os.environ.get("NIIDMIX_DEVICE_STEP", "1") == "0" or not _resident_ok():
         return False
-    hit = _no_device_step.get(id(nodes))
-    if hit is not None and nodes and hit() is nodes[0]["model"]:
+    if _no_fit(nodes):
         return False
     lr = float(params["algorithm"]["learning-rate"])
+    mom = _momentum(params)
     for nd in nodes:
         opt = nd.get("optimizer")
-        if type(opt) is not torch.optim.SGD or len(opt.param_groups) != 1:
+        if not _plugin_sgd(opt, lr, mom):
             return False
         g = opt.param_groups[0]
-        if (float(g["lr"]) != lr or g["momentum"] != 0 or g["dampening"] != 0 or
-                g["weight_decay"] != 0 or g["nesterov"] or g.get("maximize", False)):
-            return False
         hit = _sgd_checked.get(opt)
         if hit is None or hit() is not nd["model"]:
             with guard.suspended():
@@ -219,15 +262,26 @@ def _device_step_ok(params, nodes):
             if not all(q.requires_grad for q in mine):     # a frozen parameter gets no gradient:
                 return False                               # the CPU optimizer skips it
             _sgd_checked[opt] = weakref.ref(nd["model"])
+    if mom != 0.0 and not _holds_momentum(nodes, True) and _momentum_state(nodes) == "mixed":
+        return False
     return True
 
 
-def _fused_ok(params):
-    """The fused device round applies when gradients are averaged and the optimizer step is plain
-    SGD (momentum 0: the reference's default, d_sgd.py:262-263); NIIDMIX_FUSED=0 disables it."""
-    alg = params["algorithm"]
-    return (_averages_gradients(params) and float(alg.get("learning-momentum", 0.0)) == 0.0
-            and os.environ.get("NIIDMIX_FUSED", "1") != "0")
+def _fused_ok(params, nodes=None):
+    """The fused device round applies when gradients are averaged and the optimizer step is the
+    plugin's SGD (the reference's default, d_sgd.py:262-263); NIIDMIX_FUSED=0 disables it.  With
+    --learning-momentum the momentum buffers live on the device, so only the resident round
+    qualifies, and every node's optimizer (`nodes` given) must be the plugin's at params' learning
+    rate and momentum: its state is adopted and exported (sync_optimizer_state)."""
+    if not _averages_gradients(params) or os.environ.get("NIIDMIX_FUSED", "1") == "0":
+        return False
+    mom = _momentum(params)
+    if mom == 0.0:
+        return True
+    if not _resident_ok() or (nodes is not None and _no_fit(nodes)):
+        return False
+    lr = float(params["algorithm"]["learning-rate"])
+    return nodes is None or all(_plugin_sgd(nd.get("optimizer"), lr, mom) for nd in nodes)
 
 
 class _FusedEngine:
@@ -244,7 +298,16 @@ class _FusedEngine:
     each backward (accumulate_grad adds in place: -0 + g = g bit for bit, every g, where a +0 fill
     would turn a -0 gradient into +0).  While the models were not written between rounds (the
     resident round's `fresh` flag, guarded writes, and the parameters' version counters) the
-    parameters stay on the device: only gradients go H2D; otherwise they go up with them."""
+    parameters stay on the device: only gradients go H2D; otherwise they go up with them.
+
+    --learning-momentum (resident engine only): every stripe keeps an [N, w] momentum buffer in
+    HBM (fused_op), one more resident buffer; it never crosses PCIe during a round.  Optimizers
+    that already hold torch's momentum_buffer (CPU steps ran before) are adopted at construction;
+    export_momentum() writes the device state back into them (sync_optimizer_state, and before the
+    engine is dropped).  A new graph (set_topology) and a parameter re-upload leave it alone.
+
+    Raises _NoFit, before any slab is built, when the round needs the resident buffers (plain, or
+    momentum) and they do not fit in HBM, or the optimizers' momentum state cannot be adopted."""
 
     def __init__(self, nodes, topology, params, devices, plain=False):
         from .gradient import GradMean, build_grad_plan
@@ -253,33 +316,56 @@ class _FusedEngine:
         self.topology = topology
         self.weights_id = id(topology.get("weights"))
         self.plain = plain
-        self.key = _grad_key(params) + (float(params["algorithm"]["learning-rate"]), plain)
+        self.momentum = _momentum(params)
+        self.key = _fused_key(params, plain)
         models = [n["model"] for n in nodes]
-        self.slab = NodeSlab(models)
-        self.gslab = NodeSlab(models, grads=True)
         self.plan = None if plain else build_grad_plan(len(nodes), topology, params)
         stepped = list(range(len(nodes))) if plain else self.plan.stepped
+        # the plain round's gradients are the nodes' own: nothing to write back
+        wb = not plain and os.environ.get("NIIDMIX_GRAD_WRITEBACK", "1") != "0"
+        with guard.suspended():
+            n, p = len(models), sum(q.numel() for q in models[0].parameters())
+        # HBM budget first, while no pinned slab exists: parameters, gradients, mixed output (and
+        # the averaged gradients), plus the momentum buffer
+        fits = _resident_ok() and ResidentRound.fits(
+            n, p, devices, buffers=(4 if wb else 3) + (1 if self.momentum else 0))
+        adopt = False
+        if self.momentum:
+            held = _momentum_state(nodes, stepped)
+            if not fits or held == "mixed":
+                raise _NoFit("momentum buffers: " + ("no room in HBM" if not fits else
+                                                     "only some optimizers hold state"), not fits)
+            adopt = held == "all"
+        elif plain and not fits:
+            raise _NoFit("device-step buffers: no room in HBM", True)
+        self.slab = NodeSlab(models)
+        self.gslab = NodeSlab(models, grads=True)
         csr = to_csr(topology)
         if csr.n != self.slab.n:
             raise ValueError(f"topology has {csr.n} nodes, {self.slab.n} models given")
         self.mixer = Mixer(csr=csr, cliques=topology.get("cliques"), device=devices[0])
         lr = params["algorithm"]["learning-rate"]
 
-        n, p = self.slab.n, self.slab.p
-        # the plain round's gradients are the nodes' own: nothing to write back
-        wb = not plain and os.environ.get("NIIDMIX_GRAD_WRITEBACK", "1") != "0"
         self.resident = None
         self.runner = None
         self.param_uploads = 0          # rounds whose parameters went H2D (tests)
-        if _resident_ok() and ResidentRound.fits(n, p, devices, buffers=4 if wb else 3):
+        # momentum: 'first' until a momentum step has run (or state was adopted); 'dirty' while
+        # the device buffers are newer than the optimizers' momentum_buffer
+        self.mstate = {"first": True, "dirty": False}
+        self.stepped = stepped
+        self.optimizers = [n["optimizer"] for n in nodes] if self.momentum else None
+        if fits:
             self.resident = ResidentRound(
                 lambda dev, part: fused_op(dev, part, None if plain else GradMean(self.plan, dev),
                                            stepped, lr,
-                                           self.mixer if dev == devices[0] else self.mixer.to(dev)),
+                                           self.mixer if dev == devices[0] else self.mixer.to(dev),
+                                           momentum=self.momentum, mstate=self.mstate),
                 n, p, devices, block=_row_block(), n_in=2, n_out=2 if wb else 1)
             self.outs = (self.slab.host, self.gslab.host) if wb else (self.slab.host,)
             self.resident.version_of = self.slab.version
             guard.install(models, self.resident)
+            if adopt:
+                self._adopt_momentum()
         elif not plain:
             def make(dev, n, cols):
                 mixer = self.mixer if dev == devices[0] else self.mixer.to(dev)
@@ -296,6 +382,56 @@ class _FusedEngine:
         write to the models since (guarded writes clear `fresh`; the version counters catch writes
         through the parameters, e.g. an optimizer step or p.add_ under no_grad)."""
         return self.resident is not None and self.resident.current()
+
+    # momentum state hand-over: torch's optimizer.state[p]['momentum_buffer'] <-> part['mbuf']
+    def _momentum_chunks(self):
+        """(r0, r1) row ranges of at most ~64 MiB of one full-width buffer each."""
+        step = max(1, (64 << 20) // (4 * self.slab.p))
+        return [(r0, min(self.slab.n, r0 + step)) for r0 in range(0, self.slab.n, step)]
+
+    def _adopt_momentum(self):
+        """Upload every stepped node's momentum buffers (model.parameters() order, as the slab's
+        rows) into the stripes' device buffers; the next step is not a first step."""
+        stepped = set(self.stepped)
+        for r0, r1 in self._momentum_chunks():
+            rows = [r for r in range(r0, r1) if r in stepped]
+            if not rows:
+                continue
+            host = torch.zeros((r1 - r0, self.slab.p), dtype=torch.float32)
+            for r in rows:
+                state = self.optimizers[r].state
+                host[r - r0].copy_(torch.cat([state[q]["momentum_buffer"].detach().reshape(-1)
+                                              for _, _, q in self.slab._slots[r]]))
+            for pt in self.resident.parts:
+                pt["mbuf"][r0:r1].copy_(host[:, pt["c0"]:pt["c0"] + pt["w"]])
+        for pt in self.resident.parts:
+            torch.cuda.synchronize(pt["dev"])     # the uploads precede the round's own streams
+        self.mstate["first"] = False
+
+    def export_momentum(self):
+        """Write the device momentum buffers into the stepped nodes' optimizers, as the plain
+        per-parameter tensors torch keeps (optimizer.state[p]['momentum_buffer']).  No-op when
+        the optimizers already hold the device's state."""
+        if not self.momentum or self.resident is None or not self.mstate["dirty"]:
+            return
+        self.wait_all()
+        for pt in self.resident.parts:
+            pt["s_mix"].synchronize()
+        stepped = set(self.stepped)
+        for r0, r1 in self._momentum_chunks():
+            rows = [r for r in range(r0, r1) if r in stepped]
+            if not rows:
+                continue
+            host = torch.empty((r1 - r0, self.slab.p), dtype=torch.float32)
+            for pt in self.resident.parts:
+                host[:, pt["c0"]:pt["c0"] + pt["w"]].copy_(pt["mbuf"][r0:r1])
+            for r in rows:
+                state, off = self.optimizers[r].state, 0
+                for _, _, q in self.slab._slots[r]:
+                    k = q.numel()
+                    state[q]["momentum_buffer"] = host[r - r0, off:off + k].clone().view(q.shape)
+                    off += k
+        self.mstate["dirty"] = False
 
     def clear_grad_row(self, i):
         """Before node i's backward: its gradient views to -0.0 (see the class docstring)."""
@@ -327,6 +463,9 @@ class _FusedEngine:
             if self.resident.hosts is None:
                 self.begin_round()                    # nothing streamed: every row goes up now
             self.resident.mix(mode, timing=timing)
+            if self.momentum and len(self.stepped):
+                self.mstate["first"] = False          # the momentum step of this round is enqueued
+                self.mstate["dirty"] = True
             if not defer:
                 self.resident.wait_all()
                 return self.resident.last_timing
@@ -336,8 +475,8 @@ class _FusedEngine:
 
     def same_models(self, nodes, params):
         models = [n["model"] for n in nodes]
-        return (_grad_key(params) + (float(params["algorithm"]["learning-rate"]), self.plain)
-                == self.key and self.slab.owns(models) and self.gslab.owns(models))
+        return (_fused_key(params, self.plain) == self.key and self.slab.owns(models)
+                and self.gslab.owns(models))
 
     def valid_for(self, nodes, topology, params):
         return (topology is self.topology and id(topology.get("weights")) == self.weights_id
@@ -359,15 +498,48 @@ class _FusedEngine:
         self.weights_id = id(topology.get("weights"))
 
 
+class _NoFit(RuntimeError):
+    """_FusedEngine: the resident buffers this round needs cannot be had (see the class)."""
+
+
+def _fused_key(params, plain):
+    """What a _FusedEngine is built for besides its nodes and graph: a change rebuilds it."""
+    return _grad_key(params) + (float(params["algorithm"]["learning-rate"]), plain,
+                                _momentum(params))
+
+
 _fused_engines = {}
+
+
+def _drop_fused(key):
+    """Forget the engine under `key`; one that holds momentum state first hands it back to the
+    optimizers (export_momentum), so CPU steps or a new engine carry on from it."""
+    eng = _fused_engines.pop(key, None)
+    if eng is not None:
+        eng.export_momentum()
+
+
+def sync_optimizer_state(nodes=None):
+    """Wait for the last round and write the momentum buffers the device steps keep in HBM into
+    the optimizers of `nodes` (default: every node list) as optimizer.state[p]['momentum_buffer'],
+    the tensors torch's own step would hold; call it before reading or saving optimizer state.
+    The plugin does so itself whenever it drops an engine or goes back to CPU steps."""
+    for eng in list(_fused_engines.values()):
+        if nodes is None or eng.slab.owns([n["model"] for n in nodes]):
+            eng.export_momentum()
 
 
 def fused_round(nodes, topology, params):
     """gradient(nodes, topology, params) followed by average(nodes, topology, params), as one
     device round: gradient mean, SGD step and mixing on each column window, one H2D of parameters
-    and gradients and one D2H of the mixed parameters (niidmix.slab.FusedRoundRunner)."""
+    and gradients and one D2H of the mixed parameters (niidmix.slab.FusedRoundRunner).  With
+    --learning-momentum only the resident round does this; without it: the two calls."""
     synchronize()
     eng = _fused_engine(nodes, topology, params)
+    if eng is None:
+        gradient(nodes, topology, params)
+        average(nodes, topology, params)
+        return
     logging.info("  fused gradient %s + SGD step + mixing (GPU, %s)", eng.plan.kind, _mode(params))
     t = eng.run(_mode(params), timing=logging.getLogger().isEnabledFor(logging.INFO))
     if t:
@@ -382,11 +554,18 @@ def _fused_engine(nodes, topology, params, plain=False):
         eng.set_topology(topology)                   # same nodes, new graph (--randomize)
     if eng is None or not eng.valid_for(nodes, topology, params):
         synchronize()
-        eng = _FusedEngine(nodes, topology, params, _devices(nodes), plain=plain)
-        _fused_engines.pop(key, None)
+        eng = None
+        _drop_fused(key)                             # its momentum state: back to the optimizers
+        try:
+            eng = _FusedEngine(nodes, topology, params, _devices(nodes), plain=plain)
+        except _NoFit as e:                          # CPU step (momentum: unfused) from now on
+            logging.info("  no device step for this node list: %s", e.args[0])
+            if e.args[1]:                            # no room in HBM: not tried again
+                _no_device_step[id(nodes)] = weakref.ref(nodes[0]["model"])
+            return None
         _fused_engines[key] = eng
         while len(_fused_engines) > MAX_ENGINES:
-            _fused_engines.pop(next(iter(_fused_engines)))
+            _drop_fused(next(iter(_fused_engines)))
     return eng
 
 
@@ -740,16 +919,21 @@ def next_step(state, params, rundir):
     if streamed and _device_step_ok(params, active):
         # ... with the optimizer step on the device: each node's gradient row goes up right after
         # its backward(), the parameters stay resident (_FusedEngine(plain=True))
+        # (None: the buffers do not fit: CPU step, windowed or resident mixing)
         feng = _fused_engine(active, topology, params, plain=True)
-        if feng.resident is None:                 # the buffers do not fit: CPU step, windowed
-            _fused_engines.pop((id(active), True), None)
-            _no_device_step[id(active)] = weakref.ref(active[0]["model"])
-            feng = None
-    eng = _engine(active, topology) if streamed and feng is None else None
-    # gradient averaging, momentum 0: the fused device round, row-streamed too — each node's
-    # parameter and gradient rows go up right after its backward()
-    if feng is None and not sample and _fused_ok(params) and _row_streamed(params):
+    # gradient averaging: the fused device round, row-streamed too — each node's parameter and
+    # gradient rows go up right after its backward()
+    fused = not sample and _fused_ok(params, active)
+    if feng is None and fused and _row_streamed(params):
         feng = _fused_engine(active, topology, params)
+        fused = feng is not None
+    # a round that no longer takes the device step hands its momentum state to the optimizers
+    for plain in (True, False):
+        if (feng is None or feng.plain != plain) and _holds_momentum(active, plain) and \
+                not (fused and not plain):
+            synchronize()
+            _drop_fused((id(active), plain))
+    eng = _engine(active, topology) if streamed and feng is None else None
     if eng is None and feng is None:
         synchronize()
     if feng is not None:
@@ -798,7 +982,7 @@ def next_step(state, params, rundir):
             round_stats["enqueue_s"] += clock() - t0
             round_stats["rounds"] += 1
             eng, defer = feng, True
-        elif _fused_ok(params):
+        elif fused:
             fused_round(active, topology, params)         # ★ GPU: gradient + step + mixing
         elif eng is not None:
             t0 = clock()

@@ -18,6 +18,8 @@ Ops (registered in the `niidmix` namespace, usable as torch.ops.niidmix.*):
   mean_rows(x, mean, dist2, mode)                   k_mean_cols + k_row_dist2
   grad_segment_mean(g, seg_ptr, seg_row, out)       k_grad_segment_mean (clique gradient mean)
   sgd_step_rows(p, g, rows, neg_lr)                 k_sgd_step_rows (the optimizer step, fused round)
+  sgd_momentum_step_rows(p, g, buf, rows, neg_lr, momentum, first)
+                                                    k_sgd_momentum_step_rows (--learning-momentum)
   mix_csr(..., mode | MEAN)                         per-row gradient mean (unbiased / removed edges)
 All ops launch on torch's current HIP stream of the input's device, never synchronise, and raise
 RuntimeError (TORCH_CHECK-style) on bad arguments.  They accept HIP tensors only: there is no CPU
@@ -536,6 +538,22 @@ def sgd_step_rows(p: torch.Tensor, g: torch.Tensor, rows: torch.Tensor, neg_lr: 
     rc = _lib.lib.niidmix_sgd_step_rows_f32(p.data_ptr(), _ld(p), g.data_ptr(), _ld(g), p.shape[1],
                                             rows.data_ptr(), rows.numel(), float(neg_lr), _stream(p))
     _lib.check(rc, "niidmix::sgd_step_rows")
+
+
+@torch.library.custom_op("niidmix::sgd_momentum_step_rows", mutates_args=("p", "buf"))
+def sgd_momentum_step_rows(p: torch.Tensor, g: torch.Tensor, buf: torch.Tensor, rows: torch.Tensor,
+                           neg_lr: float, momentum: float, first: bool) -> None:
+    """torch.optim.SGD(momentum=m) on the listed rows, in place: buf = g (first) or
+    fl(fl(m * buf) + g), then p = fma(neg_lr, buf, p) (include/niidmix.h)."""
+    _slab("p", p)
+    _slab("g", g, rows=p.shape[0], cols=p.shape[1])
+    _slab("buf", buf, rows=p.shape[0], cols=p.shape[1])
+    _req(g.device == p.device and buf.device == p.device, "p, g and buf must be on the same device")
+    _vec("rows", rows, torch.int32, p.device)
+    rc = _lib.lib.niidmix_sgd_momentum_step_rows_f32(
+        p.data_ptr(), _ld(p), g.data_ptr(), _ld(g), buf.data_ptr(), _ld(buf), p.shape[1],
+        rows.data_ptr(), rows.numel(), float(neg_lr), float(momentum), int(bool(first)), _stream(p))
+    _lib.check(rc, "niidmix::sgd_momentum_step_rows")
 
 
 # ------------------------------------------------------------------------------------------------

@@ -631,15 +631,28 @@ def mixing_op(dev, part, mixer):
     return op
 
 
-def fused_op(dev, part, grad_op, step_rows, lr, mixer, grad_writeback=True):
+def fused_op(dev, part, grad_op, step_rows, lr, mixer, grad_writeback=True, momentum=0.0,
+             mstate=None):
     """ResidentRound device op of the round with gradient averaging (FusedRoundRunner's per-window
     arithmetic on the whole stripe): ins = [params, grads] -> averaged gradients (outs[1]) -> SGD
     step of the stepped rows on the parameters in place -> mixing into outs[0].  grad_op None: the
-    plain round's device step (each node's own gradient, d_sgd.py:51-52), no averaging."""
+    plain round's device step (each node's own gradient, d_sgd.py:51-52), no averaging.
+
+    momentum != 0 (--learning-momentum): the step is torch.optim.SGD(momentum)'s
+    (ops.sgd_momentum_step_rows) and the stripe owns a persistent [n, w] momentum buffer,
+    part['mbuf'], which stays in HBM between rounds.  mstate (shared by the stripes of one engine):
+    'first' -- no momentum step has run and no optimizer state was adopted: the step copies the
+    gradient into the buffer; the engine clears it after the round."""
     from . import ops
     part["mixer"] = mixer
     rows = torch.as_tensor(step_rows, dtype=torch.int32).to(dev)
     neg_lr = -float(lr)
+    momentum = float(momentum)
+    if momentum != 0.0:
+        part["mbuf"] = torch.zeros_like(part["ins"][0])
+    own_state = mstate is None                # a stand-alone op keeps (and clears) its own flag
+    if own_state:
+        mstate = {"first": True}
 
     def op(ins, outs, mode, kernel):
         xp, xg = ins
@@ -653,7 +666,12 @@ def fused_op(dev, part, grad_op, step_rows, lr, mixer, grad_writeback=True):
             gm = part["dm"]
         if grad_op is not None:
             grad_op(xg, out=gm)
-        if rows.numel():
+        if rows.numel() and momentum != 0.0:
+            ops.sgd_momentum_step_rows(xp, gm, part["mbuf"], rows, neg_lr, momentum,
+                                       bool(mstate["first"]))
+            if own_state:
+                mstate["first"] = False
+        elif rows.numel():
             ops.sgd_step_rows(xp, gm, rows, neg_lr)
         part["mixer"](xp, out=outs[0], mode=mode, kernel=kernel)
     return op
