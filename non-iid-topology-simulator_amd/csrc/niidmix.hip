@@ -4061,6 +4061,10 @@ const RcclApi *rccl_api() {
     return ok ? &api : nullptr;
 }
 
+// ----------------------------------------------------------------------------------------------
+// Host side.  The argument checks, environment readers and the value-to-template dispatch that
+// the C entry points share.  A check returns NIIDMIX_OK or the code set_error recorded; the entry
+// points call them in the order their errors are documented to take precedence.
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 int64_t grid_for(int64_t items) { return items < kMaxGrid ? ((items + 7) / 8) * 8 : kMaxGrid; }
@@ -4069,10 +4073,156 @@ bool overlaps(const float *a, int64_t a_elems, const float *b, int64_t b_elems) 
     return a < b + b_elems && b < a + a_elems;
 }
 
+// floats from the first element of a [n_rows, ld] slab to the end of its last row of p columns
+int64_t slab_extent(int64_t n_rows, int64_t ld, int64_t p) { return (n_rows - 1) * ld + p; }
+
+// Integer tuning variable: its value when it is set and among `allowed` (any value when the list
+// is empty), else dflt.
+int env_int(const char *name, int dflt, std::initializer_list<int> allowed = {}) {
+    const char *e = getenv(name);
+    if (!e) return dflt;
+    const int v = atoi(e);
+    if (allowed.size() == 0) return v;
+    for (int a : allowed) if (a == v) return v;
+    return dflt;
+}
+
+// Tuple-valued tuning variable: sscanf of its value, 0 fields when it is unset.
+__attribute__((format(scanf, 2, 3))) int env_scan(const char *name, const char *fmt, ...) {
+    const char *e = getenv(name);
+    if (!e) return 0;
+    va_list ap;
+    va_start(ap, fmt);
+    const int n = vsscanf(e, fmt, ap);
+    va_end(ap);
+    return n < 0 ? 0 : n;
+}
+
+// Run-time value -> template argument: calls f(std::integral_constant<V>) for the first V of the
+// list equal to v and returns its result (a kernel pointer or a return code); a value-initialised
+// result (nullptr / 0) when v is not in the list.  Nested, the lists give a cross product; a
+// restricted set of tuples is dispatched over one list of its members.
+template <auto V0, auto... Vs, class T, class F>
+auto pick(T v, F &&f) {
+    decltype(f(std::integral_constant<decltype(V0), V0>{})) r{};
+    auto match = [&](auto c) { return v == c() ? (r = f(c), true) : false; };
+    (void)(match(std::integral_constant<decltype(V0), V0>{}) || ... ||
+           match(std::integral_constant<decltype(Vs), Vs>{}));
+    return r;
+}
+
+int cu_count() {
+    static int n_cu = 0;
+    if (!n_cu) {
+        int dev = 0;
+        (void)hipGetDevice(&dev);
+        if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu < 1) n_cu = 256;
+    }
+    return n_cu;
+}
+
+// more than the default 64 KiB of dynamic LDS has to be granted per kernel
+template <class K>
+int lds_opt_in(K kfn, size_t lds, const char *name) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return set_error(NIIDMIX_EHIP, "%s: %zu B of LDS refused", name, lds);
+    return NIIDMIX_OK;
+}
+
+// Removes the flags an entry point accepts from *mode and returns them.
+int strip_flags(int *mode, int accepted) {
+    const int flags = *mode & accepted;
+    *mode &= ~accepted;
+    return flags;
+}
+
+int check_mode(int mode) {
+    if (mode != NIIDMIX_MODE_EXACT && mode != NIIDMIX_MODE_FAST)
+        return set_error(NIIDMIX_EINVAL, "unknown mode %d", mode);
+    return NIIDMIX_OK;
+}
+
+int check_groups(int n_groups) {
+    if (n_groups < 1 || n_groups > 4) return set_error(NIIDMIX_EUNSUPPORTED, "n_groups %d not in 1..4", n_groups);
+    return NIIDMIX_OK;
+}
+
+constexpr const char *kMixAlias = "x and y overlap (mixing is out-of-place / Jacobi)";
+
+int check_ld(int64_t ld_a, int64_t ld_b, int64_t p, const char *width = "p") {
+    if (ld_a < p || ld_b < p) return set_error(NIIDMIX_EINVAL, "leading dimension < %s", width);
+    return NIIDMIX_OK;
+}
+
+int check_overlap(const float *a, int64_t ld_a, const float *b, int64_t ld_b, int64_t n_rows,
+                  int64_t p, const char *alias_msg = kMixAlias) {
+    if (overlaps(a, slab_extent(n_rows, ld_a, p), b, slab_extent(n_rows, ld_b, p)))
+        return set_error(NIIDMIX_EALIAS, "%s", alias_msg);
+    return NIIDMIX_OK;
+}
+
+// Two row-major slabs [n_rows, ld] of p columns: ld >= p, then no overlap over their extents.
+int check_slab_pair(const float *a, int64_t ld_a, const float *b, int64_t ld_b, int64_t n_rows,
+                    int64_t p, const char *alias_msg = kMixAlias) {
+    if (int rc = check_ld(ld_a, ld_b, p)) return rc;
+    return check_overlap(a, ld_a, b, ld_b, n_rows, p, alias_msg);
+}
+
+// Two column-blocked slabs [p / block_cols, n_rows, block_cols] with row stride ld and a block
+// stride each: block_cols a power of two >= min_bc, ld >= block_cols, block strides >= ld, then no
+// overlap over the extents, each slab with its own block stride.
+int check_blocked_pair(const float *a, const float *b, int64_t n_rows, int64_t p, int64_t ld,
+                       int64_t block_cols, int64_t bs_a, int64_t bs_b, int64_t min_bc,
+                       const char *ld_msg, const char *bs_msg, const char *alias_msg) {
+    if (block_cols < min_bc || (block_cols & (block_cols - 1)))
+        return set_error(NIIDMIX_EINVAL, "block_cols %lld: a power of two >= %lld", (long long)block_cols,
+                         (long long)min_bc);
+    if (ld < block_cols) return set_error(NIIDMIX_EINVAL, "%s", ld_msg);
+    if (bs_a < ld || bs_b < ld) return set_error(NIIDMIX_EINVAL, "%s", bs_msg);
+    const int64_t k_blocks = (p + block_cols - 1) / block_cols;
+    const int64_t in_block = slab_extent(n_rows, ld, block_cols);
+    if (overlaps(a, (k_blocks - 1) * bs_a + in_block, b, (k_blocks - 1) * bs_b + in_block))
+        return set_error(NIIDMIX_EALIAS, "%s", alias_msg);
+    return NIIDMIX_OK;
+}
+
+// Head of both clique entry points: plan, sizes, the empty case (kEmpty: the caller returns
+// NIIDMIX_OK), then the pointers.
+constexpr int kEmpty = -1;
+int check_clique_plan(const float *x, const float *y, int64_t p, const niidmix_clique_plan *plan) {
+    if (!plan) return set_error(NIIDMIX_EINVAL, "null plan");
+    if (p < 0 || plan->n_cliques < 0 || plan->n_members < 0) return set_error(NIIDMIX_EINVAL, "negative size");
+    if (plan->n_cliques == 0 || p == 0) return kEmpty;
+    if (!x || !y || !plan->clique_ptr || !plan->member_row || !plan->member_group || !plan->coef ||
+        !plan->res_ptr || (!plan->res_col && plan->n_members > 0) || (!plan->res_val && plan->n_members > 0) ||
+        (!plan->res_member && plan->n_members > 0) || !plan->csr_ptr || !plan->csr_col || !plan->csr_val)
+        return set_error(NIIDMIX_EINVAL, "null pointer");
+    return NIIDMIX_OK;
+}
+
+// Floats per lane the operands allow: 4 when every size / stride is a multiple of 4 floats and
+// every pointer 16-B aligned, 2 for multiples of 2 and 8 B, else 1.  Callers pass the operands
+// their kernel reads at that width.
+int vec_width(std::initializer_list<int64_t> sizes, std::initializer_list<const void *> ptrs) {
+    uintptr_t s = 0, a = 0;
+    for (int64_t v : sizes) s |= (uintptr_t)v;
+    for (const void *q : ptrs) a |= reinterpret_cast<uintptr_t>(q);
+    return !(s & 3) && !(a & 15) ? 4 : !(s & 1) && !(a & 7) ? 2 : 1;
+}
+
+// Grid of the row-chunk kernels (k_sgd_step_rows, k_sgd_momentum_step_rows, k_update_rows,
+// k_grad_segment_mean): one item per (row, chunk of 256 lanes x 4 or 1 columns), grid-stride above
+// kMaxGrid.
+dim3 row_chunk_grid(int64_t n_rows, int64_t n_cols, bool vec4, int64_t *n_chunks) {
+    const int64_t cols = vec4 ? 1024 : 256;
+    *n_chunks = (n_cols + cols - 1) / cols;
+    const int64_t items = n_rows * *n_chunks;
+    return dim3((unsigned)(items < kMaxGrid ? items : kMaxGrid));
+}
+
 // NIIDMIX_CLIQUE_SKEW=<chunks> (multiple of 8; tuning): per-clique chunk rotation, 0 = off
 int64_t clique_skew() {
-    const char *e = getenv("NIIDMIX_CLIQUE_SKEW");
-    const int64_t v = e ? atoll(e) : 0;
+    const int64_t v = env_int("NIIDMIX_CLIQUE_SKEW", 0);
     return v > 0 ? (v + 7) / 8 * 8 : 0;
 }
 
@@ -4083,30 +4233,19 @@ struct BlockGeom {            // column blocking of the slabs (row-major: one bl
     int cpb_shift(int v) const { return bc_shift >= 62 ? 62 : bc_shift - (v == 4 ? 8 : v == 2 ? 7 : 6); }
 };
 
-template <int WAVES, int RPW, int G, int OCC, int RW, int FL, int V>
-void launch_clique(const float *x, int64_t ld_x, float *y, int64_t ld_y, int64_t p,
-                   const niidmix_clique_plan *pl, int64_t n_items, hipStream_t s, const BlockGeom &bg) {
-    const int64_t grid = n_items;   // one block per (clique, chunk) item; < 2^31 checked by the caller
-    hipLaunchKernelGGL((k_mix_clique<WAVES, RPW, G, OCC, RW, FL, V>), dim3((unsigned)grid),
-                       dim3(WAVES * 64), 0, s, x, ld_x, y, ld_y, p, pl->n_cliques, pl->clique_ptr,
-                       pl->member_row, pl->member_group, pl->coef, pl->res_ptr, pl->res_col,
-                       pl->res_val, pl->res_member, n_items, clique_skew(), bg.cpb_shift(V), bg.bs_x,
-                       bg.bs_y, pl->csr_ptr, pl->csr_col, pl->csr_val);
-}
-
 template <int WAVES, int RPW, int OCC, int RW, int FL, int V>
 int launch_clique_g(const float *x, int64_t ld_x, float *y, int64_t ld_y, int64_t p,
                     const niidmix_clique_plan *pl, hipStream_t s, const BlockGeom &bg) {
     const int64_t n_chunks = (p + 64 * V - 1) / (64 * V);
+    // one block per (clique, chunk) item
     const int64_t n_items = (int64_t)pl->n_cliques * ((n_chunks + 7) / 8) * 8;
     if (n_items > 0x7fffffffLL) return set_error(NIIDMIX_EUNSUPPORTED, "too many (clique, chunk) items for one grid");
-    switch (pl->n_groups) {
-        case 1: launch_clique<WAVES, RPW, 1, OCC, RW, FL, V>(x, ld_x, y, ld_y, p, pl, n_items, s, bg); break;
-        case 2: launch_clique<WAVES, RPW, 2, OCC, RW, FL, V>(x, ld_x, y, ld_y, p, pl, n_items, s, bg); break;
-        case 3: launch_clique<WAVES, RPW, 3, OCC, RW, FL, V>(x, ld_x, y, ld_y, p, pl, n_items, s, bg); break;
-        case 4: launch_clique<WAVES, RPW, 4, OCC, RW, FL, V>(x, ld_x, y, ld_y, p, pl, n_items, s, bg); break;
-        default: return set_error(NIIDMIX_EUNSUPPORTED, "n_groups %d not in 1..4", pl->n_groups);
-    }
+    if (int rc = check_groups(pl->n_groups)) return rc;
+    auto kfn = pick<1, 2, 3, 4>(pl->n_groups, [](auto G) { return k_mix_clique<WAVES, RPW, G(), OCC, RW, FL, V>; });
+    hipLaunchKernelGGL(kfn, dim3((unsigned)n_items), dim3(WAVES * 64), 0, s, x, ld_x, y, ld_y, p,
+                       pl->n_cliques, pl->clique_ptr, pl->member_row, pl->member_group, pl->coef,
+                       pl->res_ptr, pl->res_col, pl->res_val, pl->res_member, n_items, clique_skew(),
+                       bg.cpb_shift(V), bg.bs_x, bg.bs_y, pl->csr_ptr, pl->csr_col, pl->csr_val);
     return check_launch("k_mix_clique");
 }
 
@@ -4114,9 +4253,10 @@ int launch_clique_g(const float *x, int64_t ld_x, float *y, int64_t ld_y, int64_
 // of <= 112 members).  Chosen when a 256-column chunk of all member rows (n_members KB) would not
 // fit an XCD's L2; NIIDMIX_CLIQUE_Q=1 disables it, =4 forces it (A/B).
 constexpr int64_t kQRowsMin = 4096;
-template <int G, int W, int R, int OCC, int GA, int Q, int MS = 1>
-int launch_clique_q(const float *x, int64_t ld_x, float *y, int64_t ld_y, int64_t p,
-                    const niidmix_clique_plan *pl, hipStream_t s, const BlockGeom &bg) {
+template <int W, int R, int OCC, int GA, int Q = 4, int MS = 1>
+int launch_clique_q_g(const float *x, int64_t ld_x, float *y, int64_t ld_y, int64_t p,
+                      const niidmix_clique_plan *pl, hipStream_t s, const BlockGeom &bg) {
+    if (int rc = check_groups(pl->n_groups)) return rc;
     constexpr int64_t CW = 4 * (64 / Q);
     constexpr int CW_SHIFT = Q == 8 ? 5 : 6;
     if (bg.bc_shift < CW_SHIFT) return set_error(NIIDMIX_EINVAL, "%d-column items do not fit %d-column blocks", (int)CW, 1 << bg.bc_shift);
@@ -4130,35 +4270,22 @@ int launch_clique_q(const float *x, int64_t ld_x, float *y, int64_t ld_y, int64_
                        bg.bs_y * 4 <= (int64_t)0xffffffffLL;
     // NIIDMIX_Q_PERSIST=k (tuning): k blocks per CU loop over the items instead of one block each
     int64_t grid = n_items;
-    if (const char *e = getenv("NIIDMIX_Q_PERSIST")) {
-        const int k = atoi(e);
-        int dev = 0, n_cu = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu < 1) n_cu = 256;
-        if (k > 0 && (int64_t)k * n_cu < n_items) grid = (int64_t)k * n_cu / 8 * 8;
-    }
-#define NIIDMIX_CQ(O) hipLaunchKernelGGL((k_mix_clique_q<W, R, G, Q, OCC, GA, O, MS>), dim3((unsigned)grid), dim3(W * 64), 0, s, x, ld_x, y, ld_y, p, pl->n_cliques, pl->clique_ptr, pl->member_row, pl->member_group, pl->coef, pl->res_ptr, pl->res_col, pl->res_val, n_cg, n_items, cpb, bg.bs_x, bg.bs_y, pl->csr_ptr, pl->csr_col, pl->csr_val)
-    if (off32) NIIDMIX_CQ(true); else NIIDMIX_CQ(false);
-#undef NIIDMIX_CQ
+    const int k = env_int("NIIDMIX_Q_PERSIST", 0);
+    if (k > 0 && (int64_t)k * cu_count() < n_items) grid = (int64_t)k * cu_count() / 8 * 8;
+    auto kfn = pick<1, 2, 3, 4>(pl->n_groups, [&](auto G) {
+        return pick<true, false>(off32, [&](auto O) { return k_mix_clique_q<W, R, G(), Q, OCC, GA, O(), MS>; });
+    });
+    hipLaunchKernelGGL(kfn, dim3((unsigned)grid), dim3(W * 64), 0, s, x, ld_x, y, ld_y, p, pl->n_cliques,
+                       pl->clique_ptr, pl->member_row, pl->member_group, pl->coef, pl->res_ptr,
+                       pl->res_col, pl->res_val, n_cg, n_items, cpb, bg.bs_x, bg.bs_y, pl->csr_ptr,
+                       pl->csr_col, pl->csr_val);
     return check_launch("k_mix_clique_q");
-}
-
-template <int W, int R, int OCC, int GA, int Q = 4, int MS = 1>
-int launch_clique_q_g(const float *x, int64_t ld_x, float *y, int64_t ld_y, int64_t p,
-                      const niidmix_clique_plan *pl, hipStream_t s, const BlockGeom &bg) {
-    switch (pl->n_groups) {
-        case 1: return launch_clique_q<1, W, R, OCC, GA, Q, MS>(x, ld_x, y, ld_y, p, pl, s, bg);
-        case 2: return launch_clique_q<2, W, R, OCC, GA, Q, MS>(x, ld_x, y, ld_y, p, pl, s, bg);
-        case 3: return launch_clique_q<3, W, R, OCC, GA, Q, MS>(x, ld_x, y, ld_y, p, pl, s, bg);
-        case 4: return launch_clique_q<4, W, R, OCC, GA, Q, MS>(x, ld_x, y, ld_y, p, pl, s, bg);
-        default: return set_error(NIIDMIX_EUNSUPPORTED, "n_groups %d not in 1..4", pl->n_groups);
-    }
 }
 
 bool use_clique_q(const niidmix_clique_plan *pl, const BlockGeom &bg) {
     if (pl->max_clique > 112 || bg.bc_shift < 6) return false;
     if (bg.bc_shift < 8) return true;          // 64- / 128-column blocks: only this tile reads them
-    if (const char *e = getenv("NIIDMIX_CLIQUE_Q")) return atoi(e) == 4;
+    if (getenv("NIIDMIX_CLIQUE_Q")) return env_int("NIIDMIX_CLIQUE_Q", 0) == 4;
     return pl->n_members >= kQRowsMin;
 }
 
@@ -4173,7 +4300,7 @@ int launch_clique_tiled(const float *x, int64_t ld_x, float *y, int64_t ld_y, in
                         const niidmix_clique_plan *pl, bool vec4, hipStream_t s,
                         const BlockGeom &bg = BlockGeom()) {
     int waves = 0, rpw = 0, occ = 0, rw = 0, ob = 0, v = 0;
-    if (const char *e = getenv("NIIDMIX_CLIQUE_TILE")) sscanf(e, "%dx%dx%dx%dx%dx%d", &waves, &rpw, &occ, &rw, &ob, &v);
+    env_scan("NIIDMIX_CLIQUE_TILE", "%dx%dx%dx%dx%dx%d", &waves, &rpw, &occ, &rw, &ob, &v);
     const int vmax = bg.bc_shift >= 8 ? 4 : bg.bc_shift == 7 ? 2 : 1;    // chunks never straddle blocks
     if (v == 0) v = vmax;
     if (v > vmax) return set_error(NIIDMIX_EINVAL, "%d columns per lane do not fit %d-column blocks", v, 1 << bg.bc_shift);
@@ -4182,7 +4309,7 @@ int launch_clique_tiled(const float *x, int64_t ld_x, float *y, int64_t ld_y, in
     if (waves == 0 && use_clique_q(pl, bg)) {
         // tile: <waves>x<slots>x<occupancy>x<gateway gathers per batch>; NIIDMIX_CLIQUE_QT overrides
         int qw = 0, qr = 0, qo = 0, qg = 0, qq = 4;
-        if (const char *e = getenv("NIIDMIX_CLIQUE_QT")) sscanf(e, "%dx%dx%dx%dx%d", &qw, &qr, &qo, &qg, &qq);
+        env_scan("NIIDMIX_CLIQUE_QT", "%dx%dx%dx%dx%d", &qw, &qr, &qo, &qg, &qq);
         if (qw == 0) {
             if (mc <= 104) { qw = 8; qr = 13; qo = 4; qg = 13; }
             else { qw = 16; qr = 7; qo = 8; qg = 2; }
@@ -4358,55 +4485,33 @@ int niidmix_mix_csr_f32(const float *x, int64_t ld_x, float *y, int64_t ld_y, in
                         int64_t p, const int64_t *row_ptr, const int32_t *col, const float *val,
                         int mode, void *stream) {
     if (n_rows < 0 || p < 0) return set_error(NIIDMIX_EINVAL, "negative size");
-    const int kflags = mode & (NIIDMIX_FLAG_AVERAGE_ONLY | NIIDMIX_FLAG_MEAN);
-    const int low_degree = (mode & NIIDMIX_FLAG_LOW_DEGREE) ? 1 : 0;
+    const int flags = strip_flags(&mode, NIIDMIX_FLAG_AVERAGE_ONLY | NIIDMIX_FLAG_LOW_DEGREE | NIIDMIX_FLAG_MEAN);
+    const int kflags = flags & (NIIDMIX_FLAG_AVERAGE_ONLY | NIIDMIX_FLAG_MEAN);
     if ((kflags & NIIDMIX_FLAG_AVERAGE_ONLY) && (kflags & NIIDMIX_FLAG_MEAN))
         return set_error(NIIDMIX_EINVAL, "AVERAGE_ONLY and MEAN are exclusive");
-    mode &= ~(NIIDMIX_FLAG_AVERAGE_ONLY | NIIDMIX_FLAG_LOW_DEGREE | NIIDMIX_FLAG_MEAN);
-    if (mode != NIIDMIX_MODE_EXACT && mode != NIIDMIX_MODE_FAST)
-        return set_error(NIIDMIX_EINVAL, "unknown mode %d", mode);
+    if (int rc = check_mode(mode)) return rc;
     if (n_rows == 0 || p == 0) return NIIDMIX_OK;
     if (!x || !y || !row_ptr || !col || !val) return set_error(NIIDMIX_EINVAL, "null pointer");
-    if (ld_x < p || ld_y < p) return set_error(NIIDMIX_EINVAL, "leading dimension < p");
-    if (overlaps(x, (n_rows - 1) * ld_x + p, y, (n_rows - 1) * ld_y + p))
-        return set_error(NIIDMIX_EALIAS, "x and y overlap (mixing is out-of-place / Jacobi)");
+    if (int rc = check_slab_pair(x, ld_x, y, ld_y, n_rows, p)) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const uintptr_t align = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y);
-    const int vw = (p % 4 == 0 && ld_x % 4 == 0 && ld_y % 4 == 0 && (align & 15) == 0) ? 4
-                 : (p % 2 == 0 && ld_x % 2 == 0 && ld_y % 2 == 0 && (align & 7) == 0) ? 2 : 1;
+    const int vw = vec_width({p, ld_x, ld_y}, {x, y});
+    // gathers in flight per batch: 4 when the caller flags a low-degree graph (ring, grid), else 8
+    const bool lowdeg = (flags & NIIDMIX_FLAG_LOW_DEGREE) != 0;
     // work-item width: 2 chunks per wave for a low-degree graph (ring-100, P = 62006: 15.7 us vs
     // 16.6 us for 1 chunk and 16.6 us for 4 chunks, whose 142 VGPRs cap occupancy at 3 waves/SIMD;
-    // profiles/r01/ring100_spl.txt), else 1.  NIIDMIX_CSR_SPL=1|2|4 overrides (tuning).
-    const char *spl_env = getenv("NIIDMIX_CSR_SPL");
-    const int spl = spl_env ? (atoi(spl_env) == 4 ? 4 : atoi(spl_env) == 2 ? 2 : 1) : (low_degree ? 2 : 1);
+    // profiles/r01/ring100_spl.txt), else 1.  NIIDMIX_CSR_SPL=1|2|4 overrides (tuning; any other
+    // value means 1).
+    int spl = lowdeg ? 2 : 1;
+    if (getenv("NIIDMIX_CSR_SPL")) spl = env_int("NIIDMIX_CSR_SPL", 1, {1, 2, 4});
     const int64_t n_chunks = (p + kChunk * spl - 1) / (kChunk * spl);
     const int64_t n_row_groups = (n_rows + 3) / 4;
     const int64_t n_items = n_row_groups * ((n_chunks + 7) / 8) * 8;
-    const dim3 grid((unsigned)grid_for(n_items)), block(256);
-    // gathers in flight per batch: 4 when the caller flags a low-degree graph (ring, grid), else 8
-    const bool lowdeg = low_degree != 0;
-#define NIIDMIX_CSR(E, V, S, UU) hipLaunchKernelGGL((k_mix_csr<E, V, S, UU>), grid, block, 0, s, x, ld_x, y, ld_y, n_rows, p, row_ptr, col, val, n_row_groups, n_items, kflags)
-#define NIIDMIX_CSR_U(E, V, S) do { if (lowdeg) NIIDMIX_CSR(E, V, S, 4); else NIIDMIX_CSR(E, V, S, 8); } while (0)
-#define NIIDMIX_CSR_S(E, V) do { if (spl == 4) NIIDMIX_CSR_U(E, V, 4); else if (spl == 2) NIIDMIX_CSR_U(E, V, 2); else NIIDMIX_CSR_U(E, V, 1); } while (0)
-    if (mode == NIIDMIX_MODE_EXACT) {
-        if (vw == 4) NIIDMIX_CSR_S(true, 4); else if (vw == 2) NIIDMIX_CSR_S(true, 2); else NIIDMIX_CSR_S(true, 1);
-    } else {
-        if (vw == 4) NIIDMIX_CSR_S(false, 4); else if (vw == 2) NIIDMIX_CSR_S(false, 2); else NIIDMIX_CSR_S(false, 1);
-    }
-#undef NIIDMIX_CSR_U
-#undef NIIDMIX_CSR_S
-#undef NIIDMIX_CSR
+    auto kfn = pick<true, false>(mode == NIIDMIX_MODE_EXACT, [&](auto E) { return pick<4, 2, 1>(vw, [&](auto V) {
+        return pick<4, 2, 1>(spl, [&](auto S) { return pick<true, false>(lowdeg, [&](auto L) {
+            return k_mix_csr<E(), V(), S(), L() ? 4 : 8>; }); }); }); });
+    hipLaunchKernelGGL(kfn, dim3((unsigned)grid_for(n_items)), dim3(256), 0, s, x, ld_x, y, ld_y, n_rows, p,
+                       row_ptr, col, val, n_row_groups, n_items, kflags);
     return check_launch("k_mix_csr");
-}
-
-static int cu_count() {
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu < 1) n_cu = 256;
-    }
-    return n_cu;
 }
 
 // One-pass big-clique launch (k_mix_bigclique_reg) for cliques of 257..1024 members: 2 blocks of
@@ -4426,76 +4531,44 @@ static int launch_bigclique_reg(const float *x, int64_t ld_x, float *y, int64_t 
     const int contig = map_env ? (!strcmp(map_env, "contig") ? 1 : 0) : (bc_shift >= 62 ? 1 : 0);
     int64_t gsz = (int64_t)bpc * cu_count();
     if (gsz > items) gsz = items;
-    const dim3 grid((unsigned)gsz), block(kBigRegWaves * 64);
+    if (int rc = check_groups(plan->n_groups)) return rc;
     // float4 lanes (k_mix_bigclique_v4) on column-blocked slabs whose p, ld and block strides are
     // multiples of 4 floats, 16-B aligned: the default for one-group cliques (FC-1000, P = 2^20,
     // same box: 1.355 vs 1.407 ms, profiles/r06/bigclique_v4/); NIIDMIX_BIGREG_V4=0 / 1 turns it
     // off / on for every group count
-    const char *v4_env = getenv("NIIDMIX_BIGREG_V4");
-    const bool v4 = v4_env ? atoi(v4_env) == 1 : plan->n_groups == 1;
-    if (v4 && p % 4 == 0 && ld_x % 4 == 0 && ld_y % 4 == 0 && bs_x % 4 == 0 &&
-        bs_y % 4 == 0 && aligned16(x) && aligned16(y) && bc_shift < 62 &&
-        bs_x * 4 <= (int64_t)0xffffffffLL && bs_y * 4 <= (int64_t)0xffffffffLL) {
-#define NIIDMIX_BIGV4(G, OCC) hipLaunchKernelGGL((k_mix_bigclique_v4<G, OCC>), grid, block, 0, s, x, ld_x, y, ld_y, p, plan->n_cliques, plan->clique_ptr, plan->member_row, plan->member_group, plan->coef, plan->res_ptr, plan->res_col, plan->res_val, nch8, bc_shift, bs_x, bs_y, contig, plan->csr_ptr, plan->csr_col, plan->csr_val)
-        switch (plan->n_groups) {
-        case 1: NIIDMIX_BIGV4(1, 8); break; case 2: NIIDMIX_BIGV4(2, 4); break;
-        case 3: NIIDMIX_BIGV4(3, 4); break; case 4: NIIDMIX_BIGV4(4, 4); break;
-        default: return set_error(NIIDMIX_EUNSUPPORTED, "n_groups %d not in 1..4", plan->n_groups);
-        }
-#undef NIIDMIX_BIGV4
-        return check_launch("k_mix_bigclique_v4");
-    }
-#define NIIDMIX_BIGREG(G, R, OCC) hipLaunchKernelGGL((k_mix_bigclique_reg<G, R, OCC>), grid, block, 0, s, x, ld_x, y, ld_y, p, plan->n_cliques, plan->clique_ptr, plan->member_row, plan->member_group, plan->coef, plan->res_ptr, plan->res_col, plan->res_val, nch8, bc_shift, bs_x, bs_y, contig, plan->csr_ptr, plan->csr_col, plan->csr_val)
-    if (r16) {
-        switch (plan->n_groups) {
-        case 1: NIIDMIX_BIGREG(1, 16, 8); break; case 2: NIIDMIX_BIGREG(2, 16, 8); break;
-        case 3: NIIDMIX_BIGREG(3, 16, 8); break; case 4: NIIDMIX_BIGREG(4, 16, 8); break;
-        default: return set_error(NIIDMIX_EUNSUPPORTED, "n_groups %d not in 1..4", plan->n_groups);
-        }
-    } else {
-        switch (plan->n_groups) {
-        case 1: NIIDMIX_BIGREG(1, 32, 8); break; case 2: NIIDMIX_BIGREG(2, 32, 4); break;
-        case 3: NIIDMIX_BIGREG(3, 32, 4); break; case 4: NIIDMIX_BIGREG(4, 32, 4); break;
-        default: return set_error(NIIDMIX_EUNSUPPORTED, "n_groups %d not in 1..4", plan->n_groups);
-        }
-    }
-#undef NIIDMIX_BIGREG
-    return check_launch("k_mix_bigclique_reg");
+    const bool v4 = env_int("NIIDMIX_BIGREG_V4", plan->n_groups == 1) == 1 &&
+                    vec_width({p, ld_x, ld_y, bs_x, bs_y}, {x, y}) == 4 && bc_shift < 62 &&
+                    bs_x * 4 <= (int64_t)0xffffffffLL && bs_y * 4 <= (int64_t)0xffffffffLL;
+    // <G, OCC> of the float4 kernel: 8 waves per SIMD for one group, else 4; <G, R, OCC> of the
+    // other: 8 unless R = 32 meets groups
+    auto kfn = v4 ? pick<1, 2, 3, 4>(plan->n_groups, [](auto G) { return k_mix_bigclique_v4<G(), G() == 1 ? 8 : 4>; })
+                  : pick<true, false>(r16, [&](auto R16) { return pick<1, 2, 3, 4>(plan->n_groups, [&](auto G) {
+                        return k_mix_bigclique_reg<G(), R16() ? 16 : 32, (R16() || G() == 1) ? 8 : 4>; }); });
+    hipLaunchKernelGGL(kfn, dim3((unsigned)gsz), dim3(kBigRegWaves * 64), 0, s, x, ld_x, y, ld_y, p,
+                       plan->n_cliques, plan->clique_ptr, plan->member_row, plan->member_group, plan->coef,
+                       plan->res_ptr, plan->res_col, plan->res_val, nch8, bc_shift, bs_x, bs_y, contig,
+                       plan->csr_ptr, plan->csr_col, plan->csr_val);
+    return check_launch(v4 ? "k_mix_bigclique_v4" : "k_mix_bigclique_reg");
 }
 
 int niidmix_mix_clique_blocked_f32(const float *x, float *y, int64_t p, int64_t ld,
                                    int64_t block_cols, int64_t block_stride_x,
                                    int64_t block_stride_y, const niidmix_clique_plan *plan,
                                    void *stream) {
-    if (!plan) return set_error(NIIDMIX_EINVAL, "null plan");
-    if (p < 0 || plan->n_cliques < 0 || plan->n_members < 0) return set_error(NIIDMIX_EINVAL, "negative size");
-    if (plan->n_cliques == 0 || p == 0) return NIIDMIX_OK;
-    if (!x || !y || !plan->clique_ptr || !plan->member_row || !plan->member_group || !plan->coef ||
-        !plan->res_ptr || (!plan->res_col && plan->n_members > 0) || (!plan->res_val && plan->n_members > 0) ||
-        (!plan->res_member && plan->n_members > 0) || !plan->csr_ptr || !plan->csr_col || !plan->csr_val)
-        return set_error(NIIDMIX_EINVAL, "null pointer");
+    if (int rc = check_clique_plan(x, y, p, plan)) return rc == kEmpty ? NIIDMIX_OK : rc;
     // the register tile's items are 256 columns wide, the big-clique kernel's 32: an item never
     // straddles a block
     // (64 for cliques of <= 112 members: the multi-clique tile's 64-column items)
     const int64_t min_bc = plan->max_clique > 256 ? kBigRegCols : plan->max_clique <= 112 ? 64 : 256;
-    if (block_cols < min_bc || (block_cols & (block_cols - 1)))
-        return set_error(NIIDMIX_EINVAL, "block_cols %lld: a power of two >= %lld", (long long)block_cols,
-                         (long long)min_bc);
-    if (ld < block_cols) return set_error(NIIDMIX_EINVAL, "row stride < block_cols");
-    if (block_stride_x < ld || block_stride_y < ld)
-        return set_error(NIIDMIX_EINVAL, "block stride < row stride");
-    {   // extents of the member rows in both slabs (x may hold more rows: halo rows of a shard)
-        const int64_t k_blocks = (p + block_cols - 1) / block_cols;
-        const int64_t rows = plan->n_members > 0 ? plan->n_members : 1;
-        if (overlaps(x, (k_blocks - 1) * block_stride_x + (rows - 1) * ld + block_cols,
-                     y, (k_blocks - 1) * block_stride_y + (rows - 1) * ld + block_cols))
-            return set_error(NIIDMIX_EALIAS, "x and y overlap (mixing is out-of-place / Jacobi)");
-    }
+    // extents of the member rows in both slabs (x may hold more rows: halo rows of a shard)
+    if (int rc = check_blocked_pair(x, y, plan->n_members > 0 ? plan->n_members : 1, p, ld, block_cols,
+                                    block_stride_x, block_stride_y, min_bc, "row stride < block_cols",
+                                    "block stride < row stride", kMixAlias))
+        return rc;
     if (plan->max_clique > 2 * kBigRegWaves * 32)
         return set_error(NIIDMIX_EUNSUPPORTED, "blocked slabs: cliques of <= 1024 members");
     if (plan->max_clique_res < 0) return set_error(NIIDMIX_EINVAL, "negative max_clique_res");
-    const bool vec4 = (ld % 4 == 0) && (block_stride_x % 4 == 0) && (block_stride_y % 4 == 0) &&
-                      aligned16(x) && aligned16(y);
+    const bool vec4 = vec_width({ld, block_stride_x, block_stride_y}, {x, y}) == 4;
     if (plan->max_clique > 256)                               // one pass, 32-column items
         return launch_bigclique_reg(x, ld, y, ld, p, plan, __builtin_ctzll((unsigned long long)block_cols),
                                     block_stride_x, block_stride_y, reinterpret_cast<hipStream_t>(stream));
@@ -4506,38 +4579,23 @@ int niidmix_mix_clique_blocked_f32(const float *x, float *y, int64_t p, int64_t 
     return launch_clique_tiled(x, ld, y, ld, p, plan, vec4, reinterpret_cast<hipStream_t>(stream), bg);
 }
 
-// One-pass big-clique launch (k_mix_bigclique_reg), row-major (bc_shift 62, block strides 0) or
-// column-blocked slabs.
+// Row-major slabs: the register tiles up to 256 members, the one-pass big-clique kernel up to
+// 1024, the two-pass one above (or when NIIDMIX_BIG asks for it).
 int niidmix_mix_clique_f32(const float *x, int64_t ld_x, float *y, int64_t ld_y, int64_t p,
                            const niidmix_clique_plan *plan, void *stream) {
-    if (!plan) return set_error(NIIDMIX_EINVAL, "null plan");
-    if (p < 0 || plan->n_cliques < 0 || plan->n_members < 0) return set_error(NIIDMIX_EINVAL, "negative size");
-    if (plan->n_cliques == 0 || p == 0) return NIIDMIX_OK;
-    if (!x || !y || !plan->clique_ptr || !plan->member_row || !plan->member_group || !plan->coef ||
-        !plan->res_ptr || (!plan->res_col && plan->n_members > 0) || (!plan->res_val && plan->n_members > 0) ||
-        (!plan->res_member && plan->n_members > 0) || !plan->csr_ptr || !plan->csr_col || !plan->csr_val)
-        return set_error(NIIDMIX_EINVAL, "null pointer");
-    if (ld_x < p || ld_y < p) return set_error(NIIDMIX_EINVAL, "leading dimension < p");
-    {   // extents of the member rows in both slabs (x may hold more rows: halo rows of a shard)
-        const int64_t rows = plan->n_members > 0 ? plan->n_members : 1;
-        if (overlaps(x, (rows - 1) * ld_x + p, y, (rows - 1) * ld_y + p))
-            return set_error(NIIDMIX_EALIAS, "x and y overlap (mixing is out-of-place / Jacobi)");
-    }
+    if (int rc = check_clique_plan(x, y, p, plan)) return rc == kEmpty ? NIIDMIX_OK : rc;
+    // extents of the member rows in both slabs (x may hold more rows: halo rows of a shard)
+    if (int rc = check_slab_pair(x, ld_x, y, ld_y, plan->n_members > 0 ? plan->n_members : 1, p)) return rc;
     if (plan->max_clique_res < 0) return set_error(NIIDMIX_EINVAL, "negative max_clique_res");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const bool vec4 = (p % 4 == 0) && (ld_x % 4 == 0) && (ld_y % 4 == 0) && aligned16(x) && aligned16(y);
+    const bool vec4 = vec_width({p, ld_x, ld_y}, {x, y}) == 4;
     if (plan->max_clique > 256) {
         // big cliques (e.g. fully-connected = one clique): two-pass, one lane per column, a grid of
         // bpc blocks per CU walking the items.  Measured on FC-1000, P = 2^20 (tools/ab_clique.py):
         // 8 waves x 16 blocks/CU 2.36 ms; capping residency (to keep the pass-2 re-read in the
         // Infinity Cache) was slower: 8x4 2.57, 16x1 2.95 ms.  NIIDMIX_BIG=<waves>x<blocks per CU>
         // overrides (tuning).
-        static int n_cu = 0;
-        if (!n_cu) {
-            int dev = 0;
-            (void)hipGetDevice(&dev);
-            if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu < 1) n_cu = 256;
-        }
+        const int n_cu = cu_count();
         const char *big_env = getenv("NIIDMIX_BIG");         // "WxB": the two-pass kernel (tuning)
         if (big_env && !strcmp(big_env, "reg")) big_env = nullptr;
         if (!big_env && plan->max_clique <= 2 * kBigRegWaves * 32)
@@ -4549,15 +4607,14 @@ int niidmix_mix_clique_f32(const float *x, int64_t ld_x, float *y, int64_t ld_y,
         const int64_t items = (int64_t)plan->n_cliques * ((n_ch + 7) / 8) * 8;
         int64_t gsz = ((int64_t)bpc * n_cu + 7) / 8 * 8;
         if (gsz > items) gsz = items;
-        const dim3 grid((unsigned)gsz), block(waves * 64);
-        const size_t lds = 0;
-#define NIIDMIX_BIG(G, W) hipLaunchKernelGGL((k_mix_bigclique<G, W>), grid, block, lds, s, x, ld_x, y, ld_y, p, plan->n_cliques, plan->clique_ptr, plan->member_row, plan->member_group, plan->coef, plan->res_ptr, plan->res_col, plan->res_val, items, plan->csr_ptr, plan->csr_col, plan->csr_val)
-#define NIIDMIX_BIGW(W) switch (plan->n_groups) { case 1: NIIDMIX_BIG(1, W); break; case 2: NIIDMIX_BIG(2, W); break; case 3: NIIDMIX_BIG(3, W); break; case 4: NIIDMIX_BIG(4, W); break; default: return set_error(NIIDMIX_EUNSUPPORTED, "n_groups %d not in 1..4", plan->n_groups); }
-        if (waves == 4) { NIIDMIX_BIGW(4); }
-        else if (waves == 8) { NIIDMIX_BIGW(8); }
-        else { NIIDMIX_BIGW(16); }
-#undef NIIDMIX_BIGW
-#undef NIIDMIX_BIG
+        if (int rc = check_groups(plan->n_groups)) return rc;
+        // the kernel is built for 4, 8 and 16 waves; any other count runs the 16-wave one
+        auto kfn = pick<4, 8, 16>(waves == 4 || waves == 8 ? waves : 16, [&](auto W) {
+            return pick<1, 2, 3, 4>(plan->n_groups, [&](auto G) { return k_mix_bigclique<G(), W()>; }); });
+        hipLaunchKernelGGL(kfn, dim3((unsigned)gsz), dim3(waves * 64), 0, s, x, ld_x, y, ld_y, p,
+                           plan->n_cliques, plan->clique_ptr, plan->member_row, plan->member_group,
+                           plan->coef, plan->res_ptr, plan->res_col, plan->res_val, items, plan->csr_ptr,
+                           plan->csr_col, plan->csr_val);
         return check_launch("k_mix_bigclique");
     }
     return launch_clique_tiled(x, ld_x, y, ld_y, p, plan, vec4, s);
@@ -4567,40 +4624,28 @@ int niidmix_mix_ell_f32(const float *x, int64_t ld_x, float *y, int64_t ld_y, in
                         int64_t p, int k, const int32_t *ell_col, const float *ell_val,
                         const int32_t *ell_len, int mode, void *stream) {
     if (n_rows < 0 || p < 0) return set_error(NIIDMIX_EINVAL, "negative size");
-    const int avg_only = (mode & NIIDMIX_FLAG_AVERAGE_ONLY) ? 1 : 0;
-    mode &= ~(NIIDMIX_FLAG_AVERAGE_ONLY | NIIDMIX_FLAG_LOW_DEGREE);
-    if (mode != NIIDMIX_MODE_EXACT && mode != NIIDMIX_MODE_FAST)
-        return set_error(NIIDMIX_EINVAL, "unknown mode %d", mode);
+    const int avg_only = (strip_flags(&mode, NIIDMIX_FLAG_AVERAGE_ONLY | NIIDMIX_FLAG_LOW_DEGREE) & NIIDMIX_FLAG_AVERAGE_ONLY) ? 1 : 0;
+    if (int rc = check_mode(mode)) return rc;
     if (k < 1 || k > 8) return set_error(NIIDMIX_EUNSUPPORTED, "ELL width %d (1..8 supported)", k);
     if (n_rows == 0 || p == 0) return NIIDMIX_OK;
     if (!x || !y || !ell_col || !ell_val || !ell_len) return set_error(NIIDMIX_EINVAL, "null pointer");
-    if (ld_x < p || ld_y < p) return set_error(NIIDMIX_EINVAL, "leading dimension < p");
-    if (overlaps(x, (n_rows - 1) * ld_x + p, y, (n_rows - 1) * ld_y + p))
-        return set_error(NIIDMIX_EALIAS, "x and y overlap (mixing is out-of-place / Jacobi)");
+    if (int rc = check_slab_pair(x, ld_x, y, ld_y, n_rows, p)) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const uintptr_t align = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y);
-    const int vw = (p % 4 == 0 && ld_x % 4 == 0 && ld_y % 4 == 0 && (align & 15) == 0) ? 4
-                 : (p % 2 == 0 && ld_x % 2 == 0 && ld_y % 2 == 0 && (align & 7) == 0) ? 2 : 1;
+    const int vw = vec_width({p, ld_x, ld_y}, {x, y});
     // ELL width rounded up to an instantiated one; chunks in flight per wave by width (48 / 40 / 32
     // gather VGPRs).  NIIDMIX_ELL_CH overrides the chunks (tuning).
     const int kk = k <= 3 ? 3 : k <= 5 ? 5 : 8;
-    int ch = kk == 3 ? 4 : kk == 5 ? 2 : 1;
-    if (const char *e = getenv("NIIDMIX_ELL_CH")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4) ch = v; }
+    const int ch = env_int("NIIDMIX_ELL_CH", kk == 3 ? 4 : kk == 5 ? 2 : 1, {1, 2, 4});
     if (kk != k) return set_error(NIIDMIX_EINVAL, "ELL width %d: pad the rows to %d entries (ell_len keeps the lengths)", k, kk);
     const int64_t n_slices = (p + 256 * ch - 1) / (256 * ch);
     const int64_t n_row_groups = (n_rows + 3) / 4;
     const int64_t n_items = n_row_groups * ((n_slices + 7) / 8) * 8;
     if (n_items > 0x7fffffffLL) return set_error(NIIDMIX_EUNSUPPORTED, "too many (rows, slice) items");
-    const dim3 grid((unsigned)n_items), block(256);
-#define NIIDMIX_ELL(E, V, KK, C) hipLaunchKernelGGL((k_mix_ell<E, V, KK, C>), grid, block, 0, s, x, ld_x, y, ld_y, n_rows, p, ell_col, ell_val, ell_len, n_row_groups, n_items, avg_only)
-#define NIIDMIX_ELL_C(E, V, KK) do { if (ch == 4) NIIDMIX_ELL(E, V, KK, 4); else if (ch == 2) NIIDMIX_ELL(E, V, KK, 2); else NIIDMIX_ELL(E, V, KK, 1); } while (0)
-#define NIIDMIX_ELL_K(E, V) do { if (kk == 3) NIIDMIX_ELL_C(E, V, 3); else if (kk == 5) NIIDMIX_ELL_C(E, V, 5); else NIIDMIX_ELL_C(E, V, 8); } while (0)
-#define NIIDMIX_ELL_V(E) do { if (vw == 4) NIIDMIX_ELL_K(E, 4); else if (vw == 2) NIIDMIX_ELL_K(E, 2); else NIIDMIX_ELL_K(E, 1); } while (0)
-    if (mode == NIIDMIX_MODE_EXACT) NIIDMIX_ELL_V(true); else NIIDMIX_ELL_V(false);
-#undef NIIDMIX_ELL_V
-#undef NIIDMIX_ELL_K
-#undef NIIDMIX_ELL_C
-#undef NIIDMIX_ELL
+    auto kfn = pick<true, false>(mode == NIIDMIX_MODE_EXACT, [&](auto E) { return pick<4, 2, 1>(vw, [&](auto V) {
+        return pick<3, 5, 8>(kk, [&](auto K) { return pick<4, 2, 1>(ch, [&](auto C) {
+            return k_mix_ell<E(), V(), K(), C()>; }); }); }); });
+    hipLaunchKernelGGL(kfn, dim3((unsigned)n_items), dim3(256), 0, s, x, ld_x, y, ld_y, n_rows, p, ell_col,
+                       ell_val, ell_len, n_row_groups, n_items, avg_only);
     return check_launch("k_mix_ell");
 }
 
@@ -4608,51 +4653,34 @@ int niidmix_mix_band_f32(const float *x, int64_t ld_x, float *y, int64_t ld_y, i
                          int64_t p, int k, int band, const int32_t *ell_col, const float *ell_val,
                          const int32_t *ell_len, int mode, void *stream) {
     if (n_rows < 0 || p < 0) return set_error(NIIDMIX_EINVAL, "negative size");
-    const int avg_only = (mode & NIIDMIX_FLAG_AVERAGE_ONLY) ? 1 : 0;
-    mode &= ~(NIIDMIX_FLAG_AVERAGE_ONLY | NIIDMIX_FLAG_LOW_DEGREE);
-    if (mode != NIIDMIX_MODE_EXACT && mode != NIIDMIX_MODE_FAST)
-        return set_error(NIIDMIX_EINVAL, "unknown mode %d", mode);
+    const int avg_only = (strip_flags(&mode, NIIDMIX_FLAG_AVERAGE_ONLY | NIIDMIX_FLAG_LOW_DEGREE) & NIIDMIX_FLAG_AVERAGE_ONLY) ? 1 : 0;
+    if (int rc = check_mode(mode)) return rc;
     if (!((k == 3 && band == 1) || (k == 5 && band == 2)))
         return set_error(NIIDMIX_EUNSUPPORTED, "band kernel: (k, band) = (%d, %d), (3, 1) or (5, 2) supported", k, band);
     if (n_rows == 0 || p == 0) return NIIDMIX_OK;
     if (n_rows < 2 * band + 1) return set_error(NIIDMIX_EUNSUPPORTED, "band %d needs >= %d rows", band, 2 * band + 1);
     if (!x || !y || !ell_col || !ell_val || !ell_len) return set_error(NIIDMIX_EINVAL, "null pointer");
-    if (ld_x < p || ld_y < p) return set_error(NIIDMIX_EINVAL, "leading dimension < p");
-    if (overlaps(x, (n_rows - 1) * ld_x + p, y, (n_rows - 1) * ld_y + p))
-        return set_error(NIIDMIX_EALIAS, "x and y overlap (mixing is out-of-place / Jacobi)");
+    if (int rc = check_slab_pair(x, ld_x, y, ld_y, n_rows, p)) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const uintptr_t align = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y);
-    const int vw = (p % 4 == 0 && ld_x % 4 == 0 && ld_y % 4 == 0 && (align & 15) == 0) ? 4
-                 : (p % 2 == 0 && ld_x % 2 == 0 && ld_y % 2 == 0 && (align & 7) == 0) ? 2 : 1;
+    const int vw = vec_width({p, ld_x, ld_y}, {x, y});
     if (vw == 1) return set_error(NIIDMIX_EUNSUPPORTED, "band kernel needs even p and ld, 8-B aligned slabs");
     // rows per wave x column chunks per wave (R x CH): NIIDMIX_BAND_RC = "R,CH" among the built
     // shapes (tuning); default 4 x 1 (ring 100, P = 62 006 in a hipGraph: 15.6 us per round; 4 x 4
     // 18.3, 2 x 2 15.8, 1 x 4 16.5, 8 x 2 17.3; tools/band_probe.py, profiles/r04/band_probe.txt)
-    int rr = 4, ch = 1;
-    if (const char *e = getenv("NIIDMIX_BAND_RC")) {
-        int a = 0, b = 0;
-        if (sscanf(e, "%d,%d", &a, &b) == 2 &&
-            ((a == 1 && (b == 1 || b == 2 || b == 4)) || (a == 2 && (b == 1 || b == 2)) ||
-             (a == 4 && (b == 1 || b == 4)) || (a == 8 && b == 2))) { rr = a; ch = b; }
-    }
+    int rr = 4, ch = 1, a = 0, b = 0;
+    if (env_scan("NIIDMIX_BAND_RC", "%d,%d", &a, &b) == 2 &&
+        ((a == 1 && (b == 1 || b == 2 || b == 4)) || (a == 2 && (b == 1 || b == 2)) ||
+         (a == 4 && (b == 1 || b == 4)) || (a == 8 && b == 2))) { rr = a; ch = b; }
     const int64_t n_slices = (p + 64 * vw * ch - 1) / (64 * vw * ch);
     const int64_t n_row_groups = (n_rows + 4 * rr - 1) / (4 * rr);
     const int64_t n_items = n_row_groups * ((n_slices + 7) / 8) * 8;
     if (n_items > 0x7fffffffLL) return set_error(NIIDMIX_EUNSUPPORTED, "too many (rows, slice) items");
-    const dim3 grid((unsigned)n_items), block(256);
-#define NIIDMIX_BAND(E, V, KK, BB, RR, C) hipLaunchKernelGGL((k_mix_band<E, V, KK, BB, RR, C>), grid, block, 0, s, x, ld_x, y, ld_y, n_rows, p, ell_col, ell_val, ell_len, n_row_groups, n_items, avg_only)
-#define NIIDMIX_BAND_R(E, V, KK, BB) do { \
-        if (rr == 1) { if (ch == 1) NIIDMIX_BAND(E, V, KK, BB, 1, 1); else if (ch == 2) NIIDMIX_BAND(E, V, KK, BB, 1, 2); else NIIDMIX_BAND(E, V, KK, BB, 1, 4); } \
-        else if (rr == 2) { if (ch == 1) NIIDMIX_BAND(E, V, KK, BB, 2, 1); else NIIDMIX_BAND(E, V, KK, BB, 2, 2); } \
-        else if (rr == 4) { if (ch == 1) NIIDMIX_BAND(E, V, KK, BB, 4, 1); else NIIDMIX_BAND(E, V, KK, BB, 4, 4); } \
-        else NIIDMIX_BAND(E, V, KK, BB, 8, 2); } while (0)
-#define NIIDMIX_BAND_K(E, V) do { if (k == 3) NIIDMIX_BAND_R(E, V, 3, 1); else NIIDMIX_BAND_R(E, V, 5, 2); } while (0)
-#define NIIDMIX_BAND_V(E) do { if (vw == 4) NIIDMIX_BAND_K(E, 4); else NIIDMIX_BAND_K(E, 2); } while (0)
-    if (mode == NIIDMIX_MODE_EXACT) NIIDMIX_BAND_V(true); else NIIDMIX_BAND_V(false);
-#undef NIIDMIX_BAND_V
-#undef NIIDMIX_BAND_K
-#undef NIIDMIX_BAND_R
-#undef NIIDMIX_BAND
+    // the built (R, CH) shapes as 10 R + CH; (K, B) is (3, 1) or (5, 2)
+    auto kfn = pick<true, false>(mode == NIIDMIX_MODE_EXACT, [&](auto E) { return pick<4, 2>(vw, [&](auto V) {
+        return pick<3, 5>(k, [&](auto K) { return pick<11, 12, 14, 21, 22, 41, 44, 82>(10 * rr + ch, [&](auto RC) {
+            return k_mix_band<E(), V(), K(), K() == 3 ? 1 : 2, RC() / 10, RC() % 10>; }); }); }); });
+    hipLaunchKernelGGL(kfn, dim3((unsigned)n_items), dim3(256), 0, s, x, ld_x, y, ld_y, n_rows, p, ell_col,
+                       ell_val, ell_len, n_row_groups, n_items, avg_only);
     return check_launch("k_mix_band");
 }
 
@@ -4660,17 +4688,13 @@ int niidmix_mix_strip_f32(const float *x, int64_t ld_x, float *y, int64_t ld_y, 
                           int64_t p, int k, const int32_t *ell_col, const float *ell_val,
                           const int32_t *ell_len, int mode, void *stream) {
     if (n_rows < 0 || p < 0) return set_error(NIIDMIX_EINVAL, "negative size");
-    const int avg_only = (mode & NIIDMIX_FLAG_AVERAGE_ONLY) ? 1 : 0;
-    mode &= ~(NIIDMIX_FLAG_AVERAGE_ONLY | NIIDMIX_FLAG_LOW_DEGREE);
-    if (mode != NIIDMIX_MODE_EXACT && mode != NIIDMIX_MODE_FAST)
-        return set_error(NIIDMIX_EINVAL, "unknown mode %d", mode);
+    const int avg_only = (strip_flags(&mode, NIIDMIX_FLAG_AVERAGE_ONLY | NIIDMIX_FLAG_LOW_DEGREE) & NIIDMIX_FLAG_AVERAGE_ONLY) ? 1 : 0;
+    if (int rc = check_mode(mode)) return rc;
     if (k != 3 && k != 5 && k != 8) return set_error(NIIDMIX_EUNSUPPORTED, "ELL width %d (3, 5 or 8)", k);
     if (n_rows == 0 || p == 0) return NIIDMIX_OK;
     if (n_rows > 256) return set_error(NIIDMIX_EUNSUPPORTED, "strip kernel: %lld rows (<= 256)", (long long)n_rows);
     if (!x || !y || !ell_col || !ell_val || !ell_len) return set_error(NIIDMIX_EINVAL, "null pointer");
-    if (ld_x < p || ld_y < p) return set_error(NIIDMIX_EINVAL, "leading dimension < p");
-    if (overlaps(x, (n_rows - 1) * ld_x + p, y, (n_rows - 1) * ld_y + p))
-        return set_error(NIIDMIX_EALIAS, "x and y overlap (mixing is out-of-place / Jacobi)");
+    if (int rc = check_slab_pair(x, ld_x, y, ld_y, n_rows, p)) return rc;
     if (reinterpret_cast<uintptr_t>(x) & 3) return set_error(NIIDMIX_EUNSUPPORTED, "x not 4-B aligned");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     // float4 lanes (256-column strips, 1 KiB per staged row) when every lane's float4 stays inside
@@ -4682,10 +4706,9 @@ int niidmix_mix_strip_f32(const float *x, int64_t ld_x, float *y, int64_t ld_y, 
     if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeSharedMemPerBlockOptin, dev) != hipSuccess || lds_max <= 0)
         if (hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || lds_max <= 0)
             lds_max = 65536;
-    const uintptr_t al = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y);
-    int sv = (ld_x % 4 == 0 && ld_y % 4 == 0 && (al & 15) == 0 && ld_x >= (p + 3) / 4 * 4 &&
+    int sv = (vec_width({ld_x, ld_y}, {x, y}) == 4 && ld_x >= (p + 3) / 4 * 4 &&
               n_rows * kWave * 4 * (int64_t)sizeof(float) <= (int64_t)lds_max - 4096) ? 4 : 1;
-    if (const char *e = getenv("NIIDMIX_STRIP_SV")) if (atoi(e) == 1) sv = 1;
+    if (env_int("NIIDMIX_STRIP_SV", 0) == 1) sv = 1;
     if (n_rows * kWave * sv * (int64_t)sizeof(float) > (int64_t)lds_max)
         return set_error(NIIDMIX_EUNSUPPORTED, "strip kernel: %lld rows do not fit %d B of LDS",
                          (long long)n_rows, lds_max);
@@ -4693,33 +4716,21 @@ int niidmix_mix_strip_f32(const float *x, int64_t ld_x, float *y, int64_t ld_y, 
     if (n_strips > 0x7fffffffLL) return set_error(NIIDMIX_EUNSUPPORTED, "too many strips");
     const size_t lds = (size_t)n_rows * kWave * sv * sizeof(float);   // <= lds_max
     // waves per strip: 8 (NIIDMIX_STRIP_SW = 4 / 8 / 16 overrides, tuning)
-    int sw = 8;
-    if (const char *e = getenv("NIIDMIX_STRIP_SW")) { const int v = atoi(e); if (v == 4 || v == 8 || v == 16) sw = v; }
-    const dim3 grid((unsigned)n_strips), block(sw * kWave);
-#define NIIDMIX_STRIP_W(E, KK, V, W) do { \
-        auto kfn = k_mix_strip<E, KK, W, V>; \
-        if (lds > 65536 && hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) \
-            return set_error(NIIDMIX_EHIP, "k_mix_strip: %zu B of LDS refused", lds); \
-        hipLaunchKernelGGL(kfn, grid, block, lds, s, x, ld_x, y, ld_y, (int)n_rows, p, ell_col, ell_val, ell_len, avg_only); \
-    } while (0)
-#define NIIDMIX_STRIP(E, KK, V) do { if (sw == 4) NIIDMIX_STRIP_W(E, KK, V, 4); else if (sw == 8) NIIDMIX_STRIP_W(E, KK, V, 8); else NIIDMIX_STRIP_W(E, KK, V, 16); } while (0)
-#define NIIDMIX_STRIP_V(E, KK) do { if (sv == 4) NIIDMIX_STRIP(E, KK, 4); else NIIDMIX_STRIP(E, KK, 1); } while (0)
-#define NIIDMIX_STRIP_K(E) do { if (k == 3) NIIDMIX_STRIP_V(E, 3); else if (k == 5) NIIDMIX_STRIP_V(E, 5); else NIIDMIX_STRIP_V(E, 8); } while (0)
-    if (mode == NIIDMIX_MODE_EXACT) NIIDMIX_STRIP_K(true); else NIIDMIX_STRIP_K(false);
-#undef NIIDMIX_STRIP_K
-#undef NIIDMIX_STRIP_V
-#undef NIIDMIX_STRIP
-#undef NIIDMIX_STRIP_W
+    const int sw = env_int("NIIDMIX_STRIP_SW", 8, {4, 8, 16});
+    auto kfn = pick<true, false>(mode == NIIDMIX_MODE_EXACT, [&](auto E) { return pick<3, 5, 8>(k, [&](auto K) {
+        return pick<4, 1>(sv, [&](auto V) { return pick<4, 8, 16>(sw, [&](auto W) {
+            return k_mix_strip<E(), K(), W(), V()>; }); }); }); });
+    if (lds > 65536) if (int rc = lds_opt_in(kfn, lds, "k_mix_strip")) return rc;
+    hipLaunchKernelGGL(kfn, dim3((unsigned)n_strips), dim3(sw * kWave), lds, s, x, ld_x, y, ld_y, (int)n_rows,
+                       p, ell_col, ell_val, ell_len, avg_only);
     return check_launch("k_mix_strip");
 }
 
 int niidmix_mix_tile_f32(const float *x, int64_t ld_x, float *y, int64_t ld_y, int64_t n_rows,
                          int64_t p, const niidmix_tile_plan *plan, int mode, void *stream) {
     if (!plan) return set_error(NIIDMIX_EINVAL, "null plan");
-    const int avg_only = (mode & NIIDMIX_FLAG_AVERAGE_ONLY) ? 1 : 0;
-    mode &= ~NIIDMIX_FLAG_AVERAGE_ONLY;
-    if (mode != NIIDMIX_MODE_EXACT && mode != NIIDMIX_MODE_FAST)
-        return set_error(NIIDMIX_EINVAL, "unknown mode %d", mode);
+    const int avg_only = strip_flags(&mode, NIIDMIX_FLAG_AVERAGE_ONLY) ? 1 : 0;
+    if (int rc = check_mode(mode)) return rc;
     if (p < 0 || plan->n_sub < 0) return set_error(NIIDMIX_EINVAL, "negative size");
     if (plan->rt != 8 && plan->rt != 16 && plan->rt != 32)
         return set_error(NIIDMIX_EUNSUPPORTED, "tile of %d rows (8, 16 or 32 supported)", plan->rt);
@@ -4727,44 +4738,34 @@ int niidmix_mix_tile_f32(const float *x, int64_t ld_x, float *y, int64_t ld_y, i
     if (!x || !y || !plan->sub_ptr || !plan->sub_rows || !plan->sub_wself || !plan->pos_src ||
         !plan->pos_mask || !plan->pos_w)
         return set_error(NIIDMIX_EINVAL, "null pointer");
-    if (ld_x < p || ld_y < p) return set_error(NIIDMIX_EINVAL, "leading dimension < p");
+    if (int rc = check_ld(ld_x, ld_y, p)) return rc;
     if (n_rows < 1) return set_error(NIIDMIX_EINVAL, "n_rows < 1");
-    if (overlaps(x, (n_rows - 1) * ld_x + p, y, (n_rows - 1) * ld_y + p))
-        return set_error(NIIDMIX_EALIAS, "x and y overlap (mixing is out-of-place / Jacobi)");
+    if (int rc = check_overlap(x, ld_x, y, ld_y, n_rows, p)) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const uintptr_t align = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y);
     // columns per lane: 4 for 8- and 16-row tiles, 2 for 32-row tiles (register budget);
     // NIIDMIX_TILE_NE=2|4 overrides (tuning)
-    int ne = plan->rt == 32 ? 2 : 4;
-    if (const char *e = getenv("NIIDMIX_TILE_NE")) { const int v = atoi(e); if (v == 2 || v == 4) ne = v; }
-    int vw = (p % 2 == 0 && ld_x % 2 == 0 && ld_y % 2 == 0 && (align & 7) == 0) ? 2 : 1;
-    if (ne == 4 && vw == 2 && p % 4 == 0 && ld_x % 4 == 0 && ld_y % 4 == 0 && (align & 15) == 0) vw = 4;
+    const int ne = env_int("NIIDMIX_TILE_NE", plan->rt == 32 ? 2 : 4, {2, 4});
+    int vw = vec_width({p, ld_x, ld_y}, {x, y});
+    if (vw > ne) vw = 2;                        // float4 lanes only with 4 columns per lane
     const int64_t cw = 64 * ne;
     const int64_t n_chunks = (p + cw - 1) / cw;
     const int64_t n_sub_groups = (plan->n_sub + 3) / 4;
     const int64_t n_items = n_sub_groups * ((n_chunks + 7) / 8) * 8;
-    const dim3 grid((unsigned)grid_for(n_items)), block(256);
-#define NIIDMIX_TILEK(E, V, N, R) hipLaunchKernelGGL((k_mix_tile<E, V, N, R>), grid, block, 0, s, x, ld_x, y, ld_y, p, plan->n_sub, plan->sub_ptr, plan->sub_rows, plan->sub_wself, plan->pos_src, plan->pos_mask, plan->pos_w, n_sub_groups, n_items, avg_only)
-#define NIIDMIX_TILE_V(E, N, R) do { if (vw == 4) NIIDMIX_TILEK(E, 4, 4, R); else if (vw == 2) NIIDMIX_TILEK(E, 2, N, R); else NIIDMIX_TILEK(E, 1, N, R); } while (0)
-#define NIIDMIX_TILE_N(E, R) do { if (ne == 4) NIIDMIX_TILE_V(E, 4, R); else NIIDMIX_TILE_V(E, 2, R); } while (0)
-#define NIIDMIX_TILE_R(E) do { if (plan->rt == 8) NIIDMIX_TILE_N(E, 8); else if (plan->rt == 16) NIIDMIX_TILE_N(E, 16); else NIIDMIX_TILE_N(E, 32); } while (0)
-    if (mode == NIIDMIX_MODE_EXACT) NIIDMIX_TILE_R(true); else NIIDMIX_TILE_R(false);
-#undef NIIDMIX_TILE_R
-#undef NIIDMIX_TILE_N
-#undef NIIDMIX_TILE_V
-#undef NIIDMIX_TILEK
+    auto kfn = pick<true, false>(mode == NIIDMIX_MODE_EXACT, [&](auto E) { return pick<8, 16, 32>(plan->rt, [&](auto R) {
+        return pick<4, 2>(ne, [&](auto N) { return pick<4, 2, 1>(vw, [&](auto V) {
+            return k_mix_tile<E(), V(), V() == 4 ? 4 : N(), R()>; }); }); }); });
+    hipLaunchKernelGGL(kfn, dim3((unsigned)grid_for(n_items)), dim3(256), 0, s, x, ld_x, y, ld_y, p,
+                       plan->n_sub, plan->sub_ptr, plan->sub_rows, plan->sub_wself, plan->pos_src,
+                       plan->pos_mask, plan->pos_w, n_sub_groups, n_items, avg_only);
     return check_launch("k_mix_tile");
 }
 
 int niidmix_mix_tile_lds_f32(const float *x, int64_t ld_x, float *y, int64_t ld_y, int64_t n_rows,
                              int64_t p, const niidmix_tile_lds_plan *plan, int mode, void *stream) {
     if (!plan) return set_error(NIIDMIX_EINVAL, "null plan");
-    int avg_only = (mode & NIIDMIX_FLAG_AVERAGE_ONLY) ? 1 : 0;
-    mode &= ~NIIDMIX_FLAG_AVERAGE_ONLY;
-    if (mode != NIIDMIX_MODE_EXACT && mode != NIIDMIX_MODE_FAST)
-        return set_error(NIIDMIX_EINVAL, "unknown mode %d", mode);
-    if (const char *e = getenv("NIIDMIX_TLDS_SMALL"))           // tuning: 0 = 16-row loop only
-        if (atoi(e) == 0) avg_only |= 2;
+    int avg_only = strip_flags(&mode, NIIDMIX_FLAG_AVERAGE_ONLY) ? 1 : 0;
+    if (int rc = check_mode(mode)) return rc;
+    if (env_int("NIIDMIX_TLDS_SMALL", 1) == 0) avg_only |= 2;   // tuning: 0 = 16-row loop only
     if (p < 0 || plan->n_grp < 0) return set_error(NIIDMIX_EINVAL, "negative size");
     if (plan->rt != 8 && plan->rt != 16 && plan->rt != 32)
         return set_error(NIIDMIX_EUNSUPPORTED, "tile of %d rows (8, 16 or 32 supported)", plan->rt);
@@ -4773,21 +4774,19 @@ int niidmix_mix_tile_lds_f32(const float *x, int64_t ld_x, float *y, int64_t ld_
         !plan->sub_ptr || !plan->sub_rows || !plan->sub_slot || !plan->sub_wself ||
         !plan->pos_slot || !plan->pos_mask || !plan->pos_w)
         return set_error(NIIDMIX_EINVAL, "null pointer");
-    if (ld_x < p || ld_y < p) return set_error(NIIDMIX_EINVAL, "leading dimension < p");
+    if (int rc = check_ld(ld_x, ld_y, p)) return rc;
     if (ld_x >= (1LL << 30)) return set_error(NIIDMIX_EUNSUPPORTED, "ld_x >= 2^30");
     if (n_rows < 1) return set_error(NIIDMIX_EINVAL, "n_rows < 1");
-    if (overlaps(x, (n_rows - 1) * ld_x + p, y, (n_rows - 1) * ld_y + p))
-        return set_error(NIIDMIX_EALIAS, "x and y overlap (mixing is out-of-place / Jacobi)");
+    if (int rc = check_overlap(x, ld_x, y, ld_y, n_rows, p)) return rc;
     if (plan->max_src < 1 || plan->max_src > 256)
         return set_error(NIIDMIX_EUNSUPPORTED, "group with %d source rows (1..256 supported)", plan->max_src);
     const int max_waves = tile_lds_max_waves(plan->rt);
     if (plan->max_tiles < 1 || plan->max_tiles > max_waves)
         return set_error(NIIDMIX_EUNSUPPORTED, "group with %d tiles of %d rows (1..%d supported)",
                          plan->max_tiles, plan->rt, max_waves);
-    const uintptr_t align = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y);
-    if (p % 2 || ld_x % 2 || ld_y % 2 || (align & 7))
+    if (vec_width({p, ld_x, ld_y}, {x, y}) == 1)
         return set_error(NIIDMIX_EUNSUPPORTED, "LDS tile kernel needs even p, ld and 8-B aligned slabs");
-    const int sv = (p % 4 == 0 && ld_x % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0) ? 4 : 2;
+    const int sv = vec_width({p, ld_x}, {x}) == 4 ? 4 : 2;      // staging loads read x only
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     // Item width (rt 16): the widest of 128, 120 and 96 columns that fits the most blocks per CU in
     // its 160 KB of LDS, up to three (three 7-wave blocks fill the 6 waves per SIMD the kernel's 80
@@ -4808,15 +4807,16 @@ int niidmix_mix_tile_lds_f32(const float *x, int64_t ld_x, float *y, int64_t ld_
         return set_error(NIIDMIX_EINVAL, "rem_rows needs the segment walker (seg_ptr set, mf_ptr NULL)");
     if (rem && plan->rem_regs != 0 && plan->rem_regs != 8 && plan->rem_regs != 16 && plan->rem_regs != -16)
         return set_error(NIIDMIX_EINVAL, "rem_regs %d (0, 8, 16 or -16)", plan->rem_regs);
-    const bool rem8 = rem && plan->rem_regs == 8;
-    // -16: up to 16 register rows walked in two phases of 8 (80 VGPRs instead of 96); the host
-    // sets it only for plans whose tiles read rows 0..7 before any of 8..15 (tile.rem_two_phase)
-    const bool rem2 = rem && plan->rem_regs == -16;
     if (mf && !plan->mf) return set_error(NIIDMIX_EINVAL, "null MFMA position list");
+    // Kernel variant (RT 16; the other heights have the plain position loop only): 0 plain loop,
+    // 1 segment walker, 2 walker with the matrix-core path, 3 / 4 walker with 16 / 8 register rows,
+    // 5 with up to 16 register rows walked in two phases of 8 (rem_regs -16: 80 VGPRs instead of
+    // 96; the host sets it only for plans whose tiles read rows 0..7 before any of 8..15,
+    // tile.rem_two_phase)
+    const int variant = !seg ? 0 : !rem ? (mf ? 2 : 1) : plan->rem_regs == 8 ? 4 : plan->rem_regs == -16 ? 5 : 3;
     // waves of a block on the matrix cores (the rest walk segments on the VALU side by side);
     // NIIDMIX_TLDS_MF_WAVES overrides (tuning), default every wave
-    int mf_waves = plan->max_tiles;
-    if (const char *e = getenv("NIIDMIX_TLDS_MF_WAVES")) mf_waves = atoi(e);
+    const int mf_waves = env_int("NIIDMIX_TLDS_MF_WAVES", plan->max_tiles);
     const int stage_rows = plan->max_src + (seg ? 2 : 0);
     if (plan->rt == 16) {
         auto blocks = [&](int c) {
@@ -4828,36 +4828,24 @@ int niidmix_mix_tile_lds_f32(const float *x, int64_t ld_x, float *y, int64_t ld_
         for (int c : {128, 120, 96})
             if (blocks(c) >= target) { cw = c; break; }
     }
-    if (const char *e = getenv("NIIDMIX_TLDS_COLS")) {          // tuning override: 128, 120 or 96
-        const int v = atoi(e);
-        if (v == 128 || v == 120 || v == 96) cw = v;
-    }
+    cw = env_int("NIIDMIX_TLDS_COLS", cw, {128, 120, 96});      // tuning override
     const int64_t n_chunks = (p + cw - 1) / cw;
     const int64_t n_items = (int64_t)plan->n_grp * ((n_chunks + 7) / 8) * 8;
     if (n_items > 0x7fffffffLL) return set_error(NIIDMIX_EUNSUPPORTED, "too many (group, chunk) items");
     const size_t lds = (size_t)stage_rows * cw * sizeof(float) + tlds_slack(seg, cw);
-    const dim3 grid((unsigned)n_items), block((unsigned)(64 * plan->max_tiles));
-#define NIIDMIX_TLDS_CW2(E, R, V, SG, RM, M, R2) (cw == 120 ? k_mix_tile_lds<E, R, V, 60, SG, RM, M, R2> : cw == 96 ? k_mix_tile_lds<E, R, V, 48, SG, RM, M, R2> : k_mix_tile_lds<E, R, V, 64, SG, RM, M, R2>)
-#define NIIDMIX_TLDS_CW(E, R, V, SG, RM, M) NIIDMIX_TLDS_CW2(E, R, V, SG, RM, M, false)
-#define NIIDMIX_TLDS(E, R, V) do { \
-        auto kfn = seg ? (rem ? (rem8 ? NIIDMIX_TLDS_CW(E, R, V, (R == 16), (R == 16 ? 8 : 0), false) \
-                                : rem2 ? NIIDMIX_TLDS_CW2(E, R, V, (R == 16), (R == 16 ? 8 : 0), false, (R == 16)) \
-                                     : NIIDMIX_TLDS_CW(E, R, V, (R == 16), (R == 16 ? 16 : 0), false)) \
-                              : mf ? NIIDMIX_TLDS_CW(E, R, V, (R == 16), 0, (E && R == 16)) \
-                                   : NIIDMIX_TLDS_CW(E, R, V, (R == 16), 0, false)) \
-                       : NIIDMIX_TLDS_CW(E, R, V, false, 0, false); \
-        if (lds > 65536 && hipFuncSetAttribute(reinterpret_cast<const void *>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) \
-            return set_error(NIIDMIX_EHIP, "k_mix_tile_lds: %zu B of LDS refused", lds); \
-        hipLaunchKernelGGL(kfn, grid, block, lds, s, x, ld_x, y, ld_y, p, (int64_t)plan->n_grp, plan->grp_tile_ptr, plan->grp_src_ptr, plan->grp_src_rows, plan->sub_ptr, plan->sub_rows, plan->sub_slot, plan->sub_wself, plan->pos_slot, plan->pos_mask, plan->pos_w, avg_only, seg ? plan->seg_ptr : nullptr, plan->seg, plan->seg_w, mf ? plan->mf_ptr : nullptr, plan->mf, mf_waves, plan->rem_rows); \
-    } while (0)
-#define NIIDMIX_TLDS_V(E, R) do { if (sv == 4) NIIDMIX_TLDS(E, R, 4); else NIIDMIX_TLDS(E, R, 2); } while (0)
-#define NIIDMIX_TLDS_R(E) do { if (plan->rt == 8) NIIDMIX_TLDS_V(E, 8); else if (plan->rt == 16) NIIDMIX_TLDS_V(E, 16); else NIIDMIX_TLDS_V(E, 32); } while (0)
-    if (mode == NIIDMIX_MODE_EXACT) NIIDMIX_TLDS_R(true); else NIIDMIX_TLDS_R(false);
-#undef NIIDMIX_TLDS_R
-#undef NIIDMIX_TLDS_V
-#undef NIIDMIX_TLDS
-#undef NIIDMIX_TLDS_CW
-#undef NIIDMIX_TLDS_CW2
+    auto kfn = pick<true, false>(mode == NIIDMIX_MODE_EXACT, [&](auto E) { return pick<8, 16, 32>(plan->rt, [&](auto R) {
+        return pick<4, 2>(sv, [&](auto V) { return pick<64, 60, 48>(cw / 2, [&](auto RS) {
+            return pick<0, 1, 2, 3, 4, 5>(variant, [&](auto T) {
+                constexpr int t = R() == 16 ? T() : 0;
+                return k_mix_tile_lds<E(), R(), V(), RS(), (t > 0), (t == 3 ? 16 : t >= 4 ? 8 : 0), (E() && t == 2), (t == 5)>;
+            }); }); }); }); });
+    if (lds > 65536) if (int rc = lds_opt_in(kfn, lds, "k_mix_tile_lds")) return rc;
+    hipLaunchKernelGGL(kfn, dim3((unsigned)n_items), dim3((unsigned)(64 * plan->max_tiles)), lds, s, x, ld_x,
+                       y, ld_y, p, (int64_t)plan->n_grp, plan->grp_tile_ptr, plan->grp_src_ptr,
+                       plan->grp_src_rows, plan->sub_ptr, plan->sub_rows, plan->sub_slot, plan->sub_wself,
+                       plan->pos_slot, plan->pos_mask, plan->pos_w, avg_only, seg ? plan->seg_ptr : nullptr,
+                       plan->seg, plan->seg_w, mf ? plan->mf_ptr : nullptr, plan->mf, mf_waves,
+                       plan->rem_rows);
     return check_launch("k_mix_tile_lds");
 }
 
@@ -4867,39 +4855,27 @@ int niidmix_mix_dense_f32(const float *x, int64_t ld_x, float *y, int64_t ld_y, 
     if (n < 0 || p < 0) return set_error(NIIDMIX_EINVAL, "negative size");
     if (n == 0 || p == 0) return NIIDMIX_OK;
     if (!x || !y || !w || !row_ptr || !col || !val) return set_error(NIIDMIX_EINVAL, "null pointer");
-    if (ld_x < p || ld_y < p) return set_error(NIIDMIX_EINVAL, "leading dimension < p");
-    if (overlaps(x, (n - 1) * ld_x + p, y, (n - 1) * ld_y + p))
-        return set_error(NIIDMIX_EALIAS, "x and y overlap (mixing is out-of-place / Jacobi)");
+    if (int rc = check_slab_pair(x, ld_x, y, ld_y, n, p)) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const bool vec = (p % 4 == 0) && (ld_x % 4 == 0) && aligned16(x);
+    const bool vec = vec_width({p, ld_x}, {x}) == 4;            // the tile loads read x only
     const int64_t n_it = (n + kDBM - 1) / kDBM;
     const int64_t n_jt = (p + kDBN - 1) / kDBN;
     const int64_t n_items = n_it * ((n_jt + 7) / 8) * 8;
-    const dim3 grid((unsigned)grid_for(n_items)), block(256);
     const bool avec = (n % 4 == 0) && aligned16(w);
-#define NIIDMIX_DENSE(V, A) hipLaunchKernelGGL((k_mix_dense<V, A>), grid, block, 0, s, x, ld_x, y, ld_y, n, p, w, n_it, n_items, row_ptr, col, val)
     // vectorised operands: the interleaved DS-read / MFMA schedule (18.05 vs 18.87 ms on FC-1000);
     // NIIDMIX_DENSE_SCHED=0 restores the compiler's schedule (tuning)
     const char *sc = getenv("NIIDMIX_DENSE_SCHED");
+    const bool sched = vec && avec && !(sc && sc[0] == '0');
     // K-steps of 16 (168 VGPRs, half the LDS: three blocks per CU) 17.2 vs 18.0 ms with 32 (256
     // VGPRs, two blocks; NIIDMIX_DENSE_BK=32 restores it, =8 and NIIDMIX_DENSE_OCC=4: tuning)
-    const char *bk = getenv("NIIDMIX_DENSE_BK");
-    const char *oc = getenv("NIIDMIX_DENSE_OCC");
-    const int bkv = bk ? atoi(bk) : 16, occ = oc ? atoi(oc) : 0;
-    if (vec && avec && !(sc && sc[0] == '0') && (bkv == 16 || bkv == 8)) {
-#define NIIDMIX_DENSE_T(B, O) hipLaunchKernelGGL((k_mix_dense<true, true, true, B, O>), grid, block, 0, s, x, ld_x, y, ld_y, n, p, w, n_it, n_items, row_ptr, col, val)
-        if (bkv == 16) { if (occ == 4) NIIDMIX_DENSE_T(16, 4); else NIIDMIX_DENSE_T(16, 3); }
-        else { if (occ == 4) NIIDMIX_DENSE_T(8, 4); else NIIDMIX_DENSE_T(8, 3); }
-#undef NIIDMIX_DENSE_T
-        return check_launch("k_mix_dense");
-    }
-    if (vec && avec && !(sc && sc[0] == '0')) {
-        hipLaunchKernelGGL((k_mix_dense<true, true, true>), grid, block, 0, s, x, ld_x, y, ld_y, n, p, w, n_it, n_items, row_ptr, col, val);
-        return check_launch("k_mix_dense");
-    }
-    if (vec) { if (avec) NIIDMIX_DENSE(true, true); else NIIDMIX_DENSE(true, false); }
-    else     { if (avec) NIIDMIX_DENSE(false, true); else NIIDMIX_DENSE(false, false); }
-#undef NIIDMIX_DENSE
+    const int bkv = env_int("NIIDMIX_DENSE_BK", 16), occ = env_int("NIIDMIX_DENSE_OCC", 0);
+    auto kfn = !sched ? pick<true, false>(vec, [&](auto V) { return pick<true, false>(avec, [&](auto A) {
+                            return k_mix_dense<V(), A()>; }); })
+               : (bkv == 16 || bkv == 8) ? pick<16, 8>(bkv, [&](auto B) { return pick<true, false>(occ == 4, [&](auto O4) {
+                                               return k_mix_dense<true, true, true, B(), O4() ? 4 : 3>; }); })
+                                         : &k_mix_dense<true, true, true>;
+    hipLaunchKernelGGL(kfn, dim3((unsigned)grid_for(n_items)), dim3(256), 0, s, x, ld_x, y, ld_y, n, p, w,
+                       n_it, n_items, row_ptr, col, val);
     return check_launch("k_mix_dense");
 }
 
@@ -4930,124 +4906,111 @@ int niidmix_mix_dense_bf16x6_f32(const float *x, int64_t ld_x, float *y, int64_t
     if (n < 0 || p < 0) return set_error(NIIDMIX_EINVAL, "negative size");
     if (n == 0 || p == 0) return NIIDMIX_OK;
     if (!x || !y || !wp || !row_ptr || !col || !val) return set_error(NIIDMIX_EINVAL, "null pointer");
-    if (ld_x < p || ld_y < p) return set_error(NIIDMIX_EINVAL, "leading dimension < p");
+    if (int rc = check_ld(ld_x, ld_y, p)) return rc;
     if (reinterpret_cast<uintptr_t>(wp) & 15) return set_error(NIIDMIX_EUNSUPPORTED, "wp not 16-B aligned");
-    if (overlaps(x, (n - 1) * ld_x + p, y, (n - 1) * ld_y + p))
-        return set_error(NIIDMIX_EALIAS, "x and y overlap (mixing is out-of-place / Jacobi)");
+    if (int rc = check_overlap(x, ld_x, y, ld_y, n, p)) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int64_t mpad = (n + kB6M - 1) / kB6M * kB6M, kpad = (n + kB6K - 1) / kB6K * kB6K;
     if (16 * ld_x * 4 >= (int64_t)0x7fffffffLL || 3 * mpad * kpad * 2 >= (int64_t)0x7fffffffLL)
         return set_error(NIIDMIX_EUNSUPPORTED, "bf16x6 dense GEMM: 16 rows of ld_x %lld or the split W "
                          "of n %lld exceed 2^31 B (use niidmix_mix_dense_f32)", (long long)ld_x, (long long)n);
+    // The three kernels take one argument list: a block tile of tile_m rows x 64 wn columns per
+    // item, `threads` lanes, `lds` B of dynamic LDS (opted in whatever its size).
+    auto launch = [&](auto kfn, const char *name, int64_t tile_m, int wn, int threads, size_t lds) {
+        const int64_t n_it = mpad / tile_m, n_jt = (p + 64 * wn - 1) / (64 * wn);
+        const int64_t n_items = n_it * ((n_jt + 7) / 8) * 8;
+        if (int rc = lds_opt_in(kfn, lds, name)) return rc;
+        hipLaunchKernelGGL(kfn, dim3((unsigned)grid_for(n_items)), dim3(threads), lds, s, x, ld_x, y, ld_y,
+                           n, p, wp, mpad, kpad, n_it, n_items, row_ptr, col, val);
+        return check_launch(name);
+    };
     // block tile 256 x 256 (8 waves of 128 x 64: X re-read by 4 row tiles instead of 8, 48 MFMAs
     // per wave between barriers): 9.81-9.86 vs 11.20-11.30 ms for 128 x 256 on the same box
     // (profiles/r05/dense_b6/); NIIDMIX_DENSE_B6_TM=2 selects the latter (with _WN / _SCHED: A/B)
-    const int tm = (getenv("NIIDMIX_DENSE_B6_TM") && atoi(getenv("NIIDMIX_DENSE_B6_TM")) == 2) ? 2 : 4;
+    const int tm = env_int("NIIDMIX_DENSE_B6_TM", 4, {2});
     // tuning A/B of the 128 x 256 tile (TM 2): NIIDMIX_DENSE_B6_WN=2 128 x 128 (4 waves, two blocks
     // per CU); NIIDMIX_DENSE_B6_SCHED 2 the compiler's schedule (11.2 ms on FC-1000 at P = 2^20),
     // 0 / 1 operand reads in three slices with the split beside / after the MFMAs (11.6-12.4 ms,
     // profiles/r05/dense_b6/)
     // SCHED 3 (loads pinned at the top of each K-step) by default on the 256 x 256 tile: 9.70-9.75
     // vs 9.80-9.84 ms for the compiler's schedule (2), same box, interleaved (profiles/r05/dense_b6/)
-    int wn = 4, sched = tm == 4 ? 3 : 2;
-    if (const char *e = getenv("NIIDMIX_DENSE_B6_WN")) if (atoi(e) == 2) wn = 2;
-    if (const char *e = getenv("NIIDMIX_DENSE_B6_SCHED")) { const int v = atoi(e); if (v >= 0 && v <= 3) sched = v; }
-#define NIIDMIX_B6T(WN, SC, AB, TM) do { \
-        const int64_t n_it = mpad / (64 * TM); \
-        const int64_t n_jt = (p + 64 * WN - 1) / (64 * WN); \
-        const int64_t n_items = n_it * ((n_jt + 7) / 8) * 8; \
-        const size_t lds = (size_t)2 * 3 * (64 * TM + 64 * WN) * 2 * sizeof(uint4); \
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_mix_dense_b6<WN, SC, AB, TM>), \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) \
-            return set_error(NIIDMIX_EHIP, "k_mix_dense_b6: %zu B of LDS refused", lds); \
-        hipLaunchKernelGGL((k_mix_dense_b6<WN, SC, AB, TM>), dim3((unsigned)grid_for(n_items)), dim3(128 * WN), lds, s, \
-                           x, ld_x, y, ld_y, n, p, wp, mpad, kpad, n_it, n_items, row_ptr, col, val); \
-    } while (0)
+    const int wn = env_int("NIIDMIX_DENSE_B6_WN", 4, {2});
+    const int sched = env_int("NIIDMIX_DENSE_B6_SCHED", tm == 4 ? 3 : 2, {0, 1, 2, 3});
     // W tiles by LDS-DMA (k_mix_dense_b6d): NIIDMIX_DENSE_B6_DMA = "WN,NA[,XD]" -- 4,3 (256 x 256,
     // one block per CU, W two K-steps ahead), 4,2, or 2,2 (256 x 128, two blocks per CU); XD 3:
     // X fetched three K-steps ahead (a third register set, with the 2-deep W ring)
-    if (const char *e = getenv("NIIDMIX_DENSE_B6_DMA")) {
-        int dwn = 0, dna = 0, dxd = 2;
-        if (sscanf(e, "%d,%d,%d", &dwn, &dna, &dxd) >= 2 && dwn != 0) {
-#define NIIDMIX_B6D(WN, NA, XD) do { \
-            const int64_t n_it = mpad / 256, n_jt = (p + 64 * WN - 1) / (64 * WN); \
-            const int64_t n_items = n_it * ((n_jt + 7) / 8) * 8; \
-            const size_t lds = ((size_t)NA * 3 * 256 * 2 + (size_t)2 * 3 * 64 * WN * 2) * sizeof(uint4); \
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_mix_dense_b6d<WN, 4, NA, XD>), \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) \
-                return set_error(NIIDMIX_EHIP, "k_mix_dense_b6d: %zu B of LDS refused", lds); \
-            hipLaunchKernelGGL((k_mix_dense_b6d<WN, 4, NA, XD>), dim3((unsigned)grid_for(n_items)), dim3(128 * WN), lds, s, \
-                               x, ld_x, y, ld_y, n, p, wp, mpad, kpad, n_it, n_items, row_ptr, col, val); \
-        } while (0)
-            if (dwn == 4 && dna == 3 && dxd == 2) NIIDMIX_B6D(4, 3, 2);
-            else if (dwn == 4 && dna == 2 && dxd == 2) NIIDMIX_B6D(4, 2, 2);
-            else if (dwn == 4 && dna == 2 && dxd == 3) NIIDMIX_B6D(4, 2, 3);
-            else if (dwn == 2 && dna == 2 && dxd == 2) NIIDMIX_B6D(2, 2, 2);
-            else if (dwn == 2 && dna == 2 && dxd == 3) NIIDMIX_B6D(2, 2, 3);
-            else return set_error(NIIDMIX_EINVAL, "NIIDMIX_DENSE_B6_DMA=%s: 4,3 / 4,2[,3] / 2,2[,3]", e);
+    int dwn = 0, dna = 0, dxd = 2;
+    if (env_scan("NIIDMIX_DENSE_B6_DMA", "%d,%d,%d", &dwn, &dna, &dxd) >= 2 && dwn != 0) {
+        decltype(&k_mix_dense_b6d<4, 4, 3, 2>) kfn = nullptr;
+#define NIIDMIX_B6D(WN, NA, XD) if (dwn == WN && dna == NA && dxd == XD) kfn = k_mix_dense_b6d<WN, 4, NA, XD>
+        NIIDMIX_B6D(4, 3, 2); NIIDMIX_B6D(4, 2, 2); NIIDMIX_B6D(4, 2, 3); NIIDMIX_B6D(2, 2, 2); NIIDMIX_B6D(2, 2, 3);
 #undef NIIDMIX_B6D
-            return check_launch("k_mix_dense_b6d");
-        }
+        if (!kfn) return set_error(NIIDMIX_EINVAL, "NIIDMIX_DENSE_B6_DMA=%s: 4,3 / 4,2[,3] / 2,2[,3]", getenv("NIIDMIX_DENSE_B6_DMA"));
+        return launch(kfn, "k_mix_dense_b6d", 256, dwn, 128 * dwn,
+                      ((size_t)dna * 3 * 256 * 2 + (size_t)2 * 3 * 64 * dwn * 2) * sizeof(uint4));
     }
     // one wave per SIMD (k_mix_dense_b6w, 256 x 256 tile of 4 waves of 128 x 128): tuning A/B
-    if (const char *e = getenv("NIIDMIX_DENSE_B6_W1")) if (atoi(e) == 1) {
-        const int64_t n_it = mpad / 256, n_jt = (p + 255) / 256;
-        const int64_t n_items = n_it * ((n_jt + 7) / 8) * 8;
-        const size_t lds = (size_t)2 * 3 * (256 + 256) * 2 * sizeof(uint4);
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_mix_dense_b6w),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return set_error(NIIDMIX_EHIP, "k_mix_dense_b6w: %zu B of LDS refused", lds);
-        hipLaunchKernelGGL(k_mix_dense_b6w, dim3((unsigned)grid_for(n_items)), dim3(256), lds, s,
-                           x, ld_x, y, ld_y, n, p, wp, mpad, kpad, n_it, n_items, row_ptr, col, val);
-        return check_launch("k_mix_dense_b6w");
-    }
+    if (env_int("NIIDMIX_DENSE_B6_W1", 0) == 1)
+        return launch(k_mix_dense_b6w, "k_mix_dense_b6w", 256, 4, 256, (size_t)2 * 3 * (256 + 256) * 2 * sizeof(uint4));
+    // k_mix_dense_b6<WN, SCHED, ABL, TM>: the 256-row tile (TM 4) is built 4 waves wide with SCHED
+    // 2 and 3; every other choice runs the 128-row tile (TM 2), built for WN 2 / 4 x SCHED 0 / 1 / 2
+    int ktm = 4, kwn = 4;
+    decltype(&k_mix_dense_b6<4, 2, 0, 4>) kfn = nullptr;
     int abl = 0;
 #ifdef NIIDMIX_ABLATIONS
     // time-split builds only (wrong results by construction; never in the shipped library)
-    if (const char *e = getenv("NIIDMIX_DENSE_B6_ABL")) abl = atoi(e);
+    abl = env_int("NIIDMIX_DENSE_B6_ABL", 0);
 #endif
-#define NIIDMIX_B6(WN, SC, AB) NIIDMIX_B6T(WN, SC, AB, 2)
-    if (tm == 4 && abl == 0 && wn == 4 && sched == 2) NIIDMIX_B6T(4, 2, 0, 4);
-    else if (tm == 4 && abl == 0 && wn == 4 && sched == 3) NIIDMIX_B6T(4, 3, 0, 4);
+    if (tm == 4 && abl == 0 && wn == 4 && sched >= 2)
+        kfn = pick<2, 3>(sched, [](auto S) { return k_mix_dense_b6<4, S(), 0, 4>; });
 #ifdef NIIDMIX_ABLATIONS
-    else if (abl == 1) NIIDMIX_B6T(4, 2, 1, 4);
-    else if (abl == 2) NIIDMIX_B6T(4, 2, 2, 4);
-    else if (abl == 3) NIIDMIX_B6T(4, 2, 3, 4);
-    else if (abl == 4) NIIDMIX_B6T(4, 3, 4, 4);
-    else if (abl == 5) NIIDMIX_B6T(4, 3, 0, 4);
+    else if (abl >= 1 && abl <= 5)      // 1..3 on SCHED 2, 4 on SCHED 3, 5: SCHED 3 without ablation
+        kfn = pick<1, 2, 3, 4, 5>(abl, [](auto A) { return k_mix_dense_b6<4, A() >= 4 ? 3 : 2, A() == 5 ? 0 : A(), 4>; });
 #endif
-    else if (wn == 2) { if (sched >= 2) NIIDMIX_B6(2, 2, 0); else if (sched == 1) NIIDMIX_B6(2, 1, 0); else NIIDMIX_B6(2, 0, 0); }
-    else { if (sched >= 2) NIIDMIX_B6(4, 2, 0); else if (sched == 1) NIIDMIX_B6(4, 1, 0); else NIIDMIX_B6(4, 0, 0); }
-#undef NIIDMIX_B6
-#undef NIIDMIX_B6T
-    return check_launch("k_mix_dense_b6");
+    else {
+        ktm = 2;
+        kwn = wn;
+        kfn = pick<2, 4>(wn, [&](auto W) { return pick<2, 1, 0>(sched >= 2 ? 2 : sched, [&](auto S) {
+            return k_mix_dense_b6<W(), S(), 0, 2>; }); });
+    }
+    return launch(kfn, "k_mix_dense_b6", 64 * ktm, kwn, 128 * kwn,
+                  (size_t)2 * 3 * (64 * ktm + 64 * kwn) * 2 * sizeof(uint4));
 }
 
 int niidmix_mean_rows_f32(const float *x, int64_t ld_x, int64_t n, int64_t p, float *mean,
                           double *dist2, int mode, void *stream) {
     if (n < 0 || p < 0) return set_error(NIIDMIX_EINVAL, "negative size");
-    if (mode != NIIDMIX_MODE_EXACT && mode != NIIDMIX_MODE_FAST)
-        return set_error(NIIDMIX_EINVAL, "unknown mode %d", mode);
+    if (int rc = check_mode(mode)) return rc;                   // no flags accepted
     if (n == 0 || p == 0) return NIIDMIX_OK;
     if (!x || !mean) return set_error(NIIDMIX_EINVAL, "null pointer");
-    if (ld_x < p) return set_error(NIIDMIX_EINVAL, "leading dimension < p");
-    if (overlaps(x, (n - 1) * ld_x + p, mean, p)) return set_error(NIIDMIX_EALIAS, "mean overlaps x");
+    if (int rc = check_ld(ld_x, ld_x, p)) return rc;
+    if (overlaps(x, slab_extent(n, ld_x, p), mean, p)) return set_error(NIIDMIX_EALIAS, "mean overlaps x");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const float w = (float)(1.0 / (double)n);
     const int64_t blocks = (p + 255) / 256 < 16384 ? (p + 255) / 256 : 16384;
-    if (mode == NIIDMIX_MODE_EXACT)
-        hipLaunchKernelGGL((k_mean_cols<true>), dim3((unsigned)blocks), dim3(256), 0, s, x, ld_x, n, p, w, mean);
-    else
-        hipLaunchKernelGGL((k_mean_cols<false>), dim3((unsigned)blocks), dim3(256), 0, s, x, ld_x, n, p, w, mean);
+    auto kfn = pick<true, false>(mode == NIIDMIX_MODE_EXACT, [](auto E) { return k_mean_cols<E()>; });
+    hipLaunchKernelGGL(kfn, dim3((unsigned)blocks), dim3(256), 0, s, x, ld_x, n, p, w, mean);
     int rc = check_launch("k_mean_cols");
     if (rc != NIIDMIX_OK || !dist2) return rc;
     hipLaunchKernelGGL(k_row_dist2, dim3((unsigned)n), dim3(256), 0, s, x, ld_x, p, mean, dist2);
     return check_launch("k_row_dist2");
 }
 
-static bool grad_nt() {
-    const char *e = getenv("NIIDMIX_GRAD_NT");
-    return !(e && atoi(e) == 0);
+// Row-major slabs: bc_shift 62, block strides 0; column-blocked slabs (float4 only): block_cols =
+// 1024 << bc_shift.
+static int launch_grad_segment_mean(const float *g, int64_t ld_g, float *y, int64_t ld_y, int64_t p,
+                                    int64_t n_seg, const int32_t *seg_ptr, const int32_t *seg_row,
+                                    bool vec4, int bc_shift, int64_t bs_g, int64_t bs_y, void *stream) {
+    int64_t n_chunks;
+    const dim3 grid = row_chunk_grid(n_seg, p, vec4, &n_chunks);
+    // non-temporal gradient-row loads (each row is read once): 1.375 vs 1.401 ms on the headline
+    // shape, same box (profiles/r05/grad_nt/); NIIDMIX_GRAD_NT=0 restores the default cache policy
+    const bool nt = env_int("NIIDMIX_GRAD_NT", 1) != 0;
+    auto kfn = vec4 ? pick<true, false>(nt, [](auto NT) { return k_grad_segment_mean<4, 8, NT()>; })
+                    : &k_grad_segment_mean<1, 16>;
+    hipLaunchKernelGGL(kfn, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), g, ld_g, y, ld_y, p,
+                       n_seg, seg_ptr, seg_row, n_chunks, bc_shift, bs_g, bs_y);
+    return check_launch("k_grad_segment_mean");
 }
 
 int niidmix_grad_segment_mean_f32(const float *g, int64_t ld_g, float *y, int64_t ld_y,
@@ -5056,25 +5019,9 @@ int niidmix_grad_segment_mean_f32(const float *g, int64_t ld_g, float *y, int64_
     if (p < 0 || n_seg < 0 || n_rows < 0) return set_error(NIIDMIX_EINVAL, "negative size");
     if (n_seg == 0 || p == 0 || n_rows == 0) return NIIDMIX_OK;
     if (!g || !y || !seg_ptr || !seg_row) return set_error(NIIDMIX_EINVAL, "null pointer");
-    if (ld_g < p || ld_y < p) return set_error(NIIDMIX_EINVAL, "leading dimension < p");
-    if (overlaps(g, (n_rows - 1) * ld_g + p, y, (n_rows - 1) * ld_y + p))
-        return set_error(NIIDMIX_EALIAS, "g and y overlap: the mean is out-of-place");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const bool vec4 = p % 4 == 0 && ld_g % 4 == 0 && ld_y % 4 == 0 && aligned16(g) && aligned16(y);
-    const int64_t cols = vec4 ? 1024 : 256;
-    const int64_t n_chunks = (p + cols - 1) / cols;
-    const int64_t n_items = n_seg * n_chunks;
-    const dim3 grid((unsigned)(n_items < kMaxGrid ? n_items : kMaxGrid)), block(256);
-    if (vec4 && grad_nt())
-        hipLaunchKernelGGL((k_grad_segment_mean<4, 8, true>), grid, block, 0, s, g, ld_g, y, ld_y, p, n_seg,
-                           seg_ptr, seg_row, n_chunks, 62, (int64_t)0, (int64_t)0);
-    else if (vec4)
-        hipLaunchKernelGGL((k_grad_segment_mean<4, 8, false>), grid, block, 0, s, g, ld_g, y, ld_y, p, n_seg,
-                           seg_ptr, seg_row, n_chunks, 62, (int64_t)0, (int64_t)0);
-    else
-        hipLaunchKernelGGL((k_grad_segment_mean<1, 16>), grid, block, 0, s, g, ld_g, y, ld_y, p, n_seg,
-                           seg_ptr, seg_row, n_chunks, 62, (int64_t)0, (int64_t)0);
-    return check_launch("k_grad_segment_mean");
+    if (int rc = check_slab_pair(g, ld_g, y, ld_y, n_rows, p, "g and y overlap: the mean is out-of-place")) return rc;
+    return launch_grad_segment_mean(g, ld_g, y, ld_y, p, n_seg, seg_ptr, seg_row,
+                                    vec_width({p, ld_g, ld_y}, {g, y}) == 4, 62, 0, 0, stream);
 }
 
 int niidmix_grad_segment_mean_blocked_f32(const float *g, float *y, int64_t n_rows, int64_t p,
@@ -5085,32 +5032,15 @@ int niidmix_grad_segment_mean_blocked_f32(const float *g, float *y, int64_t n_ro
     if (p < 0 || n_seg < 0 || n_rows < 0) return set_error(NIIDMIX_EINVAL, "negative size");
     if (n_seg == 0 || p == 0 || n_rows == 0) return NIIDMIX_OK;
     if (!g || !y || !seg_ptr || !seg_row) return set_error(NIIDMIX_EINVAL, "null pointer");
-    if (block_cols < 1024 || (block_cols & (block_cols - 1)))
-        return set_error(NIIDMIX_EINVAL, "block_cols %lld: a power of two >= 1024", (long long)block_cols);
-    if (ld < block_cols || block_stride_g < ld || block_stride_y < ld)
-        return set_error(NIIDMIX_EINVAL, "row stride < block_cols or block stride < row stride");
-    {   // extents of both blocked slabs, each with its own block stride
-        const int64_t k_blocks = (p + block_cols - 1) / block_cols;
-        if (overlaps(g, (k_blocks - 1) * block_stride_g + (n_rows - 1) * ld + block_cols,
-                     y, (k_blocks - 1) * block_stride_y + (n_rows - 1) * ld + block_cols))
-            return set_error(NIIDMIX_EALIAS, "g and y overlap: the mean is out-of-place");
-    }
-    if (p % 4 || ld % 4 || block_stride_g % 4 || block_stride_y % 4 || !aligned16(g) || !aligned16(y))
+    const char *stride_msg = "row stride < block_cols or block stride < row stride";
+    if (int rc = check_blocked_pair(g, y, n_rows, p, ld, block_cols, block_stride_g, block_stride_y, 1024,
+                                    stride_msg, stride_msg, "g and y overlap: the mean is out-of-place"))
+        return rc;
+    if (vec_width({p, ld, block_stride_g, block_stride_y}, {g, y}) != 4)
         return set_error(NIIDMIX_EUNSUPPORTED, "blocked gradient mean needs p, strides % 4 == 0 and 16-B aligned slabs");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int64_t n_chunks = (p + 1023) / 1024;
-    const int64_t n_items = n_seg * n_chunks;
-    const dim3 grid((unsigned)(n_items < kMaxGrid ? n_items : kMaxGrid)), block(256);
-    const int shift = __builtin_ctzll((unsigned long long)(block_cols / 1024));
-    // non-temporal gradient-row loads (each row is read once): 1.375 vs 1.401 ms on the headline
-    // shape, same box (profiles/r05/grad_nt/); NIIDMIX_GRAD_NT=0 restores the default cache policy
-    if (grad_nt())
-        hipLaunchKernelGGL((k_grad_segment_mean<4, 8, true>), grid, block, 0, s, g, ld, y, ld, p, n_seg, seg_ptr,
-                           seg_row, n_chunks, shift, block_stride_g, block_stride_y);
-    else
-        hipLaunchKernelGGL((k_grad_segment_mean<4, 8, false>), grid, block, 0, s, g, ld, y, ld, p, n_seg, seg_ptr,
-                           seg_row, n_chunks, shift, block_stride_g, block_stride_y);
-    return check_launch("k_grad_segment_mean");
+    return launch_grad_segment_mean(g, ld, y, ld, p, n_seg, seg_ptr, seg_row, true,
+                                    __builtin_ctzll((unsigned long long)(block_cols / 1024)),
+                                    block_stride_g, block_stride_y, stream);
 }
 
 int niidmix_sgd_step_rows_f32(float *p, int64_t ld_p, const float *g, int64_t ld_g, int64_t ncols,
@@ -5118,17 +5048,13 @@ int niidmix_sgd_step_rows_f32(float *p, int64_t ld_p, const float *g, int64_t ld
     if (ncols < 0 || n_rows < 0) return set_error(NIIDMIX_EINVAL, "negative size");
     if (ncols == 0 || n_rows == 0) return NIIDMIX_OK;
     if (!p || !g || !rows) return set_error(NIIDMIX_EINVAL, "null pointer");
-    if (ld_p < ncols || ld_g < ncols) return set_error(NIIDMIX_EINVAL, "leading dimension < ncols");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const bool vec4 = ncols % 4 == 0 && ld_p % 4 == 0 && ld_g % 4 == 0 && aligned16(p) && aligned16(g);
-    const int64_t cols = vec4 ? 1024 : 256;
-    const int64_t n_chunks = (ncols + cols - 1) / cols;
-    const int64_t items = n_rows * n_chunks;
-    const dim3 grid((unsigned)(items < kMaxGrid ? items : kMaxGrid)), block(256);
-    if (vec4)
-        hipLaunchKernelGGL(k_sgd_step_rows<4>, grid, block, 0, s, p, ld_p, g, ld_g, ncols, rows, n_rows, neg_lr, n_chunks);
-    else
-        hipLaunchKernelGGL(k_sgd_step_rows<1>, grid, block, 0, s, p, ld_p, g, ld_g, ncols, rows, n_rows, neg_lr, n_chunks);
+    if (int rc = check_ld(ld_p, ld_g, ncols, "ncols")) return rc;
+    const int vw = vec_width({ncols, ld_p, ld_g}, {p, g}) == 4 ? 4 : 1;
+    int64_t n_chunks;
+    const dim3 grid = row_chunk_grid(n_rows, ncols, vw == 4, &n_chunks);
+    auto kfn = pick<4, 1>(vw, [](auto V) { return k_sgd_step_rows<V()>; });
+    hipLaunchKernelGGL(kfn, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, ld_p, g, ld_g,
+                       ncols, rows, n_rows, neg_lr, n_chunks);
     return check_launch("k_sgd_step_rows");
 }
 
@@ -5139,30 +5065,19 @@ int niidmix_sgd_momentum_step_rows_f32(float *p, int64_t ld_p, const float *g, i
     if (ncols < 0 || n_rows < 0) return set_error(NIIDMIX_EINVAL, "negative size");
     if (ncols == 0 || n_rows == 0) return NIIDMIX_OK;
     if (!p || !g || !buf || !rows) return set_error(NIIDMIX_EINVAL, "null pointer");
-    if (ld_p < ncols || ld_g < ncols || ld_b < ncols)
-        return set_error(NIIDMIX_EINVAL, "leading dimension < ncols");
+    if (int rc = check_ld(ld_p, ld_g, ncols, "ncols")) return rc;
+    if (int rc = check_ld(ld_b, ld_b, ncols, "ncols")) return rc;
     // `rows` lives on the device: n_rows distinct rows reach at least row n_rows - 1
-    const int64_t ext_p = (n_rows - 1) * ld_p + ncols, ext_g = (n_rows - 1) * ld_g + ncols,
-                  ext_b = (n_rows - 1) * ld_b + ncols;
-    if (overlaps(p, ext_p, g, ext_g)) return set_error(NIIDMIX_EALIAS, "p and g overlap");
-    if (overlaps(p, ext_p, buf, ext_b)) return set_error(NIIDMIX_EALIAS, "p and buf overlap");
-    if (overlaps(g, ext_g, buf, ext_b)) return set_error(NIIDMIX_EALIAS, "g and buf overlap");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const bool vec4 = ncols % 4 == 0 && ld_p % 4 == 0 && ld_g % 4 == 0 && ld_b % 4 == 0 &&
-                      aligned16(p) && aligned16(g) && aligned16(buf);
-    const int64_t cols = vec4 ? 1024 : 256;
-    const int64_t n_chunks = (ncols + cols - 1) / cols;
-    const int64_t items = n_rows * n_chunks;
-    const dim3 grid((unsigned)(items < kMaxGrid ? items : kMaxGrid)), block(256);
-#define NIIDMIX_MOMENTUM_LAUNCH(V, FIRST)                                                          \
-    hipLaunchKernelGGL((k_sgd_momentum_step_rows<V, FIRST>), grid, block, 0, s, p, ld_p, g, ld_g,  \
-                       buf, ld_b, ncols, rows, n_rows, neg_lr, momentum, n_chunks)
-    if (vec4) {
-        if (first) NIIDMIX_MOMENTUM_LAUNCH(4, true); else NIIDMIX_MOMENTUM_LAUNCH(4, false);
-    } else {
-        if (first) NIIDMIX_MOMENTUM_LAUNCH(1, true); else NIIDMIX_MOMENTUM_LAUNCH(1, false);
-    }
-#undef NIIDMIX_MOMENTUM_LAUNCH
+    if (int rc = check_overlap(p, ld_p, g, ld_g, n_rows, ncols, "p and g overlap")) return rc;
+    if (int rc = check_overlap(p, ld_p, buf, ld_b, n_rows, ncols, "p and buf overlap")) return rc;
+    if (int rc = check_overlap(g, ld_g, buf, ld_b, n_rows, ncols, "g and buf overlap")) return rc;
+    const int vw = vec_width({ncols, ld_p, ld_g, ld_b}, {p, g, buf}) == 4 ? 4 : 1;
+    int64_t n_chunks;
+    const dim3 grid = row_chunk_grid(n_rows, ncols, vw == 4, &n_chunks);
+    auto kfn = pick<4, 1>(vw, [&](auto V) { return pick<true, false>(first != 0, [&](auto F) {
+        return k_sgd_momentum_step_rows<V(), F()>; }); });
+    hipLaunchKernelGGL(kfn, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, ld_p, g, ld_g,
+                       buf, ld_b, ncols, rows, n_rows, neg_lr, momentum, n_chunks);
     return check_launch("k_sgd_momentum_step_rows");
 }
 
@@ -5171,21 +5086,18 @@ int niidmix_update_rows_f32(const float *x, int64_t ld_x, float *y, int64_t ld_y
     if (n_rows < 0 || p < 0) return set_error(NIIDMIX_EINVAL, "negative size");
     if (n_rows == 0 || p == 0) return NIIDMIX_OK;
     if (!x || !y || !avg) return set_error(NIIDMIX_EINVAL, "null pointer");
-    if (ld_x < p || ld_y < p) return set_error(NIIDMIX_EINVAL, "leading dimension < p");
-    const int64_t ext_x = (n_rows - 1) * ld_x + p, ext_y = (n_rows - 1) * ld_y + p;
+    if (int rc = check_ld(ld_x, ld_y, p)) return rc;
+    const int64_t ext_x = slab_extent(n_rows, ld_x, p), ext_y = slab_extent(n_rows, ld_y, p);
     if (!(x == y && ld_x == ld_y) && overlaps(x, ext_x, y, ext_y))
         return set_error(NIIDMIX_EALIAS, "x and y overlap without being the same slab");
     if (overlaps(x, ext_x, avg, p) || overlaps(y, ext_y, avg, p))
         return set_error(NIIDMIX_EALIAS, "avg overlaps a slab");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const bool vec4 = p % 4 == 0 && ld_x % 4 == 0 && ld_y % 4 == 0 && aligned16(x) && aligned16(y) &&
-                      aligned16(avg);
-    const int64_t cols = vec4 ? 1024 : 256;
-    const int64_t n_chunks = (p + cols - 1) / cols;
-    const int64_t items = n_rows * n_chunks;
-    const dim3 grid((unsigned)(items < kMaxGrid ? items : kMaxGrid)), block(256);
-    if (vec4) hipLaunchKernelGGL(k_update_rows<4>, grid, block, 0, s, x, ld_x, y, ld_y, n_rows, p, avg, n_chunks);
-    else hipLaunchKernelGGL(k_update_rows<1>, grid, block, 0, s, x, ld_x, y, ld_y, n_rows, p, avg, n_chunks);
+    const int vw = vec_width({p, ld_x, ld_y}, {x, y, avg}) == 4 ? 4 : 1;
+    int64_t n_chunks;
+    const dim3 grid = row_chunk_grid(n_rows, p, vw == 4, &n_chunks);
+    auto kfn = pick<4, 1>(vw, [](auto V) { return k_update_rows<V()>; });
+    hipLaunchKernelGGL(kfn, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x, ld_x, y, ld_y,
+                       n_rows, p, avg, n_chunks);
     return check_launch("k_update_rows");
 }
 

@@ -437,6 +437,40 @@ def test_strided_slab_and_odd_p(gpu, oracle_mod):
     assert torch.all(outbig[:, :20] == 7.0) and torch.all(outbig[:, 277:] == 7.0)
 
 
+def test_vector_width_by_alignment(gpu, oracle_mod):
+    """The csr, ell, tile and band entry points choose 4, 2 or 1 floats per lane from p, the row
+    strides and the slabs' alignment: views that start 0, 2 and 1 floats into a 16-B aligned slab
+    (8-node ring, p = 40, ld = 48) take each width, and the exact kernels are bitwise the oracle at
+    all of them.  The band kernel has no one-float form: it refuses the last view."""
+    from niidmix import _lib
+    from niidmix.topology import mh_csr
+    ops = _ops()
+    n, p, ld = 8, 40, 48
+    csr = mh_csr(n, {i: [(i - 1) % n, (i + 1) % n] for i in range(n)})
+    m = _tile_mixer({"row_ptr": csr.row_ptr, "col": csr.col, "val": csr.val}, gpu, 8)
+    assert m.ell == 3 and m.band == 1
+    xh = np.random.default_rng(40).standard_normal((n, p)).astype(np.float32)
+    ref = oracle_mod.mix_exact_c(xh, csr.row_ptr, csr.col, csr.val)
+    xbuf = torch.zeros(n * ld + 4, device=gpu)
+    ybuf = torch.empty_like(xbuf)
+    for off in (0, 2, 1):
+        xv = xbuf[off:off + n * ld].view(n, ld)[:, :p]
+        out = ybuf[off:off + n * ld].view(n, ld)[:, :p]
+        assert xv.data_ptr() % 16 == 4 * off and out.data_ptr() % 16 == 4 * off
+        xv.copy_(torch.from_numpy(xh))
+        for kernel in ("csr-exact", "ell-exact", "tile-exact", "band-exact"):
+            ybuf.fill_(7.0)
+            if kernel == "band-exact" and off == 1:
+                rc = _lib.lib.niidmix_mix_band_f32(xv.data_ptr(), ld, out.data_ptr(), ld, n, p, 3, 1,
+                                                   m.e_col.data_ptr(), m.e_val.data_ptr(),
+                                                   m.e_len.data_ptr(), ops.EXACT, None)
+                assert rc == _lib.EUNSUPPORTED
+                continue
+            m(xv, out=out, kernel=kernel)
+            assert oracle_mod.bitwise_equal(out.cpu().numpy(), ref), (kernel, off)
+            assert torch.all(ybuf.view(-1)[off:off + n * ld].view(n, ld)[:, p:] == 7.0), (kernel, off)
+
+
 def test_errors(gpu):
     ops = _ops()
     g = load_golden("ring100_p257")
