@@ -23,7 +23,9 @@
  * the full extents of both (NIIDMIX_EALIAS), each slab with its own strides.
  *
  * ABI 6 (this header): niidmix_sgd_momentum_step_rows_f32 added (the optimizer step of
- * --learning-momentum on the device).
+ * --learning-momentum on the device); niidmix_linear_nll_grad_rows_f32 and its
+ * niidmix_linear_nll_grad_rows_scratch_elems added (local training of a linear classifier on the
+ * device: forward, loss and backward; a pure addition, the version is unchanged).
  * ABI 5: niidmix_dense_split_elems / niidmix_dense_split_w /
  * niidmix_mix_dense_bf16x6_f32 added (the dense GEMM on the bf16 matrix cores, fp32-accurate by
  * three-term splitting); niidmix_mix_strip_f32 refuses a strip that does not fit the device's LDS.
@@ -411,6 +413,49 @@ int niidmix_sgd_momentum_step_rows_f32(float *p, int64_t ld_p, const float *g, i
                                        float *buf, int64_t ld_b, int64_t ncols,
                                        const int32_t *rows, int64_t n_rows, float neg_lr,
                                        float momentum, int first, void *stream);
+
+/* Local training of a linear classifier on the listed rows: forward, mean NLL loss and backward of
+ * the reference's linear model (setup/model/linear.py: one nn.Linear(K, C), log_softmax, nll_loss)
+ * over each row's own batch, i.e. F.nll_loss(F.log_softmax(fc(x.view(-1, K)), 1), y).backward() on
+ * a zeroed gradient, for every listed node in one call (the drop-in's --device-training round:
+ * this call -> niidmix_sgd_step_rows_f32 / niidmix_sgd_momentum_step_rows_f32 -> mixing, the
+ * parameters never leaving HBM).
+ *   theta     [*, ld_t] parameters (device); row r is W as [C, K] row-major, then b [C]
+ *             (model.parameters() order), P = C * K + C columns
+ *   data      [S, K] samples (device), labels [S] int32 classes (device)
+ *   batch_idx [n_rows, b_max] int32 sample indices into data (device); entry i belongs to rows[i]
+ *   batch_len [n_rows] int32, 1 <= len <= b_max (device): entries past len are not read
+ *   rows      [n_rows] int32 distinct slab rows (device)
+ *   grad      [*, ld_g] gradients (device), row layout of theta: all P elements of a listed row are
+ *             written, other rows and columns past P are untouched
+ *   loss      [n_rows] mean batch loss of rows[i] (device)
+ *   scratch   caller-owned device buffer of at least
+ *             niidmix_linear_nll_grad_rows_scratch_elems(n_rows, b_max, C) floats (partial logits,
+ *             then dz); its contents are overwritten
+ * With z[s,c] = sum_k x[s,k] W[c,k] + b[c], m_s = max_c z[s,c], lse_s = m_s + log sum_c
+ * exp(z[s,c] - m_s):  loss = -(1/len) sum_s (z[s,y_s] - lse_s),  dz[s,c] = (exp(z[s,c] - lse_s) -
+ * [c == y_s]) / len,  dW[c,k] = sum_s dz[s,c] x[s,k],  db[c] = sum_s dz[s,c].
+ * fp32 FMAs in an order fixed by the launch shape (the sizes, leading dimensions and pointer
+ * alignments), no floating-point atomics: two calls on the same inputs give the same bits.  Not
+ * bit-identical to ATen's CPU result (another summation order); within 1e-5 of the
+ * condition-aware bound sum_s (p[s,c] + [c == y_s]) / len * |x[s,k]| (tests/test_gpu_train.py).
+ * Limits (NIIDMIX_EUNSUPPORTED beyond): C <= 1024, b_max * C <= 32768 (one row's dz in LDS),
+ * K <= 2^20.  float4 accesses when K and the leading dimension are multiples of 4 and the
+ * pointers 16-B aligned, scalar ones otherwise (any K, any ld).
+ * NIIDMIX_EINVAL: a null pointer, a negative or zero size, ld_t or ld_g < C * K + C, a scratch
+ * buffer that is too small.  NIIDMIX_EALIAS: grad (or scratch) overlaps theta over the least
+ * extent n_rows distinct rows can span, (n_rows - 1) * ld + P elements (the row list is on the
+ * device and is not read by the launcher, as for niidmix_sgd_momentum_step_rows_f32).
+ * batch_idx, batch_len, labels and rows are device data and are NOT checked by the launcher: an
+ * index outside data reads out of bounds (batch_len is clamped to [0, b_max]; a label outside
+ * [0, C) matches no class).  niidmix.train.DeviceTrainer checks them once per node set. */
+int64_t niidmix_linear_nll_grad_rows_scratch_elems(int64_t n_rows, int64_t b_max, int64_t C);
+int niidmix_linear_nll_grad_rows_f32(const float *theta, int64_t ld_t, const float *data,
+                                     const int32_t *labels, const int32_t *batch_idx,
+                                     const int32_t *batch_len, int64_t b_max, const int32_t *rows,
+                                     int64_t n_rows, float *grad, int64_t ld_g, float *loss,
+                                     int64_t K, int64_t C, float *scratch, int64_t scratch_elems,
+                                     void *stream);
 
 /* update_models(all_models, avg) after the 'sample' topology's uniform average (d_sgd.py:240-250,
  * :29-35): every row y_i := fl(fl(x_i * 0) + avg) (p.mul_(0.); p.add_(new)) — avg everywhere

@@ -4007,6 +4007,266 @@ __global__ __launch_bounds__(256) void k_sgd_momentum_step_rows(float *__restric
 }
 
 // ----------------------------------------------------------------------------------------------
+// Local training of a linear classifier on listed rows (niidmix_linear_nll_grad_rows_f32): row r
+// of theta is W [C, K] then b [C]; for its batch of len samples x_s = data[batch_idx[s]],
+//   z[s,c] = sum_k x[s,k] W[c,k] + b[c],   loss = -(1/len) sum_s (z[s,y_s] - lse_s),
+//   dz[s,c] = (exp(z[s,c] - lse_s) - [c == y_s]) / len,   dW = dz^T x,   db = sum_s dz
+// = F.nll_loss(F.log_softmax(fc(x), 1), y).backward() on a zeroed gradient.  Three launches, each
+// wide at any row count, no atomics (the summation order is a function of the launch shape only):
+//   k_lin_logits   per (row, K-chunk, tile slice): partial logits.  A wave owns a 4 x 4 tile of
+//                  (sample, class) pairs, its lanes split the chunk's columns (coalesced along k for
+//                  x and W alike), and the 16 per-lane sums are reduced across the wave by a
+//                  halving butterfly (8 + 4 + 2 + 1 + 2 exchanges instead of 16 x 6).
+//   k_lin_softmax  per row: chunk partials summed in chunk order + bias, max-subtracted softmax,
+//                  loss, dz written over the first chunk's partials.  A group of G lanes (the
+//                  power of two covering min(C, 64)) owns a sample.
+//   k_lin_dw       per (row, 256-lane column chunk, class-block slice): dz staged in LDS, a lane
+//                  owns V columns k and 16 classes at a time and sums over the samples in order;
+//                  x stays in registers across the class blocks when the batch has <= 16 samples.
+//                  The first chunk's block also writes db.
+// Scratch: [n_rows, split, b_max, C] floats, split = lin_split(n_rows) K-chunks at most.
+constexpr int64_t kLinMaxC = 1024;        // classes
+constexpr int64_t kLinMaxBC = 32768;      // b_max * C: dz of one row in LDS (128 KiB)
+constexpr int kLinDC = 16;                // classes per pass of k_lin_dw
+constexpr int kLinXR = 16;                // samples k_lin_dw keeps in registers
+
+__device__ __forceinline__ int lin_len(const int32_t *__restrict__ batch_len, int64_t i, int b_max) {
+    const int l = batch_len[i];
+    return l < 0 ? 0 : l > b_max ? b_max : l;
+}
+
+// Sums each of v[0..15] over the 64 lanes; lane l returns the total of entry
+// ((l & 1) << 3) | ((l & 2) << 1) | ((l & 4) >> 1) | ((l & 8) >> 3).
+__device__ __forceinline__ float lin_reduce16(float (&v)[16], int lane) {
+#pragma unroll
+    for (int st = 0; st < 4; ++st) {
+        const int half = 8 >> st;
+        const bool up = (lane >> st) & 1;
+#pragma unroll
+        for (int j = 0; j < half; ++j) {
+            const float send = up ? v[j] : v[j + half];
+            const float keep = up ? v[j + half] : v[j];
+            v[j] = keep + __shfl_xor(send, 1 << st);
+        }
+    }
+    float r = v[0];
+    r += __shfl_xor(r, 16);
+    r += __shfl_xor(r, 32);
+    return r;
+}
+
+template <int V>
+__global__ __launch_bounds__(256) void k_lin_logits(const float *__restrict__ theta, int64_t ld_t,
+                                                    const float *__restrict__ data,
+                                                    const int32_t *__restrict__ batch_idx,
+                                                    const int32_t *__restrict__ batch_len, int b_max,
+                                                    const int32_t *__restrict__ rows, int K, int C,
+                                                    int kchunk, int n_kc, int split,
+                                                    float *__restrict__ part) {
+    const int64_t i = blockIdx.x / n_kc;
+    const int kc = (int)(blockIdx.x % n_kc);
+    const int len = lin_len(batch_len, i, b_max);
+    const float *w = theta + (int64_t)rows[i] * ld_t;
+    const int32_t *idx = batch_idx + i * b_max;
+    float *out = part + (i * split + kc) * ((int64_t)b_max * C);
+    const int k0 = kc * kchunk, k1 = k0 + kchunk < K ? k0 + kchunk : K;
+    const int lane = threadIdx.x & 63;
+    const int tc = (C + 3) / 4, n_tiles = ((len + 3) / 4) * tc;
+    for (int t = wave_id() + 4 * blockIdx.y; t < n_tiles; t += 4 * gridDim.y) {
+        const int s0 = (t / tc) * 4, c0 = (t % tc) * 4;
+        const float *xp[4], *wp[4];
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {          // the tile's tail repeats its last sample / class
+            const int s = s0 + a < len ? s0 + a : len - 1, c = c0 + a < C ? c0 + a : C - 1;
+            xp[a] = data + (int64_t)idx[s] * K;
+            wp[a] = w + (int64_t)c * K;
+        }
+        float acc[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) acc[j] = 0.f;
+        for (int k = k0 + lane * V; k < k1; k += 64 * V) {
+            float xv[4][V], wv[4][V];
+#pragma unroll
+            for (int a = 0; a < 4; ++a) { ldv<V>(xp[a] + k, xv[a]); ldv<V>(wp[a] + k, wv[a]); }
+#pragma unroll
+            for (int e = 0; e < V; ++e)
+#pragma unroll
+                for (int a = 0; a < 4; ++a)
+#pragma unroll
+                    for (int b = 0; b < 4; ++b)
+                        acc[a * 4 + b] = __builtin_fmaf(xv[a][e], wv[b][e], acc[a * 4 + b]);
+        }
+        const float tot = lin_reduce16(acc, lane);
+        const int j = ((lane & 1) << 3) | ((lane & 2) << 1) | ((lane & 4) >> 1) | ((lane & 8) >> 3);
+        const int s = s0 + (j >> 2), c = c0 + (j & 3);
+        if (lane < 16 && s < len && c < C) out[(int64_t)s * C + c] = tot;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_lin_softmax(const float *__restrict__ theta, int64_t ld_t,
+                                                     const int32_t *__restrict__ labels,
+                                                     const int32_t *__restrict__ batch_idx,
+                                                     const int32_t *__restrict__ batch_len, int b_max,
+                                                     const int32_t *__restrict__ rows, int K, int C,
+                                                     int n_kc, int split, float *part,
+                                                     float *__restrict__ loss) {
+    __shared__ float red[256];
+    const int64_t i = blockIdx.x;
+    const int len = lin_len(batch_len, i, b_max);
+    const float *bias = theta + (int64_t)rows[i] * ld_t + (int64_t)C * K;
+    const int32_t *idx = batch_idx + i * b_max;
+    const int64_t stride = (int64_t)b_max * C;
+    float *z = part + i * split * stride;
+    int G = 64;
+    while (G > 1 && (G >> 1) >= C) G >>= 1;
+    const int gl = threadIdx.x & (G - 1), g = threadIdx.x / G, ng = 256 / G;
+    const float flen = (float)len;
+    float tsum = 0.f;
+    for (int sb = 0; sb < len; sb += ng) {
+        const int s = sb + g;
+        const bool on = s < len;
+        float *zs = z + (int64_t)(on ? s : 0) * C;
+        const int y = on ? labels[idx[s]] : -1;
+        float m = -__builtin_inff();
+        if (on)
+            for (int c = gl; c < C; c += G) {
+                float a = zs[c];
+                for (int q = 1; q < n_kc; ++q) a += zs[q * stride + c];
+                a += bias[c];
+                zs[c] = a;
+                m = fmaxf(m, a);
+            }
+        for (int o = G >> 1; o; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+        float se = 0.f, zy = 0.f;
+        if (on)
+            for (int c = gl; c < C; c += G) {
+                const float a = zs[c];
+                se += expf(a - m);
+                if (c == y) zy = a;
+            }
+        for (int o = G >> 1; o; o >>= 1) { se += __shfl_xor(se, o); zy += __shfl_xor(zy, o); }
+        const float lse = m + logf(se);
+        if (on) {
+            for (int c = gl; c < C; c += G) zs[c] = (expf(zs[c] - lse) - (c == y ? 1.f : 0.f)) / flen;
+            if (gl == 0) tsum += zy - lse;
+        }
+    }
+    red[threadIdx.x] = gl == 0 ? tsum : 0.f;
+    __syncthreads();
+    for (int o = 128; o; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) loss[i] = -red[0] / flen;
+}
+
+template <int V, int WV, bool C4, bool XR>
+__global__ __launch_bounds__(256) void k_lin_dw(const float *__restrict__ data,
+                                                const int32_t *__restrict__ batch_idx,
+                                                const int32_t *__restrict__ batch_len, int b_max,
+                                                const int32_t *__restrict__ rows, int K, int C,
+                                                int n_kch, int split, const float *__restrict__ part,
+                                                float *__restrict__ grad, int64_t ld_g) {
+    extern __shared__ __attribute__((aligned(16))) float lin_dz[];     // [len, C]
+    const int64_t i = blockIdx.x / n_kch;
+    const int kch = (int)(blockIdx.x % n_kch);
+    const int len = lin_len(batch_len, i, b_max);
+    const int32_t *idx = batch_idx + i * b_max;
+    const float *src = part + i * split * ((int64_t)b_max * C);
+    const int n = len * C;
+    if constexpr (C4) {
+        for (int t = threadIdx.x * 4; t < n; t += 1024)
+            *reinterpret_cast<float4 *>(lin_dz + t) = ld4(src + t);
+    } else {
+        for (int t = threadIdx.x; t < n; t += 256) lin_dz[t] = src[t];
+    }
+    __syncthreads();
+    float *g = grad + (int64_t)rows[i] * ld_g;
+    const int k = (kch * 256 + (int)threadIdx.x) * V;
+    const int ncb = (C + kLinDC - 1) / kLinDC;
+
+    auto dz_block = [&](int s, int c0, float *d) {      // dz[s, c0 .. c0 + 16), 0 past C
+        if constexpr (C4) {
+#pragma unroll
+            for (int q = 0; q < kLinDC / 4; ++q) {
+                float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (c0 + 4 * q < C) t = *reinterpret_cast<const float4 *>(lin_dz + s * C + c0 + 4 * q);
+                d[4 * q] = t.x; d[4 * q + 1] = t.y; d[4 * q + 2] = t.z; d[4 * q + 3] = t.w;
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < kLinDC; ++j) d[j] = c0 + j < C ? lin_dz[s * C + c0 + j] : 0.f;
+        }
+    };
+
+    if (k < K) {
+        float xr[XR ? kLinXR : 1][V];
+        if constexpr (XR) {
+#pragma unroll
+            for (int s = 0; s < kLinXR; ++s)
+                ldv<V>(data + (int64_t)idx[s < len ? s : 0] * K + k, xr[s]);
+        }
+        for (int cb = blockIdx.y; cb < ncb; cb += gridDim.y) {
+            const int c0 = cb * kLinDC;
+            float acc[kLinDC][V];
+#pragma unroll
+            for (int j = 0; j < kLinDC; ++j)
+#pragma unroll
+                for (int e = 0; e < V; ++e) acc[j][e] = 0.f;
+            if constexpr (XR) {
+#pragma unroll
+                for (int s = 0; s < kLinXR; ++s) {
+                    if (s < len) {
+                        float d[kLinDC];
+                        dz_block(s, c0, d);
+#pragma unroll
+                        for (int j = 0; j < kLinDC; ++j)
+#pragma unroll
+                            for (int e = 0; e < V; ++e) acc[j][e] = __builtin_fmaf(d[j], xr[s][e], acc[j][e]);
+                    }
+                }
+            } else {
+                for (int s0 = 0; s0 < len; s0 += 8) {     // 8 gathers in flight
+                    float xv[8][V];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u)
+                        ldv<V>(data + (int64_t)idx[s0 + u < len ? s0 + u : s0] * K + k, xv[u]);
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) {
+                        if (s0 + u < len) {
+                            float d[kLinDC];
+                            dz_block(s0 + u, c0, d);
+#pragma unroll
+                            for (int j = 0; j < kLinDC; ++j)
+#pragma unroll
+                                for (int e = 0; e < V; ++e)
+                                    acc[j][e] = __builtin_fmaf(d[j], xv[u][e], acc[j][e]);
+                        }
+                    }
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < kLinDC; ++j) {
+                if (c0 + j < C) {
+                    float *o = g + (int64_t)(c0 + j) * K + k;
+                    if constexpr (WV == 4) *reinterpret_cast<float4 *>(o) = make_float4(acc[j][0], acc[j][1], acc[j][2], acc[j][3]);
+                    else {
+#pragma unroll
+                        for (int e = 0; e < V; ++e) o[e] = acc[j][e];
+                    }
+                }
+            }
+        }
+    }
+    if (kch == 0 && blockIdx.y == 0)
+        for (int c = threadIdx.x; c < C; c += 256) {
+            float a = 0.f;
+            for (int s = 0; s < len; ++s) a += lin_dz[s * C + c];
+            g[(int64_t)C * K + c] = a;
+        }
+}
+
+// ----------------------------------------------------------------------------------------------
 // Halo pack of the sharded round: out[i, :] = x[rows[i], :] (the rows a peer shard reads), so that
 // one contiguous send per peer carries them.
 template <int V>
@@ -5079,6 +5339,91 @@ int niidmix_sgd_momentum_step_rows_f32(float *p, int64_t ld_p, const float *g, i
     hipLaunchKernelGGL(kfn, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, ld_p, g, ld_g,
                        buf, ld_b, ncols, rows, n_rows, neg_lr, momentum, n_chunks);
     return check_launch("k_sgd_momentum_step_rows");
+}
+
+// K-chunks of k_lin_logits at most: enough (row, chunk) blocks to fill the device at few rows; a
+// function of n_rows alone, so that the scratch size is one of (n_rows, b_max, C).
+static int64_t lin_split(int64_t n_rows) {
+    const int64_t s = (1024 + n_rows - 1) / n_rows;
+    return s < 1 ? 1 : s > 8 ? 8 : s;
+}
+
+// slices (grid y) that bring `blocks` blocks to about 2048, at most `most`
+static unsigned lin_slices(int64_t blocks, int64_t most) {
+    int64_t s = (2048 + blocks - 1) / blocks;
+    if (s > most) s = most;
+    if (s > 64) s = 64;
+    return (unsigned)(s < 1 ? 1 : s);
+}
+
+int64_t niidmix_linear_nll_grad_rows_scratch_elems(int64_t n_rows, int64_t b_max, int64_t C) {
+    if (n_rows <= 0 || b_max <= 0 || C <= 0) return 0;
+    return n_rows * lin_split(n_rows) * b_max * C;
+}
+
+int niidmix_linear_nll_grad_rows_f32(const float *theta, int64_t ld_t, const float *data,
+                                     const int32_t *labels, const int32_t *batch_idx,
+                                     const int32_t *batch_len, int64_t b_max, const int32_t *rows,
+                                     int64_t n_rows, float *grad, int64_t ld_g, float *loss,
+                                     int64_t K, int64_t C, float *scratch, int64_t scratch_elems,
+                                     void *stream) {
+    if (n_rows < 0 || b_max < 0 || K < 0 || C < 0 || scratch_elems < 0)
+        return set_error(NIIDMIX_EINVAL, "negative size");
+    if (n_rows == 0) return NIIDMIX_OK;
+    if (!theta || !data || !labels || !batch_idx || !batch_len || !rows || !grad || !loss || !scratch)
+        return set_error(NIIDMIX_EINVAL, "null pointer");
+    if (b_max == 0 || K == 0 || C == 0) return set_error(NIIDMIX_EINVAL, "b_max, K and C must be >= 1");
+    if (C > kLinMaxC || b_max * C > kLinMaxBC)
+        return set_error(NIIDMIX_EUNSUPPORTED, "C %lld, b_max * C %lld: the kernel holds C <= %lld and "
+                         "b_max * C <= %lld", (long long)C, (long long)(b_max * C), (long long)kLinMaxC,
+                         (long long)kLinMaxBC);
+    if (K > (1 << 20)) return set_error(NIIDMIX_EUNSUPPORTED, "K %lld > 2^20", (long long)K);
+    const int64_t p = C * K + C;
+    if (int rc = check_ld(ld_t, ld_g, p, "C * K + C")) return rc;
+    const int64_t need = niidmix_linear_nll_grad_rows_scratch_elems(n_rows, b_max, C);
+    if (scratch_elems < need)
+        return set_error(NIIDMIX_EINVAL, "scratch of %lld elements, %lld needed", (long long)scratch_elems,
+                         (long long)need);
+    // `rows` lives on the device: n_rows distinct rows reach at least row n_rows - 1
+    if (int rc = check_overlap(theta, ld_t, grad, ld_g, n_rows, p, "theta and grad overlap")) return rc;
+    if (overlaps(scratch, need, theta, slab_extent(n_rows, ld_t, p)) ||
+        overlaps(scratch, need, grad, slab_extent(n_rows, ld_g, p)))
+        return set_error(NIIDMIX_EALIAS, "scratch overlaps theta or grad");
+    const int64_t split = lin_split(n_rows);
+    const int64_t kchunk = ((K + split - 1) / split + 255) / 256 * 256;
+    const int64_t n_kc = (K + kchunk - 1) / kchunk;
+    const int v1 = vec_width({K, ld_t}, {theta, data}) == 4 ? 4 : 1;
+    const int v3 = vec_width({K}, {data}) == 4 ? 4 : 1;
+    const int wv3 = v3 == 4 && vec_width({ld_g}, {grad}) == 4 ? 4 : 1;
+    const bool c4 = C % 4 == 0 && aligned16(scratch);
+    const int64_t n_kch = (K + 256 * v3 - 1) / (256 * v3);
+    if (n_rows * n_kc > 0x7fffffff || n_rows * n_kch > 0x7fffffff)
+        return set_error(NIIDMIX_EUNSUPPORTED, "n_rows %lld: too many blocks", (long long)n_rows);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int ib = (int)b_max, iK = (int)K, iC = (int)C;
+
+    auto k1 = pick<4, 1>(v1, [](auto V) { return k_lin_logits<V()>; });
+    const int64_t tiles = ((b_max + 3) / 4) * ((C + 3) / 4);
+    hipLaunchKernelGGL(k1, dim3((unsigned)(n_rows * n_kc), lin_slices(n_rows * n_kc, (tiles + 3) / 4)),
+                       dim3(256), 0, s, theta, ld_t, data, batch_idx, batch_len, ib, rows, iK, iC,
+                       (int)kchunk, (int)n_kc, (int)split, scratch);
+    if (int rc = check_launch("k_lin_logits")) return rc;
+    hipLaunchKernelGGL(k_lin_softmax, dim3((unsigned)n_rows), dim3(256), 0, s, theta, ld_t, labels,
+                       batch_idx, batch_len, ib, rows, iK, iC, (int)n_kc, (int)split, scratch, loss);
+    if (int rc = check_launch("k_lin_softmax")) return rc;
+
+    // (V, WV) of k_lin_dw: (4, 4), (4, 1) or (1, 1), as one value 10 V + WV
+    auto k3 = pick<44, 41, 11>(10 * v3 + wv3, [&](auto VW) {
+        return pick<true, false>(c4, [&](auto C4) {
+            return pick<true, false>(b_max <= kLinXR, [&](auto XR) {
+                return k_lin_dw<VW() / 10, VW() % 10, C4(), XR()>; }); }); });
+    const size_t lds = (size_t)(b_max * C) * sizeof(float);
+    if (lds > 64 * 1024)
+        if (int rc = lds_opt_in(k3, lds, "k_lin_dw")) return rc;
+    hipLaunchKernelGGL(k3, dim3((unsigned)(n_rows * n_kch), lin_slices(n_rows * n_kch, (C + kLinDC - 1) / kLinDC)),
+                       dim3(256), lds, s, data, batch_idx, batch_len, ib, rows, iK, iC, (int)n_kch,
+                       (int)split, (const float *)scratch, grad, ld_g);
+    return check_launch("k_lin_dw");
 }
 
 int niidmix_update_rows_f32(const float *x, int64_t ld_x, float *y, int64_t ld_y, int64_t n_rows,

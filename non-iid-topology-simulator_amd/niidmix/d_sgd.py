@@ -19,6 +19,8 @@ NIIDMIX_MODE environment variable):
   'fast'             clique-factored / MFMA kernels, within 1e-5 condition-aware relative
 Gradient averaging (--clique-gradient, --unbiased-gradient) also runs on the GPU, bit-identical
 (niidmix.gradient); local training, optimizer steps and sampling stay on the CPU as in the reference.
+With --device-training (params['algorithm']['device-training'], opt-in) a linear model's local
+training runs on the device too: gradient, step and mixing never leave HBM (niidmix.train).
 """
 import argparse
 import itertools
@@ -709,6 +711,9 @@ def invalidate(nodes=None):
         rr = getattr(eng, "resident", None)
         if rr is not None and (nodes is None or eng.slab.owns([n["model"] for n in nodes])):
             rr.fresh = False
+    for tr in _trainers.values():
+        if nodes is None or tr.holds(nodes):
+            tr.fresh = False
 
 
 def round_engine(nodes):
@@ -724,6 +729,37 @@ def synchronize():
     this module that reads or writes the models waits first, and so must any other reader."""
     for eng in list(_engines.values()) + list(_fused_engines.values()):
         eng.wait_all()
+
+
+# --device-training: niidmix.train.DeviceTrainer per node list (the most recent one)
+_trainers = {}
+
+
+def _trainer(nodes, topology, params):
+    from .train import DeviceTrainer
+    tr = _trainers.get(id(nodes))
+    if tr is None or not tr.owns(nodes):
+        synchronize()
+        _trainers.clear()
+        tr = DeviceTrainer(nodes, topology, params, torch.device("cuda", torch.cuda.current_device()))
+        _trainers[id(nodes)] = tr
+    return tr
+
+
+def _device_training_step(state, params, rundir):
+    """next_step under --device-training: gradient, SGD step and mixing of every node on the device
+    (niidmix.train.DeviceTrainer.round); the models are current when it returns."""
+    from . import train
+    nodes = state["nodes"]
+    synchronize()
+    tr = _trainer(nodes, state["topology"], params)
+    logging.info("  gradient + SGD step + mixing (GPU, %s, device training)", _mode(params))
+    losses, epoch_done = tr.round(nodes, state["topology"], params, _mode(params))
+    if params["topology"]["name"] == "random-graph" and params["topology"]["randomize"]:
+        params["topology"]["topology-seed"] += 1
+        state["topology"] = randomized_topology(nodes, params, rundir)
+    state["step"] += 1
+    return state, losses, epoch_done, nodes
 
 
 def _engine(nodes, topology):
@@ -833,8 +869,14 @@ def init(nodes, topology, params):
     # the reference driver's logging of the models on the GPU (niidmix.logger.install_hooks:
     # Logger.log_consensus_distance, and setup.model.average under log-global-model-accuracy)
     nl.install_hooks(params)
-    for n in nodes:
-        n["train-iterator"] = _loader(n, params)
+    if params["algorithm"].get("device-training"):
+        from . import train
+        train.check_eligible(nodes, params)               # refusals: ValueError naming the flag
+        for n in nodes:
+            n["train-iterator"] = train.index_loader(n, params)
+    else:
+        for n in nodes:
+            n["train-iterator"] = _loader(n, params)
     if params["algorithm"]["initial-averaging"]:
         center = nm.average([nodes[r]["model"] for r in range(len(nodes))])
         for r in range(len(nodes)):
@@ -909,6 +951,12 @@ def randomized_topology(nodes, params, rundir):
 
 
 def next_step(state, params, rundir):
+    if params["algorithm"].get("device-training"):
+        return _device_training_step(state, params, rundir)
+    for tr in _trainers.values():
+        if tr.mom_steps and tr.holds(state["nodes"]):
+            raise ValueError("--device-training was switched off while its momentum buffers live on "
+                             "the device: handing them to the CPU optimizers mid-run is not supported")
     sample = params["topology"]["name"] == "sample"
     active = get_sample(state, params, state["step"]) if sample else state["nodes"]
     topology = state["topology"]
@@ -1030,6 +1078,10 @@ def main(argv=None):
     ap.add_argument("--unbiased-gradient", action="store_const", const=True, default=False)
     ap.add_argument("--mixing-mode", choices=["exact", "fast"], default="exact",
                     help="exact: bit-identical to the reference loop; fast: clique/MFMA kernels")
+    ap.add_argument("--device-training", action="store_const", const=True, default=False,
+                    help="linear models only: local training (forward, loss, backward), the SGD step "
+                         "and the mixing all run on the device; same samples as the CPU path, "
+                         "gradients within 1e-5 (condition-aware) of it, not bit-identical")
     ap.add_argument("--no-deferred-writeback", dest="deferred_writeback", action="store_false",
                     help="next_step returns only once every mixed row is back in the models (by "
                          "default it returns while they stream back, whenever the driver reads no "
@@ -1052,6 +1104,7 @@ def main(argv=None):
         "batch-size": args.batch_size, "initial-averaging": args.initial_averaging,
         "clique-gradient": args.clique_gradient, "unbiased-gradient": args.unbiased_gradient,
         "mixing-mode": args.mixing_mode, "deferred-writeback": args.deferred_writeback,
+        **({"device-training": True} if args.device_training else {}),
     })
     if args.rundir is None:
         print(rundir)

@@ -21,6 +21,9 @@ Ops (registered in the `niidmix` namespace, usable as torch.ops.niidmix.*):
   sgd_momentum_step_rows(p, g, buf, rows, neg_lr, momentum, first)
                                                     k_sgd_momentum_step_rows (--learning-momentum)
   mix_csr(..., mode | MEAN)                         per-row gradient mean (unbiased / removed edges)
+  linear_nll_grad_rows(theta, data, labels, batch_idx, batch_len, rows, grad, loss, K, C)
+                                                    k_lin_logits + k_lin_softmax + k_lin_dw (local
+                                                    training of a linear model, --device-training)
 All ops launch on torch's current HIP stream of the input's device, never synchronise, and raise
 RuntimeError (TORCH_CHECK-style) on bad arguments.  They accept HIP tensors only: there is no CPU
 implementation and no fallback.
@@ -554,6 +557,48 @@ def sgd_momentum_step_rows(p: torch.Tensor, g: torch.Tensor, buf: torch.Tensor, 
         p.data_ptr(), _ld(p), g.data_ptr(), _ld(g), buf.data_ptr(), _ld(buf), p.shape[1],
         rows.data_ptr(), rows.numel(), float(neg_lr), float(momentum), int(bool(first)), _stream(p))
     _lib.check(rc, "niidmix::sgd_momentum_step_rows")
+
+
+@torch.library.custom_op("niidmix::linear_nll_grad_rows", mutates_args=("grad", "loss"))
+def linear_nll_grad_rows(theta: torch.Tensor, data: torch.Tensor, labels: torch.Tensor,
+                         batch_idx: torch.Tensor, batch_len: torch.Tensor, rows: torch.Tensor,
+                         grad: torch.Tensor, loss: torch.Tensor, K: int, C: int) -> None:
+    """Mean-NLL gradient and loss of a linear classifier on the listed rows (include/niidmix.h,
+    niidmix_linear_nll_grad_rows_f32): row r of theta is W [C, K] then b [C]; batch_idx[i] lists
+    the batch_len[i] samples of data / labels that rows[i] trains on.  The scratch buffer comes
+    from torch's caching allocator.  The index tensors' CONTENTS are not checked here
+    (niidmix.train.DeviceTrainer checks them once)."""
+    K, C = int(K), int(C)
+    _req(K >= 1 and C >= 1, "K and C must be >= 1")
+    p = C * K + C
+    _slab("theta", theta)
+    _slab("grad", grad)
+    _req(theta.shape[1] == p and grad.shape[1] == p,
+         f"theta and grad: expected C * K + C = {p} columns, got {theta.shape[1]} and {grad.shape[1]}")
+    _slab("data", data, cols=K)
+    _req(data.is_contiguous(), "data: expected a contiguous [S, K] tensor")
+    dev = theta.device
+    _req(grad.device == dev and data.device == dev, "theta, grad and data must be on the same device")
+    _vec("labels", labels, torch.int32, dev, data.shape[0])
+    _vec("rows", rows, torch.int32, dev)
+    n = rows.numel()
+    _vec("batch_len", batch_len, torch.int32, dev, n)
+    _req(batch_idx.device == dev and batch_idx.dtype == torch.int32 and batch_idx.dim() == 2
+         and batch_idx.is_contiguous() and batch_idx.shape[0] == n,
+         f"batch_idx: expected a contiguous int32 [{n}, b_max] tensor on {dev}")
+    _vec("loss", loss, torch.float32, dev, n)
+    _req(n <= theta.shape[0] and n <= grad.shape[0], "more rows listed than theta or grad has")
+    if n == 0:
+        return
+    b_max = batch_idx.shape[1]
+    _req(b_max >= 1, "batch_idx: b_max must be >= 1")
+    elems = int(_lib.lib.niidmix_linear_nll_grad_rows_scratch_elems(n, b_max, C))
+    scratch = torch.empty(elems, dtype=torch.float32, device=dev)
+    rc = _lib.lib.niidmix_linear_nll_grad_rows_f32(
+        theta.data_ptr(), _ld(theta), data.data_ptr(), labels.data_ptr(), batch_idx.data_ptr(),
+        batch_len.data_ptr(), b_max, rows.data_ptr(), n, grad.data_ptr(), _ld(grad), loss.data_ptr(),
+        K, C, scratch.data_ptr(), elems, _stream(theta))
+    _lib.check(rc, "niidmix::linear_nll_grad_rows")
 
 
 # ------------------------------------------------------------------------------------------------

@@ -1,0 +1,190 @@
+#!/usr/bin/env python
+"""Device-training probe (measurement tool): what niidmix_linear_nll_grad_rows_f32 and the
+--device-training round cost on one GPU, at the two shapes
+    ref   N 1000, K 784,  C 10,   B 125   (the reference's linear model on MNIST)
+    e2e   N 1000, K 1023, C 1024, B 16    (P = 2^20, the E2E shape of DESIGN §5)
+
+  kernel   device-event times of single launches of the gradient call, alternating with
+           niidmix_stream_copy_f32 over the parameter slab within every repetition, reported
+           against the algorithmic bytes 4 (2 N P + sum(len) K) as a share of 8 TB/s and of the
+           stream copy's rate in the same run.
+  rounds   d_sgd.next_step on the headline topology (d-cliques 1000, cliques of 100,
+           fully-connected), flag off and flag on interleaved round by round after a warm-up:
+           median, minimum and maximum of each.
+
+    python tools/device_training_probe.py kernel --shape ref [--warmup 5] [--reps 20]
+    python tools/device_training_probe.py rounds --shape ref [--warmup 2] [--rounds 10]
+    python tools/device_training_probe.py all        # every step as a child process of its own
+
+`all` runs the four steps one after the other, each in a fresh process under its own time limit,
+and stops at the first that fails.  Every step prints one JSON line.
+"""
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [REPO, os.path.join(REPO, "non-iid-topology-simulator_amd")]
+
+SHAPES = {"ref": (1000, 784, 10, 125), "e2e": (1000, 1023, 1024, 16)}
+STEP_LIMIT_S = {"kernel": 180, "rounds": 420}
+
+
+def kernel(a):
+    import torch
+    from niidmix import _lib, train
+    n, k, c, b = SHAPES[a.shape]
+    n = a.nodes or n
+    dev = torch.device("cuda:0")
+    p = c * k + c
+    ld = train.padded_ld(p)
+    gen = torch.Generator(device=dev).manual_seed(1)
+    s = n * 2 * b
+    theta = (torch.rand(n, ld, device=dev, generator=gen) - 0.5) * (2 / k ** 0.5)
+    grad = torch.zeros(n, ld, device=dev)
+    data = torch.rand(s, k, device=dev, generator=gen)
+    labels = torch.randint(0, c, (s,), device=dev, generator=gen).to(torch.int32)
+    idx = torch.stack([torch.randperm(2 * b, device=dev, generator=gen)[:b] + 2 * b * i
+                       for i in range(n)]).to(torch.int32).contiguous()
+    blen = torch.full((n,), b, dtype=torch.int32, device=dev)
+    rows = torch.arange(n, dtype=torch.int32, device=dev)
+    loss = torch.empty(n, device=dev)
+    lib = _lib.lib
+    elems = int(lib.niidmix_linear_nll_grad_rows_scratch_elems(n, b, c))
+    scratch = torch.empty(elems, device=dev)
+    strm = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    numel = n * ld - (n * ld) % 4
+
+    def grad_call():
+        return lib.niidmix_linear_nll_grad_rows_f32(
+            theta.data_ptr(), ld, data.data_ptr(), labels.data_ptr(), idx.data_ptr(), blen.data_ptr(),
+            b, rows.data_ptr(), n, grad.data_ptr(), ld, loss.data_ptr(), k, c, scratch.data_ptr(),
+            elems, strm)
+
+    def copy_call():
+        return lib.niidmix_stream_copy_f32(theta.data_ptr(), grad.data_ptr(), numel, strm)
+
+    calls = [("copy", copy_call, 8 * numel), ("grad", grad_call, 4 * (2 * n * p + n * b * k))]
+    times = {name: [] for name, _, _ in calls}
+    for rep in range(a.warmup + a.reps):
+        for name, fn, _ in calls:
+            s0, e0 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s0.record()
+            _lib.check(fn(), name)
+            e0.record()
+            e0.synchronize()
+            if rep >= a.warmup:
+                times[name].append(s0.elapsed_time(e0) * 1e-3)
+    assert bool(torch.isfinite(loss).all())
+    out = {"step": "kernel", "shape": a.shape, "n": n, "k": k, "c": c, "b": b, "warmup": a.warmup,
+           "reps": a.reps, "device": torch.cuda.get_device_name(dev), "lib_sha16": _lib.lib_sha16()}
+    for name, _, nbytes in calls:
+        t = times[name]
+        med = statistics.median(t)
+        out[name] = {"bytes": nbytes, "median_ms": med * 1e3, "min_ms": min(t) * 1e3,
+                     "max_ms": max(t) * 1e3, "gbps_median": nbytes / med / 1e9}
+    out["grad"]["share_of_8TBps"] = out["grad"]["gbps_median"] / 8000
+    out["grad"]["share_of_stream_copy"] = out["grad"]["gbps_median"] / out["copy"]["gbps_median"]
+    print(json.dumps(out))
+
+
+def rounds(a):
+    import torch
+    import torch.nn.functional as F
+    from niidmix import d_sgd
+    from niidmix.generate import dcliques
+    from niidmix.topology import mh_csr
+    n, k, c, b = SHAPES[a.shape]
+    n = a.nodes or n
+    per_node = 2 * b
+
+    class Net(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.fc = torch.nn.Linear(k, c)
+
+        def forward(self, x, params):
+            return F.log_softmax(self.fc(x.view(-1, k)), dim=1)
+
+    edges, cliques = dcliques(n, min(100, n), "fully-connected", 1337)
+    topo = {"edges": edges, "csr": mh_csr(n, edges), "weights": torch.tensor([]), "cliques": cliques}
+    g = torch.Generator().manual_seed(5)
+    x = torch.rand(per_node, k, generator=g)               # every node trains on the same samples
+    y = torch.randint(0, c, (per_node,), generator=g)
+    runs = {}
+    for flag in (False, True):
+        torch.manual_seed(7)
+        params = {"meta": {"log": "WARNING", "seed": 7}, "model": {"input-size": k},
+                  "topology": {"name": "d-cliques", "remove-clique-edges": 0},
+                  "logger": {"accuracy-logging-interval": 0, "accuracy-logging-interval-steps": 0,
+                             "log-consensus-distance": False},
+                  "algorithm": {"learning-rate": 0.01, "learning-momentum": 0.0, "batch-size": b,
+                                "initial-averaging": False, "clique-gradient": False,
+                                "unbiased-gradient": False, "deferred-writeback": True,
+                                "mixing-mode": a.mode, "device-training": flag}}
+        ts = [(x[j], int(y[j])) for j in range(per_node)]
+        nodes = []
+        for r in range(n):
+            mdl = Net()
+            nodes.append({"rank": r, "epoch": 0, "train-set": ts, "model": mdl,
+                          "optimizer": d_sgd.optimizer(mdl, params)})
+        state, _, _ = d_sgd.init(nodes, topo, params)
+        runs[flag] = [state, params, []]
+    for rnd in range(a.warmup + a.rounds):
+        for flag in (False, True):
+            state, params, times = runs[flag]
+            t0 = time.perf_counter()
+            state, losses, _, _ = d_sgd.next_step(state, params, None)
+            d_sgd.synchronize()
+            dt = time.perf_counter() - t0
+            runs[flag][0] = state
+            if rnd >= a.warmup:
+                times.append(dt)
+    out = {"step": "rounds", "shape": a.shape, "n": n, "k": k, "c": c, "b": b, "mode": a.mode,
+           "warmup": a.warmup, "rounds": a.rounds, "threads": torch.get_num_threads(),
+           "device": torch.cuda.get_device_name(0)}
+    for flag, key in ((False, "flag_off"), (True, "flag_on")):
+        t = runs[flag][2]
+        out[key] = {"median_ms": statistics.median(t) * 1e3, "min_ms": min(t) * 1e3,
+                    "max_ms": max(t) * 1e3}
+    out["on_over_off"] = out["flag_on"]["median_ms"] / out["flag_off"]["median_ms"]
+    print(json.dumps(out))
+
+
+def run_all(a):
+    for step in ("kernel", "rounds"):
+        for shape in SHAPES:
+            cmd = [sys.executable, os.path.abspath(__file__), step, "--shape", shape]
+            print("+", " ".join(cmd[1:]), flush=True)
+            rc = subprocess.run(cmd, timeout=STEP_LIMIT_S[step]).returncode
+            if rc != 0:
+                sys.exit(f"device_training_probe: {step} {shape} ended with status {rc}; stopping")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("step", choices=["kernel", "rounds", "all"])
+    ap.add_argument("--shape", choices=list(SHAPES), default="ref")
+    ap.add_argument("--nodes", type=int, default=0, help="override the shape's node count")
+    ap.add_argument("--warmup", type=int, default=None)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--rounds", type=int, default=10)
+    ap.add_argument("--mode", choices=["exact", "fast"], default="exact")
+    a = ap.parse_args()
+    if a.step == "all":
+        return run_all(a)
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit("device_training_probe: no GPU (a rate is only ever measured on one)")
+    if a.warmup is None:
+        a.warmup = 5 if a.step == "kernel" else 2
+    (kernel if a.step == "kernel" else rounds)(a)
+
+
+if __name__ == "__main__":
+    main()
