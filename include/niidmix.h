@@ -457,6 +457,62 @@ int niidmix_linear_nll_grad_rows_f32(const float *theta, int64_t ld_t, const flo
                                      int64_t K, int64_t C, float *scratch, int64_t scratch_elems,
                                      void *stream);
 
+/* Evaluation of a linear classifier on the listed rows: what the reference's logger computes per
+ * node on the CPU (model.forward + F.nll_loss(reduction='sum') + argmax over a DataLoader), for
+ * every job in one call (the drop-in's --device-evaluation; niidmix.evaluate.DeviceEvaluator).
+ * Job i evaluates slab row rows[i] on the contiguous samples data[seg_start[i] .. seg_start[i] +
+ * seg_len[i]).  rows may repeat and segments may coincide (a shared test set is every job with
+ * seg_start = 0); nothing in theta is written.
+ *   theta     [*, ld_t] parameters (device), the row layout of niidmix_linear_nll_grad_rows_f32:
+ *             W as [C, K] row-major, then b [C]; P = C * K + C columns
+ *   data      [S, K] samples (device), labels [S] int32 classes (device)
+ *   rows, seg_start, seg_len   [n_jobs] int32 (device); seg_len[i] is clamped to [0, max_len]
+ *   loss_sum  [n_jobs] double (device): sum_s nll_s; each nll_s is fp32 and they are added in
+ *             double, in sample order within a tile of 64 samples, the tiles in tile order
+ *   correct   [n_jobs] int32 (device): #{s : pred_s == y_s}
+ *   pred      NULL, or [n_jobs, ld_pred] int32 (device): pred[i * ld_pred + j] is the prediction for
+ *             job i's j-th sample; entries at or past seg_len[i] are untouched
+ *   scratch   caller-owned device buffer (8-B aligned) of at least
+ *             niidmix_linear_eval_rows_scratch_bytes(n_jobs, max_len, C) bytes (per (job, tile)
+ *             partial sums and counts); its contents are overwritten
+ * With z[s,c] = b[c] + sum_k x[s,k] W[c,k]:  pred_s is the lowest class index that attains the
+ * maximum, a NaN logit counting as the maximum and the first NaN winning (torch.argmax /
+ * torch.max(.., 1) on the CPU);  nll_s = m_s + log sum_c exp(z[s,c] - m_s) - z[s,y_s], m_s = max_c
+ * z[s,c].  A job of length 0 gets 0.0 and 0.
+ * fp32 FMAs, every logit one chain over k = 0 .. K-1; no floating-point atomics (the partial
+ * results of a (job, tile) go to scratch and a second, small launch adds them in tile order): two
+ * calls on the same inputs give the same bits, a job's outputs do not depend on which other jobs
+ * the call lists, and an inf or NaN in one row's parameters stays in the jobs that list that row.
+ * Not bit-identical to ATen's CPU result (another summation order): loss_sum within 1e-5 of the
+ * condition-aware bound sum_s 2 A_s, A_s = max_c (|b_c| + sum_k |x[s,k]| |W[c,k]|), and pred equal to
+ * the float64 argmax wherever the top two float64 logits are more than 2e-5 A_s apart
+ * (tests/test_gpu_eval.py).
+ * Limits (NIIDMIX_EUNSUPPORTED beyond): C <= 1024, K <= 2^20, at most 2^31 - 1 (job group, tile)
+ * blocks.  float4 accesses when K and ld_t are multiples of 4 and theta and data 16-B aligned,
+ * scalar ones otherwise (any K, any ld_t >= P).
+ * Checked before anything touches the GPU, in this order:
+ *   NIIDMIX_EINVAL        a null pointer other than pred
+ *   NIIDMIX_EINVAL        n_jobs, K or C < 1, max_len < 0
+ *   NIIDMIX_EUNSUPPORTED  C > 1024, K > 2^20
+ *   NIIDMIX_EINVAL        ld_t < C * K + C
+ *   NIIDMIX_EINVAL        ld_pred < max_len (pred given)
+ *   NIIDMIX_EINVAL        a scratch buffer that is too small or not 8-B aligned
+ *   NIIDMIX_EALIAS        loss_sum, correct, pred or scratch overlaps theta.  The row list is on
+ *                         the device, is not read by the launcher and may repeat, so the extent
+ *                         taken for theta is the one row every call reads, P elements from its
+ *                         base (niidmix::linear_eval_rows checks the whole slab).
+ * rows, seg_start, seg_len and labels are device data and are NOT checked by the launcher: a row
+ * or a segment outside its array reads out of bounds (a label outside [0, C) matches no class).
+ * niidmix.evaluate.DeviceEvaluator checks them once per registered set and builds the job lists
+ * itself. */
+int64_t niidmix_linear_eval_rows_scratch_bytes(int64_t n_jobs, int64_t max_len, int64_t C);
+int niidmix_linear_eval_rows_f32(const float *theta, int64_t ld_t, const float *data,
+                                 const int32_t *labels, const int32_t *rows,
+                                 const int32_t *seg_start, const int32_t *seg_len, int64_t n_jobs,
+                                 int64_t max_len, double *loss_sum, int32_t *correct, int32_t *pred,
+                                 int64_t ld_pred, int64_t K, int64_t C, void *scratch,
+                                 int64_t scratch_bytes, void *stream);
+
 /* update_models(all_models, avg) after the 'sample' topology's uniform average (d_sgd.py:240-250,
  * :29-35): every row y_i := fl(fl(x_i * 0) + avg) (p.mul_(0.); p.add_(new)) — avg everywhere
  * except NaN where x_i is non-finite and the sign rule of (+-0) + (+-0) where avg is 0.

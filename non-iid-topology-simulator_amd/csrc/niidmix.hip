@@ -4267,6 +4267,250 @@ __global__ __launch_bounds__(256) void k_lin_dw(const float *__restrict__ data,
 }
 
 // ----------------------------------------------------------------------------------------------
+// Evaluation of a linear classifier (niidmix_linear_eval_rows_f32): job i scores slab row rows[i]
+// (W [C, K] then b [C], as above) on the contiguous samples data[seg_start[i] .. + seg_len[i]):
+// summed NLL, number of correct argmax predictions and, optionally, the predictions.  Two launches:
+//   k_lin_eval      per (group of jobs, tile of 64 samples): a 64 x 64 tile of logits, rows =
+//                   samples, columns = "virtual columns" (job, class), in registers (4 x 4 per lane),
+//                   K walked once in stages of 32 through LDS (the next stage's global loads are in
+//                   flight while the current one is multiplied).  C < 64: 64 / C consecutive jobs
+//                   fill the columns when their segments coincide (a shared test set: the X tile is
+//                   staged once for all of them); jobs of a group whose segments differ run one
+//                   after the other.  C > 64: one job, column blocks of 64 classes, the softmax
+//                   state (max, argmax, sum of exponentials, z[y]) carried across the blocks.  The
+//                   epilogue (bias, softmax, argmax, loss) runs on the tile in LDS: the logits never
+//                   reach HBM.  Every logit is one lane's fma chain over k = 0 .. K-1 from 0, so a
+//                   job's bits do not depend on the jobs it shares a group or a call with.
+//   k_lin_eval_sum  per job: the tiles' partial sums (double) and counts added in tile order.
+// No atomics; scratch: [n_jobs, n_tiles] doubles, then [n_jobs, n_tiles] int32.
+constexpr int kEvTS = 64;               // samples per tile
+constexpr int kEvCB = 64;               // virtual columns per block
+constexpr int kEvKC = 32;               // k per stage
+constexpr int kEvRS = kEvKC + 4;        // row stride of the staged tiles: float4 reads of 16 rows
+                                        // 36 floats apart fall in 16 distinct bank quads
+constexpr int kEvZS = kEvCB + 1;        // row stride of the logit tile
+
+__host__ __device__ inline int ev_group(int C) { return C >= kEvCB ? 1 : kEvCB / C; }
+
+__device__ __forceinline__ int ev_len(const int32_t *__restrict__ seg_len, int64_t i, int max_len) {
+    const int l = seg_len[i];
+    return l < 0 ? 0 : l > max_len ? max_len : l;
+}
+
+struct EvState {       // softmax state of one (job, sample) over the classes seen so far
+    float best;        // running maximum: the first NaN, else the largest logit
+    int idx;           // its class: the lowest index that attains it
+    float sum;         // sum of exp(z - best)
+    float zy;          // z[y]
+};
+
+// Folds classes c0 .. c0 + n (n >= 1, logits z[0 .. n)) into st; `first`: st is empty.
+__device__ __forceinline__ void ev_scan(const float *z, int n, int c0, int y, bool first, EvState &st) {
+    float bm = z[0], zy = c0 == y ? z[0] : 0.f;
+    int bi = c0;
+    for (int j = 1; j < n; ++j) {
+        const float v = z[j];
+        if (!(bm != bm) && (v > bm || v != v)) { bm = v; bi = c0 + j; }
+        if (c0 + j == y) zy = v;
+    }
+    float bs = 0.f;
+    for (int j = 0; j < n; ++j) bs += expf(z[j] - bm);
+    const float ninf = -__builtin_inff();
+    if (first) {
+        st.best = bm; st.idx = bi; st.sum = bs; st.zy = zy;
+        return;
+    }
+    st.zy += zy;
+    const bool take = !(st.best != st.best) && (bm > st.best || bm != bm);
+    if (bm == ninf) return;                      // exp(-inf - m) = 0: nothing to add
+    if (st.best == ninf) st.sum = bs;            // all earlier terms were 0
+    else {
+        const float m = take ? bm : st.best;
+        st.sum = st.sum * expf(st.best - m) + bs * expf(bm - m);
+    }
+    if (take) { st.best = bm; st.idx = bi; }
+}
+
+// nj jobs first .. first + nj with the same segment (start st0), tile t of ns samples.
+template <int V>
+__device__ __forceinline__ void ev_run(const float *__restrict__ theta, int64_t ld_t,
+                                       const float *__restrict__ data,
+                                       const int32_t *__restrict__ labels,
+                                       const int32_t *__restrict__ rows, int64_t first, int nj, int st0,
+                                       int t, int ns, int n_tiles, int K, int C,
+                                       double *__restrict__ part_loss, int32_t *__restrict__ part_cnt,
+                                       int32_t *__restrict__ pred, int64_t ld_pred, float *xs, float *ws,
+                                       float *zb, unsigned char *okf) {
+    constexpr int NL = V == 4 ? 2 : 8;           // loads per lane and staged tile
+    const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15;
+    const int vc = nj * C;                       // virtual columns: <= 64 unless nj == 1
+    const int n_cb = (vc + kEvCB - 1) / kEvCB;
+    const int64_t s0 = (int64_t)st0 + (int64_t)t * kEvTS;
+    const float *xbase = data + s0 * K;
+    EvState st = {0.f, 0, 0.f, 0.f};             // carried across column blocks (n_cb > 1, tid < ns)
+    const int y_own = n_cb > 1 && tid < ns ? labels[s0 + tid] : -1;
+
+    for (int cb = 0; cb < n_cb; ++cb) {
+        const int ncol = vc - cb * kEvCB < kEvCB ? vc - cb * kEvCB : kEvCB;
+        // lane's staged elements: row r0 + RQ q, columns kq .. kq + V of the stage
+        constexpr int RQ = kEvTS / NL;
+        const int r0 = V == 4 ? tid >> 3 : tid >> 5, kq = V == 4 ? (tid & 7) * 4 : tid & 31;
+        const int lo = r0 * kEvRS + kq;
+        const float *xp = xbase + (int64_t)r0 * K + kq;
+        const float *wp[NL];
+#pragma unroll
+        for (int q = 0; q < NL; ++q) {
+            const int v = cb * kEvCB + (r0 + RQ * q < ncol ? r0 + RQ * q : 0);
+            wp[q] = theta + (int64_t)rows[first + v / C] * ld_t + (int64_t)(v % C) * K + kq;
+        }
+        float acc[4][4];
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) acc[a][b] = 0.f;
+        float xr[NL][V], wr[NL][V];
+        auto fetch = [&](int k0) {               // rows past the tile and k past K are staged as 0
+#pragma unroll
+            for (int q = 0; q < NL; ++q) {
+                const bool in = k0 + kq < K;
+#pragma unroll
+                for (int e = 0; e < V; ++e) { xr[q][e] = 0.f; wr[q][e] = 0.f; }
+                if (in && r0 + RQ * q < ns) ldv<V>(xp + (int64_t)(RQ * q) * K + k0, xr[q]);
+                if (in && r0 + RQ * q < ncol) ldv<V>(wp[q] + k0, wr[q]);
+            }
+        };
+        fetch(0);
+        for (int k0 = 0; k0 < K; k0 += kEvKC) {
+            __syncthreads();                     // the previous stage has been read
+#pragma unroll
+            for (int q = 0; q < NL; ++q) {
+                if constexpr (V == 4) {
+                    *reinterpret_cast<float4 *>(xs + lo + RQ * q * kEvRS) = make_float4(xr[q][0], xr[q][1], xr[q][2], xr[q][3]);
+                    *reinterpret_cast<float4 *>(ws + lo + RQ * q * kEvRS) = make_float4(wr[q][0], wr[q][1], wr[q][2], wr[q][3]);
+                } else {
+                    xs[lo + RQ * q * kEvRS] = xr[q][0];
+                    ws[lo + RQ * q * kEvRS] = wr[q][0];
+                }
+            }
+            __syncthreads();
+            if (k0 + kEvKC < K) fetch(k0 + kEvKC);
+#pragma unroll 2
+            for (int kk = 0; kk < kEvKC; kk += 4) {
+                float4 xa[4], wb[4];
+#pragma unroll
+                for (int a = 0; a < 4; ++a) xa[a] = *reinterpret_cast<const float4 *>(xs + (ty * 4 + a) * kEvRS + kk);
+#pragma unroll
+                for (int b = 0; b < 4; ++b) wb[b] = *reinterpret_cast<const float4 *>(ws + (tx + 16 * b) * kEvRS + kk);
+#pragma unroll
+                for (int a = 0; a < 4; ++a)
+#pragma unroll
+                    for (int b = 0; b < 4; ++b) {
+                        acc[a][b] = __builtin_fmaf(xa[a].x, wb[b].x, acc[a][b]);
+                        acc[a][b] = __builtin_fmaf(xa[a].y, wb[b].y, acc[a][b]);
+                        acc[a][b] = __builtin_fmaf(xa[a].z, wb[b].z, acc[a][b]);
+                        acc[a][b] = __builtin_fmaf(xa[a].w, wb[b].w, acc[a][b]);
+                    }
+            }
+        }
+        // the K loop's barriers lie between the last block's scan of zb and these stores
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const int j = tx + 16 * b;
+            if (j < ncol) {
+                const int v = cb * kEvCB + j;
+                const float bias = theta[(int64_t)rows[first + v / C] * ld_t + (int64_t)C * K + v % C];
+#pragma unroll
+                for (int a = 0; a < 4; ++a) zb[(ty * 4 + a) * kEvZS + j] = acc[a][b] + bias;
+            }
+        }
+        __syncthreads();
+        auto finish = [&](const EvState &q, int s, int jj, int y) {
+            const float nll = (q.best + logf(q.sum)) - q.zy;
+            zb[s * kEvZS + jj * C] = nll;        // the pair's own columns: nobody else reads them
+            okf[jj * kEvTS + s] = q.idx == y;
+            if (pred) pred[(first + jj) * ld_pred + (int64_t)t * kEvTS + s] = q.idx;
+        };
+        if (n_cb == 1) {                         // whole jobs in the block: a lane per (job, sample)
+            for (int p = tid; p < nj * kEvTS; p += 256) {
+                const int s = p & (kEvTS - 1), jj = p >> 6;
+                if (s < ns) {
+                    const int y = labels[s0 + s];
+                    EvState q;
+                    ev_scan(zb + s * kEvZS + jj * C, C, 0, y, true, q);
+                    finish(q, s, jj, y);
+                }
+            }
+        } else if (tid < ns) {                   // one job: lane s folds this block into its state
+            ev_scan(zb + tid * kEvZS, ncol, cb * kEvCB, y_own, cb == 0, st);
+            if (cb == n_cb - 1) finish(st, tid, 0, y_own);
+        }
+    }
+    __syncthreads();
+    if (tid < nj) {                              // the tile's partial sums, in sample order
+        double a = 0.0;
+        int c = 0;
+        for (int s = 0; s < ns; ++s) {
+            a += (double)zb[s * kEvZS + tid * C];
+            c += okf[tid * kEvTS + s];
+        }
+        part_loss[(first + tid) * n_tiles + t] = a;
+        part_cnt[(first + tid) * n_tiles + t] = c;
+    }
+    __syncthreads();                             // zb and okf are free for the group's next run
+}
+
+template <int V>
+__global__ __launch_bounds__(256) void k_lin_eval(const float *__restrict__ theta, int64_t ld_t,
+                                                  const float *__restrict__ data,
+                                                  const int32_t *__restrict__ labels,
+                                                  const int32_t *__restrict__ rows,
+                                                  const int32_t *__restrict__ seg_start,
+                                                  const int32_t *__restrict__ seg_len, int64_t n_jobs,
+                                                  int max_len, int n_tiles, int K, int C,
+                                                  double *__restrict__ part_loss,
+                                                  int32_t *__restrict__ part_cnt,
+                                                  int32_t *__restrict__ pred, int64_t ld_pred) {
+    __shared__ __attribute__((aligned(16))) float xs[kEvTS * kEvRS];
+    __shared__ __attribute__((aligned(16))) float ws[kEvCB * kEvRS];
+    __shared__ float zb[kEvTS * kEvZS];
+    __shared__ unsigned char okf[kEvTS * kEvCB];
+    const int t = (int)(blockIdx.x % (unsigned)n_tiles);
+    const int jg = ev_group(C);
+    const int64_t j0 = (int64_t)(blockIdx.x / (unsigned)n_tiles) * jg;
+    const int64_t j1 = j0 + jg < n_jobs ? j0 + jg : n_jobs;
+    for (int64_t i = j0; i < j1;) {              // runs of jobs with one segment (block-uniform)
+        const int st0 = seg_start[i], len = ev_len(seg_len, i, max_len);
+        int64_t e = i + 1;
+        while (e < j1 && seg_start[e] == st0 && ev_len(seg_len, e, max_len) == len) ++e;
+        const int left = len - t * kEvTS;
+        if (left > 0)
+            ev_run<V>(theta, ld_t, data, labels, rows, i, (int)(e - i), st0, t,
+                      left < kEvTS ? left : kEvTS, n_tiles, K, C, part_loss, part_cnt, pred, ld_pred,
+                      xs, ws, zb, okf);
+        i = e;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_lin_eval_sum(const int32_t *__restrict__ seg_len, int64_t n_jobs,
+                                                      int max_len, int n_tiles,
+                                                      const double *__restrict__ part_loss,
+                                                      const int32_t *__restrict__ part_cnt,
+                                                      double *__restrict__ loss_sum,
+                                                      int32_t *__restrict__ correct) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_jobs) return;
+    const int nt = (ev_len(seg_len, i, max_len) + kEvTS - 1) / kEvTS;
+    double a = 0.0;
+    int c = 0;
+    for (int t = 0; t < nt; ++t) {
+        a += part_loss[i * n_tiles + t];
+        c += part_cnt[i * n_tiles + t];
+    }
+    loss_sum[i] = a;
+    correct[i] = c;
+}
+
+// ----------------------------------------------------------------------------------------------
 // Halo pack of the sharded round: out[i, :] = x[rows[i], :] (the rows a peer shard reads), so that
 // one contiguous send per peer carries them.
 template <int V>
@@ -5424,6 +5668,64 @@ int niidmix_linear_nll_grad_rows_f32(const float *theta, int64_t ld_t, const flo
                        dim3(256), lds, s, data, batch_idx, batch_len, ib, rows, iK, iC, (int)n_kch,
                        (int)split, (const float *)scratch, grad, ld_g);
     return check_launch("k_lin_dw");
+}
+
+static int64_t ev_tiles(int64_t max_len) { return (max_len + kEvTS - 1) / kEvTS; }
+
+int64_t niidmix_linear_eval_rows_scratch_bytes(int64_t n_jobs, int64_t max_len, int64_t C) {
+    if (n_jobs <= 0 || max_len <= 0 || C <= 0) return 0;
+    // a double and an int32 per (job, tile), to a multiple of 16 B; C does not enter
+    return (n_jobs * ev_tiles(max_len) * 12 + 15) / 16 * 16;
+}
+
+int niidmix_linear_eval_rows_f32(const float *theta, int64_t ld_t, const float *data,
+                                 const int32_t *labels, const int32_t *rows, const int32_t *seg_start,
+                                 const int32_t *seg_len, int64_t n_jobs, int64_t max_len,
+                                 double *loss_sum, int32_t *correct, int32_t *pred, int64_t ld_pred,
+                                 int64_t K, int64_t C, void *scratch, int64_t scratch_bytes,
+                                 void *stream) {
+    if (!theta || !data || !labels || !rows || !seg_start || !seg_len || !loss_sum || !correct || !scratch)
+        return set_error(NIIDMIX_EINVAL, "null pointer");
+    if (n_jobs <= 0 || K <= 0 || C <= 0) return set_error(NIIDMIX_EINVAL, "n_jobs, K and C must be >= 1");
+    if (max_len < 0) return set_error(NIIDMIX_EINVAL, "negative max_len");
+    if (C > kLinMaxC) return set_error(NIIDMIX_EUNSUPPORTED, "C %lld > %lld", (long long)C, (long long)kLinMaxC);
+    if (K > (1 << 20)) return set_error(NIIDMIX_EUNSUPPORTED, "K %lld > 2^20", (long long)K);
+    if (max_len > 0x7fffffff) return set_error(NIIDMIX_EUNSUPPORTED, "max_len %lld: int32 segments", (long long)max_len);
+    const int64_t p = C * K + C;
+    if (int rc = check_ld(ld_t, ld_t, p, "C * K + C")) return rc;
+    if (pred && ld_pred < max_len) return set_error(NIIDMIX_EINVAL, "ld_pred < max_len");
+    const int64_t need = niidmix_linear_eval_rows_scratch_bytes(n_jobs, max_len, C);
+    if (scratch_bytes < need || (reinterpret_cast<uintptr_t>(scratch) & 7u))
+        return set_error(NIIDMIX_EINVAL, "scratch of %lld bytes (8-B aligned), %lld needed",
+                         (long long)scratch_bytes, (long long)need);
+    // `rows` lives on the device and may repeat: one row of theta is all that is known to be read
+    auto hits_theta = [&](const void *q, int64_t bytes) {
+        const char *a = reinterpret_cast<const char *>(q), *t0 = reinterpret_cast<const char *>(theta);
+        return bytes > 0 && a < t0 + p * 4 && t0 < a + bytes;
+    };
+    if (hits_theta(loss_sum, n_jobs * 8) || hits_theta(correct, n_jobs * 4) ||
+        (pred && hits_theta(pred, ((n_jobs - 1) * ld_pred + max_len) * 4)) || hits_theta(scratch, need))
+        return set_error(NIIDMIX_EALIAS, "an output or the scratch buffer overlaps theta");
+    const int64_t n_tiles = ev_tiles(max_len);
+    const int64_t jg = ev_group((int)C), n_groups = (n_jobs + jg - 1) / jg;
+    if (n_groups * n_tiles > 0x7fffffff)
+        return set_error(NIIDMIX_EUNSUPPORTED, "n_jobs %lld x max_len %lld: too many blocks",
+                         (long long)n_jobs, (long long)max_len);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    double *part_loss = reinterpret_cast<double *>(scratch);
+    int32_t *part_cnt = reinterpret_cast<int32_t *>(part_loss + n_jobs * n_tiles);
+    if (n_tiles > 0) {
+        const int v = vec_width({K, ld_t}, {theta, data}) == 4 ? 4 : 1;
+        auto k1 = pick<4, 1>(v, [](auto V) { return k_lin_eval<V()>; });
+        hipLaunchKernelGGL(k1, dim3((unsigned)(n_groups * n_tiles)), dim3(256), 0, s, theta, ld_t, data,
+                           labels, rows, seg_start, seg_len, n_jobs, (int)max_len, (int)n_tiles, (int)K,
+                           (int)C, part_loss, part_cnt, pred, ld_pred);
+        if (int rc = check_launch("k_lin_eval")) return rc;
+    }
+    hipLaunchKernelGGL(k_lin_eval_sum, dim3((unsigned)((n_jobs + 255) / 256)), dim3(256), 0, s, seg_len,
+                       n_jobs, (int)max_len, (int)n_tiles, (const double *)part_loss,
+                       (const int32_t *)part_cnt, loss_sum, correct);
+    return check_launch("k_lin_eval_sum");
 }
 
 int niidmix_update_rows_f32(const float *x, int64_t ld_x, float *y, int64_t ld_y, int64_t n_rows,

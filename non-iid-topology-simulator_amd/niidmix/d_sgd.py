@@ -21,6 +21,8 @@ Gradient averaging (--clique-gradient, --unbiased-gradient) also runs on the GPU
 (niidmix.gradient); local training, optimizer steps and sampling stay on the CPU as in the reference.
 With --device-training (params['algorithm']['device-training'], opt-in) a linear model's local
 training runs on the device too: gradient, step and mixing never leave HBM (niidmix.train).
+With --device-evaluation (params['algorithm']['device-evaluation'], opt-in) the logger's accuracy
+and loss events of linear models are computed on the device as well (niidmix.evaluate).
 """
 import argparse
 import itertools
@@ -746,6 +748,19 @@ def _trainer(nodes, topology, params):
     return tr
 
 
+def device_trainer(models):
+    """(DeviceTrainer, rows) when every one of `models` is a row of a live --device-training
+    trainer (rows: their positions in its slabs), else None.  For readers of the device parameters
+    (niidmix.evaluate); DeviceTrainer.current() says whether the device copy is current."""
+    models = list(models)
+    for tr in _trainers.values():
+        pos = {id(mdl): i for i, mdl in enumerate(tr.models)}
+        rows = [pos.get(id(mdl)) for mdl in models]
+        if rows and all(r is not None for r in rows):
+            return tr, rows
+    return None
+
+
 def _device_training_step(state, params, rundir):
     """next_step under --device-training: gradient, SGD step and mixing of every node on the device
     (niidmix.train.DeviceTrainer.round); the models are current when it returns."""
@@ -869,6 +884,9 @@ def init(nodes, topology, params):
     # the reference driver's logging of the models on the GPU (niidmix.logger.install_hooks:
     # Logger.log_consensus_distance, and setup.model.average under log-global-model-accuracy)
     nl.install_hooks(params)
+    if params["algorithm"].get("device-evaluation"):
+        from . import evaluate
+        evaluate.check_eligible(nodes, params)            # refusals: ValueError naming the flag
     if params["algorithm"].get("device-training"):
         from . import train
         train.check_eligible(nodes, params)               # refusals: ValueError naming the flag
@@ -1082,6 +1100,11 @@ def main(argv=None):
                     help="linear models only: local training (forward, loss, backward), the SGD step "
                          "and the mixing all run on the device; same samples as the CPU path, "
                          "gradients within 1e-5 (condition-aware) of it, not bit-identical")
+    ap.add_argument("--device-evaluation", action="store_const", const=True, default=False,
+                    help="linear models only: the logger's train, test, validation and full-train "
+                         "accuracy and loss of every logged node (and of the global model) are "
+                         "computed on the device (niidmix.evaluate); replaces Logger.state's ssh / "
+                         "SLURM workers; within 1e-5 (condition-aware) of the CPU loops")
     ap.add_argument("--no-deferred-writeback", dest="deferred_writeback", action="store_false",
                     help="next_step returns only once every mixed row is back in the models (by "
                          "default it returns while they stream back, whenever the driver reads no "
@@ -1105,6 +1128,7 @@ def main(argv=None):
         "clique-gradient": args.clique_gradient, "unbiased-gradient": args.unbiased_gradient,
         "mixing-mode": args.mixing_mode, "deferred-writeback": args.deferred_writeback,
         **({"device-training": True} if args.device_training else {}),
+        **({"device-evaluation": True} if args.device_evaluation else {}),
     })
     if args.rundir is None:
         print(rundir)

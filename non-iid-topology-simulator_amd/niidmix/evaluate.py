@@ -1,0 +1,297 @@
+"""Accuracy and loss of linear models on the device (`--device-evaluation`).
+
+The reference's logger evaluates every logged node with CPU DataLoader loops: its own train-set
+in Logger.log_train_accuracy (tools/simulate/logger.py:205-249), and the shared validation, test
+and full train sets in worker processes it reaches over ssh (logger.py:166-185,
+tools/simulate/run_logger.py).  For the reference's linear model (setup/model/linear.py: one
+nn.Linear(K, C), log_softmax) DeviceEvaluator computes the same numbers in one kernel call per
+set for all nodes at once (niidmix::linear_eval_rows):
+
+    parameters   a live DeviceTrainer's device slab, read in place (--device-training; no upload),
+                 else the models' parameters stacked and uploaded once per call
+    sets         materialised once as [M, K] fp32 + int32 labels in HBM (register_sets); the
+                 nodes' own train-sets are the trainer's when one is live
+    accuracy(models_or_nodes, set_name)   run_logger.model_accuracy: (correct / M, loss_sum / M)
+    train_accuracy(nodes)                 Logger.log_train_accuracy: chunks of 1000 samples,
+                                          (total correct / total samples, mean of the chunks' mean
+                                          losses)
+
+Not bit-identical to the CPU loops (another summation order; tests/test_gpu_eval.py states the
+bounds), so the path is opt-in.  A model that is not log_softmax(Linear) is refused with a
+ValueError naming the flag: there is no silent CPU fallback.
+"""
+import sys
+
+import torch
+
+from . import ops, train
+
+FLAG = "--device-evaluation"
+CHUNK = 1000          # Logger.log_train_accuracy's DataLoader batch size (logger.py:217)
+SET_NAMES = ("valid", "test", "full-train")
+
+
+def enabled(params):
+    return bool(params.get("algorithm", {}).get("device-evaluation"))
+
+
+def chunk_jobs(offsets, chunk=CHUNK):
+    """The (node, chunk) jobs of train_accuracy: offsets [n + 1] are the nodes' sample ranges in
+    one concatenated array.  Returns (node index, segment start, segment length) lists: each node's
+    range cut into consecutive chunks of `chunk` samples, the last one short."""
+    node, start, length = [], [], []
+    for i in range(len(offsets) - 1):
+        for s in range(offsets[i], offsets[i + 1], chunk):
+            node.append(i)
+            start.append(s)
+            length.append(min(chunk, offsets[i + 1] - s))
+    return node, start, length
+
+
+def fold_chunks(n_nodes, node, length, loss_sum, correct):
+    """[(accuracy, loss)] per node from its chunks' summed losses and correct counts: accuracy is
+    total correct over total samples, loss the mean over chunks of each chunk's mean loss
+    (logger.py:223-228, :243-245); (0.0, 0.0) for a node without samples."""
+    tot = [[0, 0, 0.0, 0] for _ in range(n_nodes)]      # correct, samples, sum of means, chunks
+    for i, ln, ls, c in zip(node, length, loss_sum, correct):
+        t = tot[i]
+        t[0] += int(c)
+        t[1] += int(ln)
+        t[2] += float(ls) / ln
+        t[3] += 1
+    return [(t[0] / t[1], t[2] / t[3]) if t[1] else (0.0, 0.0) for t in tot]
+
+
+def check_eligible(nodes, params):
+    """The refusals that need no GPU (d_sgd.init calls this): raises ValueError naming the flag.
+    Returns (K, C)."""
+    if not nodes:
+        raise ValueError(f"{FLAG}: no nodes")
+    return _shape([nd["model"] for nd in nodes])
+
+
+def _shape(models):
+    shape = train.linear_shape(models[0])
+    for i, mdl in enumerate(models):
+        if shape is None or train.linear_shape(mdl) != shape:
+            raise ValueError(f"{FLAG} needs models whose parameters are exactly a [C, K] weight and "
+                             f"a [C] bias, the same on every model (model {i} differs)")
+    if shape[1] > train.MAX_C:
+        raise ValueError(f"{FLAG}: C = {shape[1]} exceeds the kernel's limit (C <= {train.MAX_C})")
+    return shape
+
+
+class _Set:
+    """A sample set in HBM: data [M, K] fp32, labels [M] int32, and its first samples as the model
+    takes them (for the forward probe)."""
+
+    def __init__(self, data, labels, lo, hi, probe):
+        self.data, self.labels, self.lo, self.hi, self.probe = data, labels, lo, hi, probe
+        self.m = int(labels.shape[0])
+        self.k = int(data.shape[1]) if self.m else None
+
+
+def _materialise(source, device, what):
+    """Any dataset or DataLoader of (x, y) -> _Set on `device`."""
+    loader = source if isinstance(source, torch.utils.data.DataLoader) else \
+        torch.utils.data.DataLoader(source, batch_size=CHUNK)
+    xs, ys, probe = [], [], None
+    for x, y in loader:
+        x, y = torch.as_tensor(x), torch.as_tensor(y)
+        if probe is None:
+            probe = (x[:train.PROBE_SAMPLES].clone(), y[:train.PROBE_SAMPLES].to(torch.int64).clone())
+        xs.append(x.reshape(x.shape[0], -1).to(torch.float32))
+        ys.append(y.reshape(-1).to(torch.int64))
+    dev = torch.device(device)
+    if not xs:
+        return _Set(torch.empty((0, 1), dtype=torch.float32, device=dev),
+                    torch.empty(0, dtype=torch.int32, device=dev), 0, -1, None)
+    if len({x.shape[1] for x in xs}) != 1:
+        raise ValueError(f"{FLAG}: the samples of {what} do not flatten to one size")
+    x, y = torch.cat(xs).contiguous(), torch.cat(ys)
+    if x.shape[0] >= 2 ** 31:
+        raise ValueError(f"{FLAG}: {x.shape[0]} samples in {what} exceed int32 indices")
+    need = x.numel() * 4 + y.numel() * 4
+    free, _ = torch.cuda.mem_get_info(dev)
+    if need > 0.8 * free:              # DeviceTrainer._check_fit's rule
+        raise RuntimeError(f"{FLAG}: {need / 2**30:.1f} GiB of samples ({what}) do not fit in "
+                           f"{free / 2**30:.1f} GiB of free HBM")
+    return _Set(x.to(dev), y.to(torch.int32).to(dev), int(y.min()), int(y.max()), probe)
+
+
+class DeviceEvaluator:
+    def __init__(self, params, device=None):
+        self.params = params
+        self.device = torch.device(device) if device is not None else None
+        self.sets = {}
+        self.last_source = None          # "trainer" (device slab read in place) or "stacked"
+        self._probed = set()             # (model class, K, C) whose forward was probed
+        self._train = None               # (train-sets, _Set, offsets) of the last node list
+
+    def _dev(self):
+        if self.device is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        return self.device
+
+    # -------------------------------------------------------------------------------------------
+    def register_sets(self, valid=None, test=None, full_train=None):
+        """Datasets or DataLoaders of (x, y) for accuracy(.., "valid" / "test" / "full-train"),
+        copied to the device once."""
+        for name, src in (("valid", valid), ("test", test), ("full-train", full_train)):
+            if src is not None:
+                self.sets[name] = _materialise(src, self._dev(), f"the {name} set")
+        return self
+
+    def _set(self, name):
+        name = name.replace("_", "-")
+        if name not in SET_NAMES:
+            raise ValueError(f"{FLAG}: unknown set {name!r} (one of {', '.join(SET_NAMES)})")
+        if name not in self.sets:
+            ds = sys.modules.get("setup.dataset")
+            fn = getattr(ds, {"valid": "valid", "test": "test", "full-train": "train"}[name], None)
+            if not callable(fn):
+                raise ValueError(f"{FLAG}: no {name} set: register it "
+                                 "(niidmix.evaluate.register_sets) before the first logged step")
+            self.sets[name] = _materialise(fn(self.params), self._dev(), f"the {name} set")
+        return self.sets[name]
+
+    def _check(self, st, k, c, what):
+        if st.m and st.k != k:
+            raise ValueError(f"{FLAG}: the samples of {what} flatten to {st.k} values, the model "
+                             f"takes K = {k}")
+        if st.m and (st.lo < 0 or st.hi >= c):
+            raise ValueError(f"{FLAG}: {what} has a label outside [0, {c})")
+
+    def _probe(self, model, st, k, c):
+        key = (type(model), k, c)
+        if key in self._probed or st.probe is None:
+            return
+        try:
+            train.probe_forward(model, st.probe[0], st.probe[1], self.params, self._dev(), FLAG)
+        except ValueError:
+            raise
+        except Exception as e:         # a forward that does not take these samples at all
+            raise ValueError(f"{FLAG}: the model's forward failed on the set's samples "
+                             f"({type(e).__name__}: {e}); only log_softmax(Linear) is evaluated")
+        self._probed.add(key)
+
+    # -------------------------------------------------------------------------------------------
+    def _theta(self, models):
+        """(theta slab [*, P] on the device, row of each model)."""
+        from . import d_sgd
+        k, c = _shape(models)
+        hit = d_sgd.device_trainer(models)
+        if hit is not None:
+            tr, rows = hit
+            if self.device is None or tr.device == self.device:
+                cur = tr.current()
+                if cur is not None:
+                    self.device = tr.device
+                    self.last_source = "trainer"
+                    return cur, rows, k, c
+        d_sgd.synchronize()              # the models must hold the last round's rows
+        p = c * k + c
+        theta = torch.zeros((len(models), train.padded_ld(p)), dtype=torch.float32,
+                            device=self._dev())[:, :p]
+        theta.copy_(train._flat_params(models))
+        self.last_source = "stacked"
+        return theta, list(range(len(models))), k, c
+
+    def _run(self, theta, st, rows, start, length, k, c):
+        dev = theta.device
+        n = len(rows)
+        idx = torch.tensor([rows, start, length], dtype=torch.int32).to(dev)
+        loss = torch.empty(n, dtype=torch.float64, device=dev)
+        correct = torch.empty(n, dtype=torch.int32, device=dev)
+        ops.linear_eval_rows(theta, st.data, st.labels, idx[0], idx[1], idx[2], max(length), loss,
+                             correct, None, k, c)
+        return loss.cpu().tolist(), correct.cpu().tolist()
+
+    @staticmethod
+    def _models(items):
+        return [it["model"] if isinstance(it, dict) else it for it in items]
+
+    def accuracy(self, models_or_nodes, set_name):
+        """[(accuracy, loss)] of every model on a registered set: correct / M and loss_sum / M;
+        (0.0, 0.0) for an empty set."""
+        models = self._models(models_or_nodes)
+        if not models:
+            return []
+        theta, rows, k, c = self._theta(models)
+        st = self._set(set_name)
+        if st.m == 0:
+            return [(0.0, 0.0) for _ in models]
+        self._check(st, k, c, f"the {set_name} set")
+        self._probe(models[0], st, k, c)
+        loss, correct = self._run(theta, st, rows, [0] * len(rows), [st.m] * len(rows), k, c)
+        return [(cr / st.m, ls / st.m) for ls, cr in zip(loss, correct)]
+
+    def _train_sets(self, nodes, theta_dev):
+        """The nodes' own train-sets in one array: a live trainer's, else materialised (kept while
+        the same train-set objects are asked for)."""
+        from . import d_sgd
+        hit = d_sgd.device_trainer([nd["model"] for nd in nodes])
+        if hit is not None and hit[0].device == theta_dev:
+            tr, rows = hit
+            ts = nodes[0]["train-set"]
+            probe = None
+            if len(ts):
+                items = [ts[j] for j in range(min(train.PROBE_SAMPLES, len(ts)))]
+                probe = (torch.stack([torch.as_tensor(s[0]) for s in items]),
+                         torch.as_tensor([int(s[1]) for s in items], dtype=torch.int64))
+            st = _Set(tr.data, tr.labels, 0, tr.c - 1, probe)
+            return st, [(tr.offsets[r], tr.offsets[r + 1]) for r in rows]
+        sets = [nd["train-set"] for nd in nodes]
+        if self._train is None or len(self._train[0]) != len(sets) or \
+                any(a is not b for a, b in zip(self._train[0], sets)):
+            offsets = [0]
+            for ts in sets:
+                offsets.append(offsets[-1] + len(ts))
+            st = _materialise(torch.utils.data.ConcatDataset(sets), theta_dev, "the nodes' train-sets")
+            self._train = (sets, st, offsets)
+        _, st, offsets = self._train
+        return st, [(offsets[i], offsets[i + 1]) for i in range(len(sets))]
+
+    def train_accuracy(self, nodes):
+        """[(accuracy, loss)] of every node on its own train-set, as Logger.log_train_accuracy:
+        one job per (node, chunk of 1000 samples), all nodes in one call."""
+        nodes = list(nodes)
+        if not nodes:
+            return []
+        theta, rows, k, c = self._theta([nd["model"] for nd in nodes])
+        st, ranges = self._train_sets(nodes, theta.device)
+        self._check(st, k, c, "the nodes' train-sets")
+        node, start, length = [], [], []
+        for i, (a, b) in enumerate(ranges):
+            nd, s, ln = chunk_jobs([a, b])
+            node += [i] * len(nd)
+            start += s
+            length += ln
+        if not node:
+            return [(0.0, 0.0) for _ in nodes]
+        self._probe(nodes[0]["model"], st, k, c)
+        loss, correct = self._run(theta, st, [rows[i] for i in node], start, length, k, c)
+        return fold_chunks(len(nodes), node, length, loss, correct)
+
+
+# the evaluator the logger hook uses (niidmix.logger.device_state), one per params object
+_default = None
+
+
+def default(params):
+    global _default
+    if _default is None or _default.params is not params:
+        sets = _default.sets if _default is not None else {}
+        _default = DeviceEvaluator(params)
+        _default.sets = sets             # sets registered before the run's params were known
+    return _default
+
+
+def register_sets(valid=None, test=None, full_train=None, params=None):
+    """Register the shared sets with the hook's evaluator (call it before the first logged step)."""
+    global _default
+    if _default is None:
+        _default = DeviceEvaluator(params if params is not None else {})
+    elif params is not None:
+        default(params)
+    return _default.register_sets(valid=valid, test=test, full_train=full_train)

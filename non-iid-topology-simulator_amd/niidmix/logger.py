@@ -18,6 +18,10 @@ that are not slab-backed are stacked (niidmix.model).
                                  log_consensus_distance (when simulate.logger is imported) and,
                                  with log-global-model-accuracy, setup.model.average through here.
                                  Opt out: NIIDMIX_GPU_LOGGER=0 or params.algorithm.gpu-logger false
+                                 With --device-evaluation also Logger.state -> device_state: the
+                                 accuracy events computed on the device (niidmix.evaluate), no
+                                 ssh / SLURM workers.
+  state_events(evaluator, logger, nodes, state)   what that Logger.state writes, as a list
   consensus_distance_event(state)   the event dict, reference schema (doc/experiment.md)
   log_consensus_distance(logger, state)
   average(models, weights=None)  setup.model.average (tools/setup/model/__init__.py:15-25),
@@ -209,25 +213,96 @@ def _enabled(params):
     return params.get("algorithm", {}).get("gpu-logger", True) is not False
 
 
+def _accuracy_event(data, acc, loss, step, epoch, rank=None, running_loss=None):
+    """An "accuracy" event with the reference's keys in the reference's order (doc/experiment.md):
+    node events carry "rank", "train" node events "running_loss" too."""
+    ev = {"type": "accuracy", "data": data}
+    if rank is not None:
+        ev["rank"] = rank
+    ev.update(epoch=epoch, step=step, loss=loss)
+    if running_loss is not None:
+        ev["running_loss"] = running_loss
+    ev.update(accuracy=acc, timestamp=time.strftime("%Y-%m-%d-%H:%M:%S-%Z"))
+    return ev
+
+
+def state_events(evaluator, logger, nodes, state):
+    """What Logger.state(nodes, state) logs, as [(event file, event)] in the order written, from
+    `evaluator` (niidmix.evaluate.DeviceEvaluator: accuracy / train_accuracy):
+      * unless skip-training: a "train" event per node on its own train-set, with the running-loss
+        bookkeeping of Logger.log_train_accuracy (the mean of the losses Logger.loss collected
+        since the last event; the sum is reset only when there were any, the count always);
+      * with log-global-model-accuracy: "train" (the full train set), "test" and "valid" events of
+        the average of the logged nodes' models (niidmix.logger.average), all nodes being in the
+        same epoch, in events/global.jsonlines;
+      * per node "test", "valid" and "full-train" events unless skip-testing, skip-validation,
+        skip-full-training."""
+    lp = logger.params["logger"]
+    step = state["step"]
+    out = []
+    if not lp.get("skip-training"):
+        for node, (acc, loss) in zip(nodes, evaluator.train_accuracy(nodes)):
+            rank = node["rank"]
+            if logger.running_loss_count[rank] > 0:
+                running = logger.running_loss[rank] / logger.running_loss_count[rank]
+                logger.running_loss[rank] = 0.0
+            else:
+                running = 0.0
+            out.append((node["event-file"],
+                        _accuracy_event("train", acc, loss, step, node["epoch"], rank, running)))
+            logger.running_loss_count[rank] = 0
+    if lp.get("log-global-model-accuracy"):
+        epoch = nodes[0]["epoch"]
+        assert all(n["epoch"] == epoch for n in nodes), "Inconsistent epochs between nodes"
+        center = average([n["model"] for n in nodes])
+        for data, name in (("train", "full-train"), ("test", "test"), ("valid", "valid")):
+            acc, loss = evaluator.accuracy([center], name)[0]
+            out.append((logger.global_events, _accuracy_event(data, acc, loss, step, epoch)))
+    sets = [name for name, skip in (("test", "skip-testing"), ("valid", "skip-validation"),
+                                    ("full-train", "skip-full-training")) if not lp.get(skip)]
+    per_set = [(name, evaluator.accuracy(nodes, name)) for name in sets]
+    for i, node in enumerate(nodes):
+        path = os.path.join(logger.rundir, "events", "{}.jsonlines".format(node["rank"]))
+        for name, res in per_set:
+            out.append((path, _accuracy_event(name, res[i][0], res[i][1], step, node["epoch"],
+                                              node["rank"])))
+    return out
+
+
+def device_state(logger, nodes, state):
+    """Logger.state(self, nodes, state) under --device-evaluation: the same events in the same
+    files, computed on the device; no ssh, no pickled models, no temporary files."""
+    if not nodes:
+        return
+    from . import evaluate
+    for path, ev in state_events(evaluate.default(logger.params), logger, nodes, state):
+        with open(path, "a") as events:
+            events.write(json.dumps(ev) + "\n")
+
+
 def install_hooks(params):
     """Called by niidmix.d_sgd.init.  When the reference driver's modules are loaded (run.py imports
     simulate.logger and setup.model before it imports the plugin), route
-      Logger.log_consensus_distance            -> log_consensus_distance (always), and
-      setup.model.average (Logger.state, :112) -> average (with log-global-model-accuracy).
+      Logger.log_consensus_distance            -> log_consensus_distance (always),
+      setup.model.average (Logger.state, :112) -> average (with log-global-model-accuracy), and
+      Logger.state                             -> device_state (with --device-evaluation).
     Returns the names patched.  Idempotent."""
-    if not _enabled(params):
-        return []
     done = []
     lg = sys.modules.get("simulate.logger")
     cls = getattr(lg, "Logger", None) if lg is not None else None
-    if isinstance(cls, type):
-        if cls.log_consensus_distance is not log_consensus_distance:
-            install(cls)
-        done.append("simulate.logger.Logger.log_consensus_distance")
-    sm = sys.modules.get("setup.model")
-    if params.get("logger", {}).get("log-global-model-accuracy") and sm is not None and \
-            callable(getattr(sm, "average", None)):
-        if sm.average is not average:
-            sm.average = average
-        done.append("setup.model.average")
+    if _enabled(params):
+        if isinstance(cls, type):
+            if cls.log_consensus_distance is not log_consensus_distance:
+                install(cls)
+            done.append("simulate.logger.Logger.log_consensus_distance")
+        sm = sys.modules.get("setup.model")
+        if params.get("logger", {}).get("log-global-model-accuracy") and sm is not None and \
+                callable(getattr(sm, "average", None)):
+            if sm.average is not average:
+                sm.average = average
+            done.append("setup.model.average")
+    if params.get("algorithm", {}).get("device-evaluation") and isinstance(cls, type):
+        if getattr(cls, "state", None) is not device_state:
+            cls.state = device_state
+        done.append("simulate.logger.Logger.state")
     return done

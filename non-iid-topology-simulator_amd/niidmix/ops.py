@@ -24,6 +24,10 @@ Ops (registered in the `niidmix` namespace, usable as torch.ops.niidmix.*):
   linear_nll_grad_rows(theta, data, labels, batch_idx, batch_len, rows, grad, loss, K, C)
                                                     k_lin_logits + k_lin_softmax + k_lin_dw (local
                                                     training of a linear model, --device-training)
+  linear_eval_rows(theta, data, labels, rows, seg_start, seg_len, max_len, loss_sum, correct, pred,
+                   K, C)                            k_lin_eval + k_lin_eval_sum (summed loss, correct
+                                                    count and predictions of a linear model per
+                                                    (row, sample segment), --device-evaluation)
 All ops launch on torch's current HIP stream of the input's device, never synchronise, and raise
 RuntimeError (TORCH_CHECK-style) on bad arguments.  They accept HIP tensors only: there is no CPU
 implementation and no fallback.
@@ -599,6 +603,67 @@ def linear_nll_grad_rows(theta: torch.Tensor, data: torch.Tensor, labels: torch.
         batch_len.data_ptr(), b_max, rows.data_ptr(), n, grad.data_ptr(), _ld(grad), loss.data_ptr(),
         K, C, scratch.data_ptr(), elems, _stream(theta))
     _lib.check(rc, "niidmix::linear_nll_grad_rows")
+
+
+def _hits(a, b):
+    """Tensors a and b share a byte (extents from their own strides)."""
+    if a.numel() == 0 or b.numel() == 0 or \
+            a.untyped_storage().data_ptr() != b.untyped_storage().data_ptr():
+        return False
+
+    def ext(t):
+        return t.data_ptr(), t.data_ptr() + \
+            (sum((n - 1) * s for n, s in zip(t.shape, t.stride())) + 1) * t.element_size()
+    (a0, a1), (b0, b1) = ext(a), ext(b)
+    return a0 < b1 and b0 < a1
+
+
+@torch.library.custom_op("niidmix::linear_eval_rows", mutates_args=("loss_sum", "correct", "pred"))
+def linear_eval_rows(theta: torch.Tensor, data: torch.Tensor, labels: torch.Tensor,
+                     rows: torch.Tensor, seg_start: torch.Tensor, seg_len: torch.Tensor,
+                     max_len: int, loss_sum: torch.Tensor, correct: torch.Tensor,
+                     pred: Optional[torch.Tensor], K: int, C: int) -> None:
+    """Summed NLL, correct count and (optionally) predictions of a linear classifier, one job per
+    (slab row, contiguous sample segment) (include/niidmix.h, niidmix_linear_eval_rows_f32): job i
+    scores row rows[i] of theta (W [C, K] then b [C]) on data[seg_start[i] .. + seg_len[i]), lengths
+    clamped to max_len.  loss_sum is float64, correct int32, pred None or int32 [n_jobs, >= max_len].
+    The scratch buffer comes from torch's caching allocator.  The index tensors' CONTENTS are not
+    checked here (niidmix.evaluate.DeviceEvaluator builds and checks them)."""
+    K, C, max_len = int(K), int(C), int(max_len)
+    _req(K >= 1 and C >= 1, "K and C must be >= 1")
+    _req(max_len >= 0, "max_len must be >= 0")
+    p = C * K + C
+    _slab("theta", theta)
+    _req(theta.shape[1] == p, f"theta: expected C * K + C = {p} columns, got {theta.shape[1]}")
+    _slab("data", data, cols=K)
+    _req(data.is_contiguous(), "data: expected a contiguous [S, K] tensor")
+    dev = theta.device
+    _req(data.device == dev, "theta and data must be on the same device")
+    _vec("labels", labels, torch.int32, dev, data.shape[0])
+    _vec("rows", rows, torch.int32, dev)
+    n = rows.numel()
+    _req(n >= 1, "rows: at least one job")
+    _vec("seg_start", seg_start, torch.int32, dev, n)
+    _vec("seg_len", seg_len, torch.int32, dev, n)
+    _vec("loss_sum", loss_sum, torch.float64, dev, n)
+    _vec("correct", correct, torch.int32, dev, n)
+    outs = [loss_sum, correct]
+    if pred is not None:
+        _req(pred.device == dev and pred.dtype == torch.int32 and pred.dim() == 2
+             and pred.shape[0] == n and pred.shape[1] >= max_len
+             and (pred.stride(1) == 1 or pred.shape[1] <= 1),
+             f"pred: expected an int32 [{n}, >= {max_len}] tensor on {dev} with contiguous rows")
+        outs.append(pred)
+    for o in outs:
+        _req(not _hits(o, theta), "an output overlaps theta")
+    nbytes = max(16, int(_lib.lib.niidmix_linear_eval_rows_scratch_bytes(n, max_len, C)))
+    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    rc = _lib.lib.niidmix_linear_eval_rows_f32(
+        theta.data_ptr(), _ld(theta), data.data_ptr(), labels.data_ptr(), rows.data_ptr(),
+        seg_start.data_ptr(), seg_len.data_ptr(), n, max_len, loss_sum.data_ptr(), correct.data_ptr(),
+        pred.data_ptr() if pred is not None else None, _ld(pred) if pred is not None else 0,
+        K, C, scratch.data_ptr(), nbytes, _stream(theta))
+    _lib.check(rc, "niidmix::linear_eval_rows")
 
 
 # ------------------------------------------------------------------------------------------------

@@ -139,6 +139,43 @@ def fp64_reference(w, b, x, y):
     return loss, g, a
 
 
+def probe_forward(model, x, y, params, device, flag, whose="the"):
+    """`forward` cannot be inspected: require that model.forward + nll_loss + backward on the CPU
+    agree with the gradient kernel on the samples x (as the model takes them) with labels y, under
+    the tests' tolerance (both are within 1e-5 A of the float64 result, hence within 2e-5 A of each
+    other).  Shared by DeviceTrainer and niidmix.evaluate.DeviceEvaluator; raises ValueError naming
+    `flag`."""
+    k, c = linear_shape(model)
+    p, nb = c * k + c, int(x.shape[0])
+    mdl = copy.deepcopy(model)
+    for q in mdl.parameters():
+        q.grad = None
+    loss = F.nll_loss(mdl.forward(x, params), y)
+    loss.backward()
+    g_cpu = torch.cat([q.grad.reshape(-1) for q in mdl.parameters()])
+    dev = torch.device(device)
+    theta = torch.zeros((1, padded_ld(p)), dtype=torch.float32, device=dev)[:, :p]
+    theta.copy_(_flat_params([mdl]))
+    grad = torch.zeros((1, padded_ld(p)), dtype=torch.float32, device=dev)[:, :p]
+    out = torch.empty(1, dtype=torch.float32, device=dev)
+    bi = torch.arange(nb, dtype=torch.int32, device=dev).reshape(1, nb)
+    bl = torch.tensor([nb], dtype=torch.int32, device=dev)
+    xf = x.reshape(nb, -1).to(torch.float32)
+    ops.linear_nll_grad_rows(theta, xf.contiguous().to(dev), y.to(torch.int32).to(dev), bi, bl,
+                             torch.zeros(1, dtype=torch.int32, device=dev), grad, out, k, c)
+    w, b = [q.detach() for q in mdl.parameters()]
+    l64, _, a = fp64_reference(w, b, xf, y)
+    dg = (grad[0].cpu().double() - g_cpu.double()).abs()
+    loss = loss.detach()
+    dl = abs(float(out[0]) - float(loss))
+    if not bool((dg <= 2e-5 * a).all()) or not dl <= 2e-5 * max(abs(float(l64)), 1.0):
+        raise ValueError(
+            f"{flag}: the model's forward is not log_softmax(Linear(x.view(-1, K))): on {whose} "
+            f"first {nb} samples the kernel's loss {float(out[0]):.6g} / gradient differ from "
+            f"forward + nll_loss + backward on the CPU (loss {float(loss):.6g}, worst gradient "
+            f"ratio {float((dg / a.clamp_min(1e-300)).max()):.3g} of the bound)")
+
+
 class DeviceTrainer:
     """Data, parameters, gradients (and momentum) of one node list in HBM, and the round above."""
 
@@ -216,40 +253,13 @@ class DeviceTrainer:
                                f"{free / 2**30:.1f} GiB of free HBM")
 
     def _probe(self, nodes, params):
-        """`forward` cannot be inspected: require that model.forward + nll_loss + backward on the CPU
-        agree with the kernel on node 0's first samples, under the tests' tolerance (both are
-        within 1e-5 A of the float64 result, hence within 2e-5 A of each other)."""
+        """probe_forward on node 0's first samples."""
         ts = nodes[0]["train-set"]
         nb = min(PROBE_SAMPLES, len(ts), self.b_max)
         items = [ts[j] for j in range(nb)]
         x = torch.stack([torch.as_tensor(s[0]) for s in items])
         y = torch.as_tensor([int(s[1]) for s in items], dtype=torch.int64)
-        mdl = copy.deepcopy(self.models[0])
-        for q in mdl.parameters():
-            q.grad = None
-        loss = F.nll_loss(mdl.forward(x, params), y)
-        loss.backward()
-        g_cpu = torch.cat([q.grad.reshape(-1) for q in mdl.parameters()])
-        dev = self.device
-        theta = torch.zeros((1, self.ld), dtype=torch.float32, device=dev)[:, :self.p]
-        theta.copy_(_flat_params([mdl]))
-        grad = torch.zeros((1, self.ld), dtype=torch.float32, device=dev)[:, :self.p]
-        out = torch.empty(1, dtype=torch.float32, device=dev)
-        bi = torch.arange(nb, dtype=torch.int32, device=dev).reshape(1, nb)
-        bl = torch.tensor([nb], dtype=torch.int32, device=dev)
-        ops.linear_nll_grad_rows(theta, self.data, self.labels, bi, bl, self.rows[:1], grad, out,
-                                 self.k, self.c)
-        w, b = [q.detach() for q in mdl.parameters()]
-        l64, _, a = fp64_reference(w, b, x.reshape(nb, -1).float(), y)
-        dg = (grad[0].cpu().double() - g_cpu.double()).abs()
-        loss = loss.detach()
-        dl = abs(float(out[0]) - float(loss))
-        if not bool((dg <= 2e-5 * a).all()) or not dl <= 2e-5 * max(abs(float(l64)), 1.0):
-            raise ValueError(
-                f"{FLAG}: the model's forward is not log_softmax(Linear(x.view(-1, K))): on node 0's "
-                f"first {nb} samples the kernel's loss {float(out[0]):.6g} / gradient differ from "
-                f"forward + nll_loss + backward on the CPU (loss {float(loss):.6g}, worst gradient "
-                f"ratio {float((dg / a.clamp_min(1e-300)).max()):.3g} of the bound)")
+        probe_forward(self.models[0], x, y, params, self.device, FLAG, "node 0's")
 
     # -------------------------------------------------------------------------------------------
     def owns(self, nodes):
@@ -283,6 +293,15 @@ class DeviceTrainer:
         self.param_uploads += 1
         self.fresh = True
         self.version = self.slab.version()
+
+    def current(self):
+        """The device parameters [N, P] when they are the models' current values (the test round()
+        makes before it decides to upload), else None.  Readers such as
+        niidmix.evaluate.DeviceEvaluator use them in place: no upload."""
+        if not self.fresh or self.slab is None or not self.slab.owns(self.models) or \
+                self.version != self.slab.version():
+            return None
+        return self.theta[self.cur]
 
     def write_back(self):
         self._host().copy_(self.theta[self.cur])     # D2H, synchronous: the models are current
