@@ -513,6 +513,71 @@ int niidmix_linear_eval_rows_f32(const float *theta, int64_t ld_t, const float *
                                  int64_t ld_pred, int64_t K, int64_t C, void *scratch,
                                  int64_t scratch_bytes, void *stream);
 
+/* Evaluation of GN-LeNet on the listed rows: the job model, the outputs and the contracts of
+ * niidmix_linear_eval_rows_f32 for the reference's second model (setup/model/gn_lenet.py).  Job i
+ * evaluates slab row rows[i] on the contiguous samples data[seg_start[i] .. seg_start[i] +
+ * seg_len[i]); rows may repeat and segments may coincide; nothing in theta is written.
+ *   theta     [*, ld_t] parameters (device); a row holds model.parameters() in registration order:
+ *               conv1.w [32,Cin,5,5], conv1.b [32], gn1.w [32], gn1.b [32],
+ *               conv2.w [32,32,5,5],  conv2.b [32], gn2.w [32], gn2.b [32],
+ *               conv3.w [64,32,5,5],  conv3.b [64], gn3.w [64], gn3.b [64],
+ *               fc.w [C,F], fc.b [C]
+ *             with F = 64 h3 w3, h_{i+1} = floor((h_i - 3) / 2) + 1 three times from H (w from W);
+ *             P = 800 Cin + 77184 + C F + C columns (80554 at Cin 1, 28 x 28 or 24 x 24, C 10;
+ *             85354 at Cin 3, 32 x 32, C 10)
+ *   data      [S, Cin * H * W] samples, each [Cin, H, W] row-major (device), labels [S] int32
+ *   rows, seg_start, seg_len   [n_jobs] int32 (device); seg_len[i] is clamped to [0, max_len]
+ *   loss_sum  [n_jobs] double (device): sum_s nll_s; each nll_s is fp32 and they are added in
+ *             double, in sample order within a tile of 2 samples, the tiles in tile order
+ *   correct   [n_jobs] int32 (device): #{s : pred_s == y_s}
+ *   pred      NULL, or [n_jobs, ld_pred] int32 (device); entries at or past seg_len[i] untouched
+ *   logits    NULL, or [n_jobs, ld_logits, C] fp32 (device): the classifier's output z (before
+ *             log_softmax) of job i's j-th sample at (i * ld_logits + j) * C; entries at or past
+ *             seg_len[i] untouched
+ *   scratch   caller-owned device buffer (8-B aligned) of at least
+ *             niidmix_gnlenet_eval_rows_scratch_bytes(n_jobs, max_len, Cin, H, W, C) bytes: per
+ *             (job, tile) partial sums and counts and, when a tile's activations do not fit in LDS
+ *             (H or W above 34 or so), activation slots for at most 4096 resident workgroups, so
+ *             the size is bounded by a term proportional to the call's jobs plus a constant
+ * The forward pass is the reference's:
+ *   conv(5 x 5, stride 1, zero padding 2) -> maxpool(3, stride 2, floor) -> GroupNorm -> ReLU
+ *   conv -> GroupNorm -> maxpool -> ReLU;  conv -> GroupNorm -> maxpool -> ReLU
+ *   flatten in (channel, row, column) order -> linear
+ * with 32 / 32 / 64 channels and GroupNorm(2 groups, eps 1e-5, biased variance, affine).  The
+ * group statistics take two passes, the mean and then the centred squares, both fp32.  pred_s and
+ * nll_s = lse(z_s) - z[s, y_s] follow niidmix_linear_eval_rows_f32's rule: the lowest index that
+ * attains the maximum, a NaN counting as the maximum, the first NaN winning.  A job of length 0
+ * gets 0.0 and 0.
+ * fp32 FMAs only, every value a chain or a fixed tree of one workgroup; no floating-point atomics:
+ * two calls on the same inputs give the same bits; a job's outputs depend neither on which other
+ * jobs the call lists nor on how the caller splits the job list over calls; theta is not written;
+ * an inf or NaN in one row's parameters stays in the jobs that list that row.  Not bit-identical to
+ * ATen's CPU result (another summation order): the logits are within 4 e32 of the float64 forward,
+ * e32 being the error of torch's own fp32 forward on the CPU (tests/test_gpu_eval_gnlenet.py).
+ * Limits (NIIDMIX_EUNSUPPORTED beyond): C <= 1024, Cin <= 4, 15 <= H, W <= 64 (below 15 the third
+ * pool has no output).  Any ld_t >= P, any alignment of theta and data.
+ * Checked before anything touches the GPU, in this order:
+ *   NIIDMIX_EINVAL        a null pointer other than pred and logits
+ *   NIIDMIX_EINVAL        n_jobs, Cin, H, W or C < 1, max_len < 0
+ *   NIIDMIX_EUNSUPPORTED  C > 1024, Cin > 4, H or W outside [15, 64]
+ *   NIIDMIX_EINVAL        ld_t < P
+ *   NIIDMIX_EINVAL        ld_pred < max_len (pred given), ld_logits < max_len (logits given)
+ *   NIIDMIX_EINVAL        a scratch buffer that is too small or not 8-B aligned
+ *   NIIDMIX_EALIAS        loss_sum, correct, pred, logits or scratch overlaps theta (one row of
+ *                         theta, P elements from its base, as for niidmix_linear_eval_rows_f32)
+ * rows, seg_start, seg_len and labels are device data and are NOT checked by the launcher: a row
+ * or a segment outside its array reads out of bounds (a label outside [0, C) matches no class).
+ * niidmix.evaluate.DeviceEvaluator checks them and builds the job lists itself. */
+int64_t niidmix_gnlenet_eval_rows_scratch_bytes(int64_t n_jobs, int64_t max_len, int64_t Cin,
+                                                int64_t H, int64_t W, int64_t C);
+int niidmix_gnlenet_eval_rows_f32(const float *theta, int64_t ld_t, const float *data,
+                                  const int32_t *labels, const int32_t *rows,
+                                  const int32_t *seg_start, const int32_t *seg_len, int64_t n_jobs,
+                                  int64_t max_len, double *loss_sum, int32_t *correct, int32_t *pred,
+                                  int64_t ld_pred, float *logits, int64_t ld_logits, int64_t Cin,
+                                  int64_t H, int64_t W, int64_t C, void *scratch,
+                                  int64_t scratch_bytes, void *stream);
+
 /* update_models(all_models, avg) after the 'sample' topology's uniform average (d_sgd.py:240-250,
  * :29-35): every row y_i := fl(fl(x_i * 0) + avg) (p.mul_(0.); p.add_(new)) — avg everywhere
  * except NaN where x_i is non-finite and the sign rule of (+-0) + (+-0) where avg is 0.

@@ -4491,6 +4491,7 @@ __global__ __launch_bounds__(256) void k_lin_eval(const float *__restrict__ thet
     }
 }
 
+template <int TS>      // samples per tile: kEvTS (k_lin_eval) or kGnTS (k_gnl_eval)
 __global__ __launch_bounds__(256) void k_lin_eval_sum(const int32_t *__restrict__ seg_len, int64_t n_jobs,
                                                       int max_len, int n_tiles,
                                                       const double *__restrict__ part_loss,
@@ -4499,7 +4500,7 @@ __global__ __launch_bounds__(256) void k_lin_eval_sum(const int32_t *__restrict_
                                                       int32_t *__restrict__ correct) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n_jobs) return;
-    const int nt = (ev_len(seg_len, i, max_len) + kEvTS - 1) / kEvTS;
+    const int nt = (ev_len(seg_len, i, max_len) + TS - 1) / TS;
     double a = 0.0;
     int c = 0;
     for (int t = 0; t < nt; ++t) {
@@ -4508,6 +4509,393 @@ __global__ __launch_bounds__(256) void k_lin_eval_sum(const int32_t *__restrict_
     }
     loss_sum[i] = a;
     correct[i] = c;
+}
+
+// ----------------------------------------------------------------------------------------------
+// Evaluation of GN-LeNet (niidmix_gnlenet_eval_rows_f32; the reference's setup/model/gn_lenet.py):
+//   conv1(Cin -> 32, 5 x 5, pad 2) -> maxpool(3, 2) -> GroupNorm(2) -> ReLU
+//   conv2(32 -> 32) -> GroupNorm(2) -> maxpool(3, 2) -> ReLU
+//   conv3(32 -> 64) -> GroupNorm(2) -> maxpool(3, 2) -> ReLU -> flatten -> linear(F -> C)
+// k_gnl_eval: one workgroup per (job, tile of kGnTS samples) walks the whole network; a sample is
+// never split over workgroups (the group statistics need its whole map).  Two activation buffers
+// of kGnTS * 32 h1 w1 floats (the pooled conv1 map, the largest one kept) ping-pong through the
+// layers: in LDS when they fit (up to 34 x 34 inputs), else in a slot of the scratch buffer owned
+// by the workgroup (a persistent grid of at most kGnMaxSlots workgroups).
+//   conv1     a lane per (sample, 8 output channels, pooled position): the 3 x 3 conv outputs
+//             under the pool window from a 7 x 7 input patch in registers, pooled while written (the
+//             full-resolution map, 98 KiB per MNIST sample, never exists).
+//   conv2/3   implicit GEMM, K = 800: a lane per (sample, 8 output channels, row, 4 columns), 32
+//             accumulators; the weights pass through LDS in stages of 6400 floats as [k][channel]
+//             (float4 broadcast reads), the next stage's global loads in flight while the current
+//             one is multiplied.  A job's 322 KB of weights are re-read by its tiles from L2.
+//   GroupNorm a wave per (sample, group): the mean, then the centred squares, both fp32, lanes
+//             striding the group's contiguous map, a fixed xor butterfly across the wave.
+//   linear    a wave per class, lanes striding F, the same butterfly; softmax, argmax and loss as
+//             k_lin_eval (ev_scan); partial sums per (job, tile), added by k_lin_eval_sum.
+// Every value is a fixed-order chain of one workgroup: a job's bits depend on nothing but its row,
+// its samples and the tile's position in the job.
+constexpr int kGnTS = 2;                // samples per tile
+constexpr int kGnOT = 8;                // output channels per lane
+constexpr int kGnPX = 4;                // columns per lane (conv2, conv3)
+constexpr int kGnStage = 6400;          // weights per stage: 8 input channels x 25 x 32, 4 x 25 x 64
+constexpr int kGnWFloats = 7200;        // the stage in LDS, rows padded by 4: 200 x 36 >= 100 x 68
+constexpr int kGnStat = 16 + 2 * kGnTS * 64;   // mean / rstd, nll / hit, then (scale, shift)
+constexpr int kGnMaxCin = 4, kGnMinHW = 15, kGnMaxHW = 64;
+constexpr int64_t kGnLdsMax = 160 * 1024;
+constexpr int64_t kGnMaxSlots = 4096;
+constexpr int64_t kGnMaxGrid = 1 << 20;
+
+struct GnShape {
+    int Cin, H, W, C;
+    int h1, w1, h2, w2, h3, w3, F;
+    // offsets of the 14 tensors in a row (model.parameters() order)
+    int c1w, c1b, g1w, g1b, c2w, c2b, g2w, g2b, c3w, c3b, g3w, g3b, fw, fb;
+    int64_t P;
+};
+
+__host__ __device__ inline int gn_down(int h) { return (h - 3) / 2 + 1; }
+
+inline GnShape gn_shape(int Cin, int H, int W, int C) {
+    GnShape g;
+    g.Cin = Cin; g.H = H; g.W = W; g.C = C;
+    g.h1 = gn_down(H); g.w1 = gn_down(W);
+    g.h2 = gn_down(g.h1); g.w2 = gn_down(g.w1);
+    g.h3 = gn_down(g.h2); g.w3 = gn_down(g.w2);
+    g.F = 64 * g.h3 * g.w3;
+    int o = 0;
+    g.c1w = o; o += 32 * Cin * 25; g.c1b = o; o += 32; g.g1w = o; o += 32; g.g1b = o; o += 32;
+    g.c2w = o; o += 32 * 32 * 25; g.c2b = o; o += 32; g.g2w = o; o += 32; g.g2b = o; o += 32;
+    g.c3w = o; o += 64 * 32 * 25; g.c3b = o; o += 64; g.g3w = o; o += 64; g.g3b = o; o += 64;
+    g.fw = o;
+    g.fb = o + C * g.F;                           // C <= 1024, F <= 3136
+    g.P = (int64_t)g.fb + C;
+    return g;
+}
+
+// floats of one workgroup's two activation buffers
+inline int64_t gn_act_floats(const GnShape &g) { return 2 * (int64_t)kGnTS * 32 * g.h1 * g.w1; }
+inline int64_t gn_lds_bytes_global() { return (int64_t)(kGnWFloats + kGnStat) * 4; }
+inline int64_t gn_lds_bytes(const GnShape &g) { return gn_lds_bytes_global() + gn_act_floats(g) * 4; }
+
+// max_pool2d's maximum: a NaN wins and stays
+__device__ __forceinline__ float gn_max(float a, float b) { return (b > a || b != b) ? b : a; }
+__device__ __forceinline__ float gn_relu(float v) { return v <= 0.f ? 0.f : v; }
+
+__device__ __forceinline__ float gn_wave_sum(float v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+// conv1 + maxpool: in = the tile's samples [Cin, H, W] in global memory (sample s at x0 + s *
+// Cin H W; the caller clamps s to the tile), out [kGnTS, 32, h1, w1] = max over the 3 x 3 window
+// of the conv outputs, plus the bias.
+__device__ __forceinline__ void gn_conv1_pool(const float *__restrict__ x0, int ns, const GnShape &g,
+                                              const float *__restrict__ th, float *out, float *ws) {
+    constexpr int WS = 32 + 4;
+    const int tid = threadIdx.x;
+    const int nk = g.Cin * 25;
+    for (int e = tid; e < 32 * nk; e += 256) ws[(e % nk) * WS + e / nk] = th[g.c1w + e];
+    __syncthreads();
+    const int hw1 = g.h1 * g.w1, per_g = kGnTS * hw1;
+    const int64_t sample = (int64_t)g.Cin * g.H * g.W;
+#pragma unroll 1
+    for (int item = tid; item < 4 * per_g; item += 256) {
+        const int ocg = item / per_g, rem = item % per_g;
+        const int s = rem / hw1, pos = rem % hw1;
+        const int pi = pos / g.w1, pj = pos % g.w1;
+        const float *xs = x0 + (int64_t)(s < ns ? s : 0) * sample;
+        float acc[9][kGnOT];
+#pragma unroll
+        for (int a = 0; a < 9; ++a)
+#pragma unroll
+            for (int o = 0; o < kGnOT; ++o) acc[a][o] = 0.f;
+#pragma unroll 1
+        for (int ic = 0; ic < g.Cin; ++ic) {
+            float patch[7][7];
+#pragma unroll
+            for (int r = 0; r < 7; ++r) {
+                const int yy = 2 * pi - 2 + r;
+                const bool rok = (unsigned)yy < (unsigned)g.H;
+#pragma unroll
+                for (int c = 0; c < 7; ++c) {
+                    const int xx = 2 * pj - 2 + c;
+                    const bool ok = rok && (unsigned)xx < (unsigned)g.W;
+                    const float v = xs[((int64_t)ic * g.H + (ok ? yy : 0)) * g.W + (ok ? xx : 0)];
+                    patch[r][c] = ok ? v : 0.f;
+                }
+            }
+#pragma unroll
+            for (int ky = 0; ky < 5; ++ky)
+#pragma unroll
+                for (int kx = 0; kx < 5; ++kx) {
+                    const float *wp = ws + (ic * 25 + ky * 5 + kx) * WS + ocg * kGnOT;
+                    const float4 wa = *reinterpret_cast<const float4 *>(wp);
+                    const float4 wb = *reinterpret_cast<const float4 *>(wp + 4);
+                    const float wv[kGnOT] = {wa.x, wa.y, wa.z, wa.w, wb.x, wb.y, wb.z, wb.w};
+#pragma unroll
+                    for (int di = 0; di < 3; ++di)
+#pragma unroll
+                        for (int dj = 0; dj < 3; ++dj)
+#pragma unroll
+                            for (int o = 0; o < kGnOT; ++o)
+                                acc[di * 3 + dj][o] = __builtin_fmaf(patch[di + ky][dj + kx], wv[o], acc[di * 3 + dj][o]);
+                }
+        }
+#pragma unroll
+        for (int o = 0; o < kGnOT; ++o) {
+            float m = acc[0][o];
+#pragma unroll
+            for (int a = 1; a < 9; ++a) m = gn_max(m, acc[a][o]);
+            const int oc = ocg * kGnOT + o;
+            out[(s * 32 + oc) * hw1 + pos] = m + th[g.c1b + oc];
+        }
+    }
+    __syncthreads();
+}
+
+// 5 x 5 convolution, 32 -> CO channels, zero padding 2: in [kGnTS, 32, h, w] -> out [kGnTS, CO, h, w]
+// (bias added).  wg: the weights [CO, 32, 5, 5] of the job's row, bg the bias.  Every output is
+// one fma chain over (input channel, ky, kx) from 0.
+template <int CO>
+__device__ __forceinline__ void gn_conv(const float *in, float *out, int h, int w,
+                                        const float *__restrict__ wg, const float *__restrict__ bg,
+                                        float *ws) {
+    constexpr int ICB = kGnStage / (25 * CO);    // input channels per stage: 8 or 4
+    constexpr int KR = ICB * 25;                 // k rows per stage
+    constexpr int WS = CO + 4;
+    constexpr int NST = 32 / ICB;
+    constexpr int NPRE = kGnStage / 256;
+    static_assert(KR * WS <= kGnWFloats && NPRE * 256 == kGnStage, "stage size");
+    const int tid = threadIdx.x;
+    const int xg = (w + kGnPX - 1) / kGnPX, per_s = h * xg;
+    const int n_items = (CO / kGnOT) * kGnTS * per_s;
+#pragma unroll 1
+    for (int base = 0; base < n_items; base += 512) {
+        int is[2], iy[2], ix[2], io[2];
+        bool ok[2];
+        float acc[2][kGnPX][kGnOT];
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int item = base + r * 256 + tid;
+            ok[r] = item < n_items;
+            const int it = ok[r] ? item : 0;
+            io[r] = it / (kGnTS * per_s);
+            const int rem = it % (kGnTS * per_s);
+            is[r] = rem / per_s;
+            iy[r] = (rem % per_s) / xg;
+            ix[r] = ((rem % per_s) % xg) * kGnPX;
+#pragma unroll
+            for (int p = 0; p < kGnPX; ++p)
+#pragma unroll
+                for (int o = 0; o < kGnOT; ++o) acc[r][p][o] = 0.f;
+        }
+        float pre[NPRE];
+        auto fetch = [&](int st) {               // element e of the stage: channel e / KR, k row e % KR
+#pragma unroll
+            for (int q = 0; q < NPRE; ++q) {
+                const int e = q * 256 + tid;
+                pre[q] = wg[((e / KR) * 32 + st * ICB) * 25 + e % KR];
+            }
+        };
+        fetch(0);
+#pragma unroll 1
+        for (int st = 0; st < NST; ++st) {
+            __syncthreads();                     // the previous stage has been read
+#pragma unroll
+            for (int q = 0; q < NPRE; ++q) {
+                const int e = q * 256 + tid;
+                ws[(e % KR) * WS + e / KR] = pre[q];
+            }
+            __syncthreads();
+            if (st + 1 < NST) fetch(st + 1);
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                if (base + r * 256 >= n_items) continue;          // block-uniform
+#pragma unroll 1
+                for (int icl = 0; icl < ICB; ++icl) {
+                    const float *ip = in + ((is[r] * 32 + st * ICB + icl) * h) * w;
+#pragma unroll
+                    for (int ky = 0; ky < 5; ++ky) {
+                        const int yy = iy[r] + ky - 2;
+                        const bool rok = (unsigned)yy < (unsigned)h;
+                        const float *rp = ip + (rok ? yy : 0) * w;
+                        float v[kGnPX + 4];
+#pragma unroll
+                        for (int e = 0; e < kGnPX + 4; ++e) {
+                            const int xx = ix[r] - 2 + e;
+                            const bool in_x = rok && (unsigned)xx < (unsigned)w;
+                            const float t = rp[in_x ? xx : 0];
+                            v[e] = in_x ? t : 0.f;
+                        }
+#pragma unroll
+                        for (int kx = 0; kx < 5; ++kx) {
+                            const float *wp = ws + (icl * 25 + ky * 5 + kx) * WS + io[r] * kGnOT;
+                            const float4 wa = *reinterpret_cast<const float4 *>(wp);
+                            const float4 wb = *reinterpret_cast<const float4 *>(wp + 4);
+                            const float wv[kGnOT] = {wa.x, wa.y, wa.z, wa.w, wb.x, wb.y, wb.z, wb.w};
+#pragma unroll
+                            for (int p = 0; p < kGnPX; ++p)
+#pragma unroll
+                                for (int o = 0; o < kGnOT; ++o)
+                                    acc[r][p][o] = __builtin_fmaf(v[p + kx], wv[o], acc[r][p][o]);
+                        }
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            if (!ok[r]) continue;
+#pragma unroll
+            for (int o = 0; o < kGnOT; ++o) {
+                const int oc = io[r] * kGnOT + o;
+                const float b = bg[oc];
+#pragma unroll
+                for (int p = 0; p < kGnPX; ++p)
+                    if (ix[r] + p < w) out[((is[r] * CO + oc) * h + iy[r]) * w + ix[r] + p] = acc[r][p][o] + b;
+            }
+        }
+    }
+    __syncthreads();
+}
+
+// GroupNorm(2, CO) statistics of buf [kGnTS, CO, hw] in two passes, then per (sample, channel)
+// scale = rstd * weight, shift = bias - scale * mean into stat[16 + 2 (s CO + c)].
+template <int CO>
+__device__ __forceinline__ void gn_stats(const float *buf, int hw, const float *__restrict__ gw,
+                                         const float *__restrict__ gb, float *stat) {
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int n = (CO / 2) * hw;
+    for (int pair = wave; pair < kGnTS * 2; pair += 4) {
+        const float *p = buf + pair * n;         // (sample, group) maps are contiguous, in this order
+        float a = 0.f;
+        for (int i = lane; i < n; i += 64) a += p[i];
+        const float mean = gn_wave_sum(a) / (float)n;
+        float q = 0.f;
+        for (int i = lane; i < n; i += 64) {
+            const float d = p[i] - mean;
+            q = __builtin_fmaf(d, d, q);
+        }
+        const float var = gn_wave_sum(q) / (float)n;
+        if (lane == 0) {
+            stat[pair * 2] = mean;
+            stat[pair * 2 + 1] = 1.0f / sqrtf(var + 1e-5f);
+        }
+    }
+    __syncthreads();
+    for (int e = tid; e < kGnTS * CO; e += 256) {
+        const int c = e % CO, pair = (e / CO) * 2 + c / (CO / 2);
+        const float scale = stat[pair * 2 + 1] * gw[c];
+        stat[16 + 2 * e] = scale;
+        stat[16 + 2 * e + 1] = __builtin_fmaf(-scale, stat[pair * 2], gb[c]);
+    }
+    __syncthreads();
+}
+
+// out [kGnTS, CO, ho, wo] = relu(maxpool(3, 2)(in * scale + shift)), in [kGnTS, CO, h, w]
+template <int CO>
+__device__ __forceinline__ void gn_norm_pool(const float *in, float *out, int h, int w, int ho, int wo,
+                                             const float *stat) {
+    for (int e = threadIdx.x; e < kGnTS * CO * ho * wo; e += 256) {
+        const int j = e % wo, i = (e / wo) % ho, sc = e / (wo * ho);
+        const float scale = stat[16 + 2 * sc], shift = stat[16 + 2 * sc + 1];
+        const float *p = in + (sc * h + 2 * i) * w + 2 * j;
+        float m = __builtin_fmaf(p[0], scale, shift);
+#pragma unroll
+        for (int a = 1; a < 9; ++a) m = gn_max(m, __builtin_fmaf(p[(a / 3) * w + a % 3], scale, shift));
+        out[e] = gn_relu(m);
+    }
+    __syncthreads();
+}
+
+template <bool LDS>
+__global__ __launch_bounds__(256) void k_gnl_eval(const float *__restrict__ theta, int64_t ld_t,
+                                                  const float *__restrict__ data,
+                                                  const int32_t *__restrict__ labels,
+                                                  const int32_t *__restrict__ rows,
+                                                  const int32_t *__restrict__ seg_start,
+                                                  const int32_t *__restrict__ seg_len, int64_t n_jobs,
+                                                  int max_len, int n_tiles, const GnShape g,
+                                                  double *__restrict__ part_loss,
+                                                  int32_t *__restrict__ part_cnt,
+                                                  int32_t *__restrict__ pred, int64_t ld_pred,
+                                                  float *__restrict__ logits, int64_t ld_logits,
+                                                  float *act) {
+    extern __shared__ __attribute__((aligned(16))) float gn_smem[];
+    float *ws = gn_smem, *stat = gn_smem + kGnWFloats;
+    const int tid = threadIdx.x;
+    const int hw1 = g.h1 * g.w1, a1 = kGnTS * 32 * hw1;
+    float *buf_a, *buf_b;
+    if constexpr (LDS) buf_a = gn_smem + kGnWFloats + kGnStat;
+    else buf_a = act + (int64_t)blockIdx.x * (2 * a1);
+    buf_b = buf_a + a1;
+    const int64_t n_work = n_jobs * n_tiles, sample = (int64_t)g.Cin * g.H * g.W;
+    for (int64_t wk = blockIdx.x; wk < n_work; wk += gridDim.x) {       // wk = job * n_tiles + tile
+        const int64_t job = wk / n_tiles;
+        const int t = (int)(wk % n_tiles);
+        const int left = ev_len(seg_len, job, max_len) - t * kGnTS;
+        if (left <= 0) continue;                                      // block-uniform
+        const int ns = left < kGnTS ? left : kGnTS;
+        const int64_t s0 = (int64_t)seg_start[job] + (int64_t)t * kGnTS;
+        const float *th = theta + (int64_t)rows[job] * ld_t;
+
+        gn_conv1_pool(data + s0 * sample, ns, g, th, buf_a, ws);
+        gn_stats<32>(buf_a, hw1, th + g.g1w, th + g.g1b, stat);
+        for (int e = tid; e < a1; e += 256)
+            buf_a[e] = gn_relu(__builtin_fmaf(buf_a[e], stat[16 + 2 * (e / hw1)], stat[16 + 2 * (e / hw1) + 1]));
+        __syncthreads();
+        gn_conv<32>(buf_a, buf_b, g.h1, g.w1, th + g.c2w, th + g.c2b, ws);
+        gn_stats<32>(buf_b, hw1, th + g.g2w, th + g.g2b, stat);
+        gn_norm_pool<32>(buf_b, buf_a, g.h1, g.w1, g.h2, g.w2, stat);
+        gn_conv<64>(buf_a, buf_b, g.h2, g.w2, th + g.c3w, th + g.c3b, ws);
+        gn_stats<64>(buf_b, g.h2 * g.w2, th + g.g3w, th + g.g3b, stat);
+        gn_norm_pool<64>(buf_b, buf_a, g.h2, g.w2, g.h3, g.w3, stat);
+
+        // classifier: buf_a is [kGnTS, F] in (channel, row, column) order; logits to ws [kGnTS, C]
+        const int wave = tid >> 6, lane = tid & 63;
+        for (int c = wave; c < g.C; c += 4) {
+            const float *wr = th + g.fw + (int64_t)c * g.F;
+            float z[kGnTS];
+#pragma unroll
+            for (int s = 0; s < kGnTS; ++s) z[s] = 0.f;
+            for (int f = lane; f < g.F; f += 64) {
+                const float wv = wr[f];
+#pragma unroll
+                for (int s = 0; s < kGnTS; ++s) z[s] = __builtin_fmaf(buf_a[s * g.F + f], wv, z[s]);
+            }
+            const float b = th[g.fb + c];
+#pragma unroll
+            for (int s = 0; s < kGnTS; ++s) {
+                const float v = gn_wave_sum(z[s]) + b;
+                if (lane == 0) ws[s * g.C + c] = v;
+            }
+        }
+        __syncthreads();
+        if (logits)
+            for (int e = tid; e < ns * g.C; e += 256)
+                logits[(job * ld_logits + (int64_t)t * kGnTS) * g.C + e] = ws[e];
+        if (tid < ns) {
+            const int y = labels[s0 + tid];
+            EvState q;
+            ev_scan(ws + tid * g.C, g.C, 0, y, true, q);
+            stat[8 + tid] = (q.best + logf(q.sum)) - q.zy;
+            stat[8 + kGnTS + tid] = q.idx == y ? 1.f : 0.f;
+            if (pred) pred[job * ld_pred + (int64_t)t * kGnTS + tid] = q.idx;
+        }
+        __syncthreads();
+        if (tid == 0) {                                               // in sample order
+            double a = 0.0;
+            int c = 0;
+            for (int s = 0; s < ns; ++s) {
+                a += (double)stat[8 + s];
+                c += stat[8 + kGnTS + s] != 0.f;
+            }
+            part_loss[wk] = a;
+            part_cnt[wk] = c;
+        }
+        __syncthreads();                                              // ws, stat and the buffers are free
+    }
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -5722,8 +6110,88 @@ int niidmix_linear_eval_rows_f32(const float *theta, int64_t ld_t, const float *
                            (int)C, part_loss, part_cnt, pred, ld_pred);
         if (int rc = check_launch("k_lin_eval")) return rc;
     }
-    hipLaunchKernelGGL(k_lin_eval_sum, dim3((unsigned)((n_jobs + 255) / 256)), dim3(256), 0, s, seg_len,
-                       n_jobs, (int)max_len, (int)n_tiles, (const double *)part_loss,
+    hipLaunchKernelGGL(k_lin_eval_sum<kEvTS>, dim3((unsigned)((n_jobs + 255) / 256)), dim3(256), 0, s,
+                       seg_len, n_jobs, (int)max_len, (int)n_tiles, (const double *)part_loss,
+                       (const int32_t *)part_cnt, loss_sum, correct);
+    return check_launch("k_lin_eval_sum");
+}
+
+static int64_t gn_tiles(int64_t max_len) { return (max_len + kGnTS - 1) / kGnTS; }
+
+static bool gn_supported(int64_t Cin, int64_t H, int64_t W, int64_t C) {
+    return Cin >= 1 && Cin <= kGnMaxCin && C >= 1 && C <= kLinMaxC && H >= kGnMinHW && H <= kGnMaxHW &&
+           W >= kGnMinHW && W <= kGnMaxHW;
+}
+
+// workgroups of a call whose activations live in the scratch buffer (0: they fit in LDS)
+static int64_t gn_slots(const GnShape &g, int64_t n_work) {
+    if (gn_lds_bytes(g) <= kGnLdsMax) return 0;
+    return n_work < kGnMaxSlots ? n_work : kGnMaxSlots;
+}
+
+int64_t niidmix_gnlenet_eval_rows_scratch_bytes(int64_t n_jobs, int64_t max_len, int64_t Cin, int64_t H,
+                                                int64_t W, int64_t C) {
+    if (n_jobs <= 0 || max_len <= 0 || !gn_supported(Cin, H, W, C)) return 0;
+    const GnShape g = gn_shape((int)Cin, (int)H, (int)W, (int)C);
+    const int64_t n_work = n_jobs * gn_tiles(max_len);
+    // a double and an int32 per (job, tile), to a multiple of 16 B; then the activation slots
+    return (n_work * 12 + 15) / 16 * 16 + gn_slots(g, n_work) * gn_act_floats(g) * 4;
+}
+
+int niidmix_gnlenet_eval_rows_f32(const float *theta, int64_t ld_t, const float *data,
+                                  const int32_t *labels, const int32_t *rows, const int32_t *seg_start,
+                                  const int32_t *seg_len, int64_t n_jobs, int64_t max_len,
+                                  double *loss_sum, int32_t *correct, int32_t *pred, int64_t ld_pred,
+                                  float *logits, int64_t ld_logits, int64_t Cin, int64_t H, int64_t W,
+                                  int64_t C, void *scratch, int64_t scratch_bytes, void *stream) {
+    if (!theta || !data || !labels || !rows || !seg_start || !seg_len || !loss_sum || !correct || !scratch)
+        return set_error(NIIDMIX_EINVAL, "null pointer");
+    if (n_jobs <= 0 || Cin <= 0 || H <= 0 || W <= 0 || C <= 0)
+        return set_error(NIIDMIX_EINVAL, "n_jobs, Cin, H, W and C must be >= 1");
+    if (max_len < 0) return set_error(NIIDMIX_EINVAL, "negative max_len");
+    if (C > kLinMaxC) return set_error(NIIDMIX_EUNSUPPORTED, "C %lld > %lld", (long long)C, (long long)kLinMaxC);
+    if (Cin > kGnMaxCin) return set_error(NIIDMIX_EUNSUPPORTED, "Cin %lld > %d", (long long)Cin, kGnMaxCin);
+    if (!gn_supported(Cin, H, W, C))
+        return set_error(NIIDMIX_EUNSUPPORTED, "H %lld, W %lld: the kernel holds %d <= H, W <= %d",
+                         (long long)H, (long long)W, kGnMinHW, kGnMaxHW);
+    if (max_len > 0x7fffffff) return set_error(NIIDMIX_EUNSUPPORTED, "max_len %lld: int32 segments", (long long)max_len);
+    const GnShape g = gn_shape((int)Cin, (int)H, (int)W, (int)C);
+    if (int rc = check_ld(ld_t, ld_t, g.P, "P")) return rc;
+    if (pred && ld_pred < max_len) return set_error(NIIDMIX_EINVAL, "ld_pred < max_len");
+    if (logits && ld_logits < max_len) return set_error(NIIDMIX_EINVAL, "ld_logits < max_len");
+    const int64_t need = niidmix_gnlenet_eval_rows_scratch_bytes(n_jobs, max_len, Cin, H, W, C);
+    if (scratch_bytes < need || (reinterpret_cast<uintptr_t>(scratch) & 7u))
+        return set_error(NIIDMIX_EINVAL, "scratch of %lld bytes (8-B aligned), %lld needed",
+                         (long long)scratch_bytes, (long long)need);
+    // `rows` lives on the device and may repeat: one row of theta is all that is known to be read
+    auto hits_theta = [&](const void *q, int64_t bytes) {
+        const char *a = reinterpret_cast<const char *>(q), *t0 = reinterpret_cast<const char *>(theta);
+        return bytes > 0 && a < t0 + g.P * 4 && t0 < a + bytes;
+    };
+    if (hits_theta(loss_sum, n_jobs * 8) || hits_theta(correct, n_jobs * 4) ||
+        (pred && hits_theta(pred, ((n_jobs - 1) * ld_pred + max_len) * 4)) ||
+        (logits && hits_theta(logits, ((n_jobs - 1) * ld_logits + max_len) * C * 4)) ||
+        hits_theta(scratch, need))
+        return set_error(NIIDMIX_EALIAS, "an output or the scratch buffer overlaps theta");
+    const int64_t n_tiles = gn_tiles(max_len), n_work = n_jobs * n_tiles;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    double *part_loss = reinterpret_cast<double *>(scratch);
+    int32_t *part_cnt = reinterpret_cast<int32_t *>(part_loss + n_work);
+    if (n_tiles > 0) {
+        const int64_t slots = gn_slots(g, n_work);
+        float *act = reinterpret_cast<float *>(reinterpret_cast<char *>(scratch) + (n_work * 12 + 15) / 16 * 16);
+        const int64_t grid = slots ? slots : n_work < kGnMaxGrid ? n_work : kGnMaxGrid;
+        const size_t lds = slots ? gn_lds_bytes_global() : gn_lds_bytes(g);
+        auto k1 = pick<true, false>(slots == 0, [](auto L) { return k_gnl_eval<L()>; });
+        if (lds > 64 * 1024)
+            if (int rc = lds_opt_in(k1, lds, "k_gnl_eval")) return rc;
+        hipLaunchKernelGGL(k1, dim3((unsigned)grid), dim3(256), lds, s, theta, ld_t, data, labels, rows,
+                           seg_start, seg_len, n_jobs, (int)max_len, (int)n_tiles, g, part_loss, part_cnt,
+                           pred, ld_pred, logits, ld_logits, act);
+        if (int rc = check_launch("k_gnl_eval")) return rc;
+    }
+    hipLaunchKernelGGL(k_lin_eval_sum<kGnTS>, dim3((unsigned)((n_jobs + 255) / 256)), dim3(256), 0, s,
+                       seg_len, n_jobs, (int)max_len, (int)n_tiles, (const double *)part_loss,
                        (const int32_t *)part_cnt, loss_sum, correct);
     return check_launch("k_lin_eval_sum");
 }

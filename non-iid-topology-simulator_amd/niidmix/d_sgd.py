@@ -22,7 +22,7 @@ Gradient averaging (--clique-gradient, --unbiased-gradient) also runs on the GPU
 With --device-training (params['algorithm']['device-training'], opt-in) a linear model's local
 training runs on the device too: gradient, step and mixing never leave HBM (niidmix.train).
 With --device-evaluation (params['algorithm']['device-evaluation'], opt-in) the logger's accuracy
-and loss events of linear models are computed on the device as well (niidmix.evaluate).
+and loss events of linear and GN-LeNet models are computed on the device as well (niidmix.evaluate).
 """
 import argparse
 import itertools

@@ -1,4 +1,4 @@
-"""Accuracy and loss of linear models on the device (`--device-evaluation`).
+"""Accuracy and loss of linear and GN-LeNet models on the device (`--device-evaluation`).
 
 The reference's logger evaluates every logged node with CPU DataLoader loops: its own train-set
 in Logger.log_train_accuracy (tools/simulate/logger.py:205-249), and the shared validation, test
@@ -16,9 +16,17 @@ set for all nodes at once (niidmix::linear_eval_rows):
                                           (total correct / total samples, mean of the chunks' mean
                                           losses)
 
-Not bit-identical to the CPU loops (another summation order; tests/test_gpu_eval.py states the
-bounds), so the path is opt-in.  A model that is not log_softmax(Linear) is refused with a
-ValueError naming the flag: there is no silent CPU fallback.
+The reference's other model, GN-LeNet (setup/model/gn_lenet.py: three 5 x 5 convolutions with
+GroupNorm(2), max-pooling and ReLU, then one Linear), goes through niidmix::gnlenet_eval_rows the
+same way.  Its parameters are read in place from a fresh single-stripe resident round's output slab
+(niidmix.slab.ResidentRound, on its mixing stream), else stacked and uploaded; the job list of a
+call is cut so that the kernel's scratch stays within a fraction of the free HBM (a job's results
+do not depend on the cut).
+
+Not bit-identical to the CPU loops (another summation order; tests/test_gpu_eval.py and
+tests/test_gpu_eval_gnlenet.py state the bounds), so the path is opt-in.  A model that is neither
+log_softmax(Linear) nor GN-LeNet is refused with a ValueError naming the flag: there is no silent
+CPU fallback.
 """
 import sys
 
@@ -29,6 +37,9 @@ from . import ops, train
 FLAG = "--device-evaluation"
 CHUNK = 1000          # Logger.log_train_accuracy's DataLoader batch size (logger.py:217)
 SET_NAMES = ("valid", "test", "full-train")
+# the GN-LeNet kernel's limits (include/niidmix.h)
+GN_MAX_CIN, GN_MIN_HW, GN_MAX_HW = 4, 15, 64
+SCRATCH_FRACTION = 0.8   # of the free HBM, for one call's scratch (DeviceTrainer._check_fit's rule)
 
 
 def enabled(params):
@@ -62,33 +73,69 @@ def fold_chunks(n_nodes, node, length, loss_sum, correct):
     return [(t[0] / t[1], t[2] / t[3]) if t[1] else (0.0, 0.0) for t in tot]
 
 
+def gn_lenet_shape(model):
+    """(Cin, C, F) when the model's parameters are exactly GN-LeNet's 14 tensors in registration
+    order (include/niidmix.h, niidmix_gnlenet_eval_rows_f32), fp32 and trainable, else None."""
+    ps = list(model.parameters())
+    if len(ps) != 14 or ps[0].dim() != 4 or ps[12].dim() != 2:
+        return None
+    if any(q.dtype != torch.float32 or not q.requires_grad for q in ps):
+        return None
+    cin, (c, f) = int(ps[0].shape[1]), (int(v) for v in ps[12].shape)
+    want = [(32, cin, 5, 5), (32,), (32,), (32,), (32, 32, 5, 5), (32,), (32,), (32,),
+            (64, 32, 5, 5), (64,), (64,), (64,), (c, f), (c,)]
+    if [tuple(q.shape) for q in ps] != want or cin < 1 or f < 64 or f % 64:
+        return None
+    return cin, c, f
+
+
+def gn_lenet_offsets(cin, c, f):
+    """Start of each of the 14 tensors in a flattened row, and P at the end (15 values)."""
+    sizes = [800 * cin, 32, 32, 32, 25600, 32, 32, 32, 51200, 64, 64, 64, c * f, c]
+    out = [0]
+    for v in sizes:
+        out.append(out[-1] + v)
+    return out
+
+
 def check_eligible(nodes, params):
     """The refusals that need no GPU (d_sgd.init calls this): raises ValueError naming the flag.
-    Returns (K, C)."""
+    Returns (K, C) for linear models and (Cin, C, F) for GN-LeNet."""
     if not nodes:
         raise ValueError(f"{FLAG}: no nodes")
-    return _shape([nd["model"] for nd in nodes])
+    return _shape([nd["model"] for nd in nodes])[1]
 
 
 def _shape(models):
-    shape = train.linear_shape(models[0])
+    """(kind, shape) of a model list that is all-linear ("linear", (K, C)) or all-GN-LeNet
+    ("gn-lenet", (Cin, C, F)), of one shape."""
+    kind, shape = "linear", train.linear_shape(models[0])
+    if shape is None:
+        kind, shape = "gn-lenet", gn_lenet_shape(models[0])
+    of = train.linear_shape if kind == "linear" else gn_lenet_shape
     for i, mdl in enumerate(models):
-        if shape is None or train.linear_shape(mdl) != shape:
+        if shape is None or of(mdl) != shape:
             raise ValueError(f"{FLAG} needs models whose parameters are exactly a [C, K] weight and "
-                             f"a [C] bias, the same on every model (model {i} differs)")
+                             f"a [C] bias, or exactly GN-LeNet's 14 tensors, the same on every model "
+                             f"(model {i} differs)")
     if shape[1] > train.MAX_C:
         raise ValueError(f"{FLAG}: C = {shape[1]} exceeds the kernel's limit (C <= {train.MAX_C})")
-    return shape
+    if kind == "gn-lenet" and shape[0] > GN_MAX_CIN:
+        raise ValueError(f"{FLAG}: {shape[0]} input channels exceed the kernel's limit "
+                         f"(Cin <= {GN_MAX_CIN})")
+    return kind, shape
 
 
 class _Set:
-    """A sample set in HBM: data [M, K] fp32, labels [M] int32, and its first samples as the model
-    takes them (for the forward probe)."""
+    """A sample set in HBM: data [M, K] fp32 (the samples flattened), labels [M] int32, the shape
+    of one sample as the model takes it ((Cin, H, W) for images), and its first samples in that
+    shape (for the forward probe)."""
 
     def __init__(self, data, labels, lo, hi, probe):
         self.data, self.labels, self.lo, self.hi, self.probe = data, labels, lo, hi, probe
         self.m = int(labels.shape[0])
         self.k = int(data.shape[1]) if self.m else None
+        self.shape = tuple(probe[0].shape[1:]) if probe is not None else None
 
 
 def _materialise(source, device, what):
@@ -124,8 +171,10 @@ class DeviceEvaluator:
         self.params = params
         self.device = torch.device(device) if device is not None else None
         self.sets = {}
-        self.last_source = None          # "trainer" (device slab read in place) or "stacked"
-        self._probed = set()             # (model class, K, C) whose forward was probed
+        self.last_source = None          # "trainer" / "resident" (device slab read in place) or "stacked"
+        self.scratch_budget = None       # bytes of scratch per GN-LeNet call (None: SCRATCH_FRACTION
+        self.last_calls = 0              # of the free HBM), and the calls the last job list took
+        self._probed = set()             # (model class, kind, sizes) whose forward was probed
         self._train = None               # (train-sets, _Set, offsets) of the last node list
 
     def _dev(self):
@@ -155,57 +204,153 @@ class DeviceEvaluator:
             self.sets[name] = _materialise(fn(self.params), self._dev(), f"the {name} set")
         return self.sets[name]
 
-    def _check(self, st, k, c, what):
-        if st.m and st.k != k:
-            raise ValueError(f"{FLAG}: the samples of {what} flatten to {st.k} values, the model "
-                             f"takes K = {k}")
+    def _check(self, st, spec, what):
+        """Refuses a set the models do not take; returns the kernel's size arguments: (K, C) for
+        linear models, (Cin, H, W, C) for GN-LeNet."""
+        kind, shape = spec
+        c = shape[1]
         if st.m and (st.lo < 0 or st.hi >= c):
             raise ValueError(f"{FLAG}: {what} has a label outside [0, {c})")
+        if kind == "linear":
+            if st.m and st.k != shape[0]:
+                raise ValueError(f"{FLAG}: the samples of {what} flatten to {st.k} values, the model "
+                                 f"takes K = {shape[0]}")
+            return shape
+        cin, _, f = shape
+        sh = st.shape
+        if sh is None or len(sh) != 3 or sh[0] != cin:
+            raise ValueError(f"{FLAG}: the samples of {what} have shape {sh}, GN-LeNet takes "
+                             f"[{cin}, H, W]")
+        h, w = int(sh[1]), int(sh[2])
+        if not (GN_MIN_HW <= h <= GN_MAX_HW and GN_MIN_HW <= w <= GN_MAX_HW):
+            raise ValueError(f"{FLAG}: samples of {h} x {w} in {what}: the kernel takes "
+                             f"{GN_MIN_HW} <= H, W <= {GN_MAX_HW}")
+        if ops.gnlenet_sizes(cin, h, w, c)[0] != f:
+            raise ValueError(f"{FLAG}: samples of shape {tuple(sh)} in {what} give GN-LeNet "
+                             f"{ops.gnlenet_sizes(cin, h, w, c)[0]} features, the model's classifier "
+                             f"takes F = {f}")
+        return cin, h, w, c
 
-    def _probe(self, model, st, k, c):
-        key = (type(model), k, c)
+    def _probe(self, model, st, spec, sizes):
+        key = (type(model), spec[0]) + tuple(sizes)
         if key in self._probed or st.probe is None:
             return
         try:
-            train.probe_forward(model, st.probe[0], st.probe[1], self.params, self._dev(), FLAG)
+            if spec[0] == "linear":
+                train.probe_forward(model, st.probe[0], st.probe[1], self.params, self._dev(), FLAG)
+            else:
+                self._probe_gn_lenet(model, st.probe[0], st.probe[1], sizes)
         except ValueError:
             raise
         except Exception as e:         # a forward that does not take these samples at all
             raise ValueError(f"{FLAG}: the model's forward failed on the set's samples "
-                             f"({type(e).__name__}: {e}); only log_softmax(Linear) is evaluated")
+                             f"({type(e).__name__}: {e}); only log_softmax(Linear) and GN-LeNet are "
+                             "evaluated")
         self._probed.add(key)
+
+    def _probe_gn_lenet(self, model, x, y, sizes):
+        """The group count and the layer order cannot be read from parameter shapes: require that
+        the kernel's log-softmaxed logits on the set's first samples agree with model.forward on
+        the CPU within 1e-3 max(1, max |z|) (another architecture differs by O(0.1))."""
+        from . import d_sgd
+        d_sgd.synchronize()
+        cin, h, w, c = sizes
+        dev, nb = self._dev(), int(x.shape[0])
+        with torch.no_grad():
+            want = model.forward(x, self.params).detach().to(torch.float32)
+        p = ops.gnlenet_sizes(cin, h, w, c)[1]
+        theta = torch.zeros((1, train.padded_ld(p)), dtype=torch.float32, device=dev)[:, :p]
+        theta.copy_(train._flat_params([model]))
+        z = torch.zeros((1, nb, c), dtype=torch.float32, device=dev)
+        idx = torch.tensor([[0], [0], [nb]], dtype=torch.int32).to(dev)
+        ops.gnlenet_eval_rows(theta, x.reshape(nb, -1).to(torch.float32).contiguous().to(dev),
+                              y.to(torch.int32).to(dev), idx[0], idx[1], idx[2], nb,
+                              torch.empty(1, dtype=torch.float64, device=dev),
+                              torch.empty(1, dtype=torch.int32, device=dev), None, z, cin, h, w, c)
+        z = z[0].cpu()
+        got = torch.log_softmax(z, 1)
+        bound = 1e-3 * max(1.0, float(z.abs().max()))
+        worst = float((got - want).abs().max()) if tuple(want.shape) == tuple(got.shape) else float("nan")
+        if not worst <= bound:
+            raise ValueError(
+                f"{FLAG}: the model's forward is not GN-LeNet's (5 x 5 convolutions of 32 / 32 / 64 "
+                f"channels, GroupNorm(2), conv-pool-norm then conv-norm-pool twice, one Linear): on "
+                f"the first {nb} samples the kernel's log-probabilities differ from forward on the "
+                f"CPU by {worst:.3g} (bound {bound:.3g})")
 
     # -------------------------------------------------------------------------------------------
     def _theta(self, models):
-        """(theta slab [*, P] on the device, row of each model)."""
+        """(theta slab [*, P] on the device, row of each model, (kind, shape), the stream the slab
+        must be read on or None for the current one)."""
         from . import d_sgd
-        k, c = _shape(models)
-        hit = d_sgd.device_trainer(models)
-        if hit is not None:
-            tr, rows = hit
-            if self.device is None or tr.device == self.device:
-                cur = tr.current()
-                if cur is not None:
-                    self.device = tr.device
-                    self.last_source = "trainer"
-                    return cur, rows, k, c
+        spec = _shape(models)
+        kind, shape = spec
+        if kind == "linear":
+            k, c = shape
+            p = c * k + c
+            hit = d_sgd.device_trainer(models)
+            if hit is not None:
+                tr, rows = hit
+                if self.device is None or tr.device == self.device:
+                    cur = tr.current()
+                    if cur is not None:
+                        self.device = tr.device
+                        self.last_source = "trainer"
+                        return cur, rows, spec, None
+        else:
+            from . import logger as nl
+            cin, c, f = shape
+            p = gn_lenet_offsets(cin, c, f)[-1]
+            hit = nl._fresh_resident(models)
+            if hit is not None and len(hit[0].parts) == 1 and hit[0].p == p:
+                pt = hit[0].parts[0]
+                if self.device is None or pt["dev"] == self.device:
+                    self.device = pt["dev"]
+                    self.last_source = "resident"
+                    return pt["outs"][0], hit[1], spec, pt["s_mix"]
         d_sgd.synchronize()              # the models must hold the last round's rows
-        p = c * k + c
         theta = torch.zeros((len(models), train.padded_ld(p)), dtype=torch.float32,
                             device=self._dev())[:, :p]
         theta.copy_(train._flat_params(models))
         self.last_source = "stacked"
-        return theta, list(range(len(models))), k, c
+        return theta, list(range(len(models))), spec, None
 
-    def _run(self, theta, st, rows, start, length, k, c):
+    def _gn_cut(self, n, max_len, sizes, dev):
+        """Jobs per call of the GN-LeNet kernel: as many as keep its scratch within the budget."""
+        from ._lib import lib
+        budget = self.scratch_budget
+        if budget is None:
+            budget = SCRATCH_FRACTION * torch.cuda.mem_get_info(dev)[0]
+        need = lambda k: int(lib.niidmix_gnlenet_eval_rows_scratch_bytes(k, max_len, *sizes))  # noqa: E731
+        if need(1) > budget:
+            raise RuntimeError(f"{FLAG}: {need(1) / 2**30:.2f} GiB of scratch for one job of "
+                               f"{max_len} samples exceed the budget of {budget / 2**30:.2f} GiB")
+        k = n
+        while need(k) > budget:          # the size grows with the jobs: halve until it fits
+            k = (k + 1) // 2
+        return k
+
+    def _run(self, theta, st, rows, start, length, spec, sizes, stream=None):
         dev = theta.device
-        n = len(rows)
-        idx = torch.tensor([rows, start, length], dtype=torch.int32).to(dev)
-        loss = torch.empty(n, dtype=torch.float64, device=dev)
-        correct = torch.empty(n, dtype=torch.int32, device=dev)
-        ops.linear_eval_rows(theta, st.data, st.labels, idx[0], idx[1], idx[2], max(length), loss,
-                             correct, None, k, c)
-        return loss.cpu().tolist(), correct.cpu().tolist()
+        with torch.cuda.device(dev), torch.cuda.stream(stream or torch.cuda.current_stream(dev)):
+            n = len(rows)
+            idx = torch.tensor([rows, start, length], dtype=torch.int32).to(dev)
+            loss = torch.empty(n, dtype=torch.float64, device=dev)
+            correct = torch.empty(n, dtype=torch.int32, device=dev)
+            if spec[0] == "linear":
+                ops.linear_eval_rows(theta, st.data, st.labels, idx[0], idx[1], idx[2], max(length),
+                                     loss, correct, None, *sizes)
+            else:
+                cut = self._gn_cut(n, max(length), sizes, dev)
+                self.last_calls = 0
+                for a in range(0, n, cut):
+                    b = min(n, a + cut)
+                    ops.gnlenet_eval_rows(theta, st.data, st.labels, idx[0, a:b], idx[1, a:b],
+                                          idx[2, a:b], max(length[a:b]), loss[a:b], correct[a:b],
+                                          None, None, *sizes)
+                    self.last_calls += 1
+            # read back on the same stream: a copy on another one would not wait for the kernel
+            return loss.cpu().tolist(), correct.cpu().tolist()
 
     @staticmethod
     def _models(items):
@@ -217,13 +362,14 @@ class DeviceEvaluator:
         models = self._models(models_or_nodes)
         if not models:
             return []
-        theta, rows, k, c = self._theta(models)
+        theta, rows, spec, stream = self._theta(models)
         st = self._set(set_name)
         if st.m == 0:
             return [(0.0, 0.0) for _ in models]
-        self._check(st, k, c, f"the {set_name} set")
-        self._probe(models[0], st, k, c)
-        loss, correct = self._run(theta, st, rows, [0] * len(rows), [st.m] * len(rows), k, c)
+        sizes = self._check(st, spec, f"the {set_name} set")
+        self._probe(models[0], st, spec, sizes)
+        loss, correct = self._run(theta, st, rows, [0] * len(rows), [st.m] * len(rows), spec, sizes,
+                                  stream)
         return [(cr / st.m, ls / st.m) for ls, cr in zip(loss, correct)]
 
     def _train_sets(self, nodes, theta_dev):
@@ -258,9 +404,9 @@ class DeviceEvaluator:
         nodes = list(nodes)
         if not nodes:
             return []
-        theta, rows, k, c = self._theta([nd["model"] for nd in nodes])
+        theta, rows, spec, stream = self._theta([nd["model"] for nd in nodes])
         st, ranges = self._train_sets(nodes, theta.device)
-        self._check(st, k, c, "the nodes' train-sets")
+        sizes = self._check(st, spec, "the nodes' train-sets") if st.m else None
         node, start, length = [], [], []
         for i, (a, b) in enumerate(ranges):
             nd, s, ln = chunk_jobs([a, b])
@@ -269,8 +415,9 @@ class DeviceEvaluator:
             length += ln
         if not node:
             return [(0.0, 0.0) for _ in nodes]
-        self._probe(nodes[0]["model"], st, k, c)
-        loss, correct = self._run(theta, st, [rows[i] for i in node], start, length, k, c)
+        self._probe(nodes[0]["model"], st, spec, sizes)
+        loss, correct = self._run(theta, st, [rows[i] for i in node], start, length, spec, sizes,
+                                  stream)
         return fold_chunks(len(nodes), node, length, loss, correct)
 
 

@@ -28,6 +28,8 @@ Ops (registered in the `niidmix` namespace, usable as torch.ops.niidmix.*):
                    K, C)                            k_lin_eval + k_lin_eval_sum (summed loss, correct
                                                     count and predictions of a linear model per
                                                     (row, sample segment), --device-evaluation)
+  gnlenet_eval_rows(theta, data, labels, rows, seg_start, seg_len, max_len, loss_sum, correct, pred,
+                    logits, Cin, H, W, C)           k_gnl_eval + k_lin_eval_sum (the same for GN-LeNet)
 All ops launch on torch's current HIP stream of the input's device, never synchronise, and raise
 RuntimeError (TORCH_CHECK-style) on bad arguments.  They accept HIP tensors only: there is no CPU
 implementation and no fallback.
@@ -664,6 +666,74 @@ def linear_eval_rows(theta: torch.Tensor, data: torch.Tensor, labels: torch.Tens
         pred.data_ptr() if pred is not None else None, _ld(pred) if pred is not None else 0,
         K, C, scratch.data_ptr(), nbytes, _stream(theta))
     _lib.check(rc, "niidmix::linear_eval_rows")
+
+
+def gnlenet_sizes(Cin, H, W, C):
+    """(F, P) of a GN-LeNet row (include/niidmix.h, niidmix_gnlenet_eval_rows_f32): the classifier's
+    input size and the parameter count."""
+    def down(h):
+        return (h - 3) // 2 + 1
+    f = 64 * down(down(down(H))) * down(down(down(W)))
+    return f, 800 * Cin + 77184 + C * f + C
+
+
+@torch.library.custom_op("niidmix::gnlenet_eval_rows",
+                         mutates_args=("loss_sum", "correct", "pred", "logits"))
+def gnlenet_eval_rows(theta: torch.Tensor, data: torch.Tensor, labels: torch.Tensor,
+                      rows: torch.Tensor, seg_start: torch.Tensor, seg_len: torch.Tensor,
+                      max_len: int, loss_sum: torch.Tensor, correct: torch.Tensor,
+                      pred: Optional[torch.Tensor], logits: Optional[torch.Tensor],
+                      Cin: int, H: int, W: int, C: int) -> None:
+    """linear_eval_rows for GN-LeNet (include/niidmix.h, niidmix_gnlenet_eval_rows_f32): job i scores
+    row rows[i] of theta (the model's 14 parameter tensors, P columns) on data[seg_start[i] .. +
+    seg_len[i]), data [S, Cin * H * W].  logits: None or fp32 [n_jobs, >= max_len, C], the
+    classifier's output before log_softmax.  The scratch buffer comes from torch's caching
+    allocator.  The index tensors' CONTENTS are not checked here."""
+    Cin, H, W, C, max_len = int(Cin), int(H), int(W), int(C), int(max_len)
+    _req(Cin >= 1 and H >= 1 and W >= 1 and C >= 1, "Cin, H, W and C must be >= 1")
+    _req(max_len >= 0, "max_len must be >= 0")
+    _req(C <= 1024 and Cin <= 4 and 15 <= H <= 64 and 15 <= W <= 64,
+         "unsupported shape: the kernel holds C <= 1024, Cin <= 4, 15 <= H, W <= 64")
+    _, p = gnlenet_sizes(Cin, H, W, C)
+    _slab("theta", theta)
+    _req(theta.shape[1] == p, f"theta: expected P = {p} columns, got {theta.shape[1]}")
+    _slab("data", data, cols=Cin * H * W)
+    _req(data.is_contiguous(), "data: expected a contiguous [S, Cin * H * W] tensor")
+    dev = theta.device
+    _req(data.device == dev, "theta and data must be on the same device")
+    _vec("labels", labels, torch.int32, dev, data.shape[0])
+    _vec("rows", rows, torch.int32, dev)
+    n = rows.numel()
+    _req(n >= 1, "rows: at least one job")
+    _vec("seg_start", seg_start, torch.int32, dev, n)
+    _vec("seg_len", seg_len, torch.int32, dev, n)
+    _vec("loss_sum", loss_sum, torch.float64, dev, n)
+    _vec("correct", correct, torch.int32, dev, n)
+    outs = [loss_sum, correct]
+    if pred is not None:
+        _req(pred.device == dev and pred.dtype == torch.int32 and pred.dim() == 2
+             and pred.shape[0] == n and pred.shape[1] >= max_len
+             and (pred.stride(1) == 1 or pred.shape[1] <= 1),
+             f"pred: expected an int32 [{n}, >= {max_len}] tensor on {dev} with contiguous rows")
+        outs.append(pred)
+    if logits is not None:
+        _req(logits.device == dev and logits.dtype == torch.float32 and logits.dim() == 3
+             and logits.shape[0] == n and logits.shape[1] >= max_len and logits.shape[2] == C
+             and logits.is_contiguous(),
+             f"logits: expected a contiguous fp32 [{n}, >= {max_len}, {C}] tensor on {dev}")
+        outs.append(logits)
+    for o in outs:
+        _req(not _hits(o, theta), "an output overlaps theta")
+    nbytes = max(16, int(_lib.lib.niidmix_gnlenet_eval_rows_scratch_bytes(n, max_len, Cin, H, W, C)))
+    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    rc = _lib.lib.niidmix_gnlenet_eval_rows_f32(
+        theta.data_ptr(), _ld(theta), data.data_ptr(), labels.data_ptr(), rows.data_ptr(),
+        seg_start.data_ptr(), seg_len.data_ptr(), n, max_len, loss_sum.data_ptr(), correct.data_ptr(),
+        pred.data_ptr() if pred is not None else None, _ld(pred) if pred is not None else 0,
+        logits.data_ptr() if logits is not None else None,
+        logits.shape[1] if logits is not None else 0,
+        Cin, H, W, C, scratch.data_ptr(), nbytes, _stream(theta))
+    _lib.check(rc, "niidmix::gnlenet_eval_rows")
 
 
 # ------------------------------------------------------------------------------------------------
