@@ -578,6 +578,73 @@ int niidmix_gnlenet_eval_rows_f32(const float *theta, int64_t ld_t, const float 
                                   int64_t H, int64_t W, int64_t C, void *scratch,
                                   int64_t scratch_bytes, void *stream);
 
+/* Local training of GN-LeNet on the listed rows: gradient and loss of one mini-batch per row, for
+ * every row in one call (the drop-in's --device-training-gn-lenet; niidmix.train.DeviceTrainer).
+ * The job model and the argument meanings are those of niidmix_linear_nll_grad_rows_f32; the row
+ * layout, the data layout, the limits and the forward pass are those of
+ * niidmix_gnlenet_eval_rows_f32.
+ *   theta     [*, ld_t] parameters (device): a row holds the model's 14 tensors, P columns
+ *   data      [S, Cin * H * W] samples, each [Cin, H, W] row-major (device), labels [S] int32
+ *   batch_idx [n_rows, b_max] int32 sample indices into data (device); entry i belongs to rows[i]
+ *   batch_len [n_rows] int32 (device), clamped to [0, b_max]: entries past len are not read.  A
+ *             length of 0 gives a zero gradient and a NaN loss (0 / 0, as F.nll_loss of no samples)
+ *   rows      [n_rows] int32 distinct slab rows (device)
+ *   grad      [*, ld_g] gradients (device), row layout of theta: all P elements of a listed row are
+ *             written, other rows and columns past P are untouched
+ *   loss      [n_rows] mean batch loss of rows[i] (device)
+ *   scratch   caller-owned device buffer (8-B aligned) of at least
+ *             niidmix_gnlenet_nll_grad_rows_scratch_bytes(n_rows, b_max, Cin, H, W, C) bytes: a
+ *             slot per (row, tile of 2 samples) with every activation the backward pass needs and
+ *             the sample's gradients, so the size is proportional to n_rows * ceil(b_max / 2)
+ *             (about 184 KB per sample at 3 x 32 x 32, 130 KB at 1 x 28 x 28); its contents are
+ *             overwritten
+ * The result is that of F.nll_loss(model.forward(x), y).backward() on a zeroed gradient:
+ *   softmax    dz[s,c] = (exp(z[s,c] - lse_s) - [c == y_s]) / len,  loss = (1/len) sum_s (lse_s - z[s,y_s])
+ *   linear     dW[c,f] = sum_s dz[s,c] feat[s,f],  db[c] = sum_s dz[s,c],  dfeat = dz W
+ *   ReLU       the gradient passes where the output is > 0
+ *   max-pool   (3, stride 2) the gradient of a window goes to its first maximum in (row, column)
+ *              scan order, a NaN counting as a maximum (the forward's and torch's rule).  Windows
+ *              overlap: every source position gathers from the at most 4 windows that cover it.
+ *   GroupNorm  (2 groups, eps 1e-5, biased variance) per (sample, group) of n elements, with
+ *              xh = (x - mean) rstd and gh = dout gamma_c:  dx = rstd (gh - mean(gh) - xh mean(gh xh)),
+ *              dgamma_c = sum dout xh,  dbeta_c = sum dout
+ *   conv       (5 x 5, zero padding 2) weight, bias and data gradients; conv1 has no data gradient
+ *              and its weight gradient reads the input at the first pool's argmax positions
+ * fp32 FMAs only and no floating-point atomics.  Every weight gradient is one fma chain per sample
+ * over the at most h w positions of its map, the samples then added in batch order; the sums of
+ * GroupNorm are fixed trees of one wave.  Two calls on the same inputs give the same bits; a row's
+ * grad and loss bits depend neither on which other rows the call lists nor on how the caller
+ * splits the row list over calls; theta is not written; an inf or NaN in one row's parameters stays
+ * in that row's outputs.  Not bit-identical to ATen's CPU result (another summation order): every
+ * tensor's gradient is within 4 e32 of the float64 gradient relative to that tensor's largest
+ * element, e32 being the same measure of torch's own fp32 autograd on the CPU
+ * (tests/test_gpu_train_gnlenet.py).
+ * Limits (NIIDMIX_EUNSUPPORTED beyond): C <= 1024, Cin <= 4, 15 <= H, W <= 64, b_max <= 2^24,
+ * n_rows <= 2^24, n_rows * ceil(b_max / 2) < 2^31 scratch slots (the scratch size then stays far
+ * inside int64; the size function returns 0 beyond), n_rows * ceil((C F + C) / 256) < 2^31 blocks.
+ * Any ld_t, ld_g >= P, any alignment of theta, grad and data.
+ * Checked before anything touches the GPU, in this order:
+ *   NIIDMIX_EINVAL        a null pointer
+ *   NIIDMIX_EINVAL        n_rows, b_max, Cin, H, W or C < 1
+ *   NIIDMIX_EUNSUPPORTED  C > 1024, Cin > 4, H or W outside [15, 64], b_max or n_rows too large
+ *   NIIDMIX_EINVAL        ld_t < P or ld_g < P
+ *   NIIDMIX_EINVAL        a scratch buffer that is too small or not 8-B aligned
+ *   NIIDMIX_EALIAS        grad, loss or scratch overlaps theta, or grad overlaps scratch, theta and
+ *                         grad taken over the least extent n_rows distinct rows can span,
+ *                         (n_rows - 1) * ld + P elements (the row list is on the device and is not
+ *                         read by the launcher)
+ * batch_idx, batch_len, labels and rows are device data and are NOT checked by the launcher: an
+ * index outside data reads out of bounds (a label outside [0, C) matches no class).
+ * niidmix.train.DeviceTrainer checks them once per node set. */
+int64_t niidmix_gnlenet_nll_grad_rows_scratch_bytes(int64_t n_rows, int64_t b_max, int64_t Cin,
+                                                    int64_t H, int64_t W, int64_t C);
+int niidmix_gnlenet_nll_grad_rows_f32(const float *theta, int64_t ld_t, const float *data,
+                                      const int32_t *labels, const int32_t *batch_idx,
+                                      const int32_t *batch_len, int64_t b_max, const int32_t *rows,
+                                      int64_t n_rows, float *grad, int64_t ld_g, float *loss,
+                                      int64_t Cin, int64_t H, int64_t W, int64_t C, void *scratch,
+                                      int64_t scratch_bytes, void *stream);
+
 /* update_models(all_models, avg) after the 'sample' topology's uniform average (d_sgd.py:240-250,
  * :29-35): every row y_i := fl(fl(x_i * 0) + avg) (p.mul_(0.); p.add_(new)) — avg everywhere
  * except NaN where x_i is non-finite and the sign rule of (+-0) + (+-0) where avg is 0.

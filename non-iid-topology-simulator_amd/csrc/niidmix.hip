@@ -4587,24 +4587,25 @@ __device__ __forceinline__ float gn_wave_sum(float v) {
     return v;
 }
 
-// conv1 + maxpool: in = the tile's samples [Cin, H, W] in global memory (sample s at x0 + s *
-// Cin H W; the caller clamps s to the tile), out [kGnTS, 32, h1, w1] = max over the 3 x 3 window
-// of the conv outputs, plus the bias.
-__device__ __forceinline__ void gn_conv1_pool(const float *__restrict__ x0, int ns, const GnShape &g,
-                                              const float *__restrict__ th, float *out, float *ws) {
+// conv1 + maxpool: in = the tile's samples [Cin, H, W] in global memory (sample s at xof(s), which
+// clamps s to the tile), out [kGnTS, 32, h1, w1] = max over the 3 x 3 window of the conv outputs,
+// plus the bias.  AM: amax [kGnTS, 32, h1, w1] gets the window position (3 row + column) of that
+// maximum, the first one in scan order (gn_max's rule).
+template <bool AM = false, class XOf>
+__device__ __forceinline__ void gn_conv1_pool(XOf xof, const GnShape &g, const float *__restrict__ th,
+                                              float *out, float *ws, unsigned char *amax = nullptr) {
     constexpr int WS = 32 + 4;
     const int tid = threadIdx.x;
     const int nk = g.Cin * 25;
     for (int e = tid; e < 32 * nk; e += 256) ws[(e % nk) * WS + e / nk] = th[g.c1w + e];
     __syncthreads();
     const int hw1 = g.h1 * g.w1, per_g = kGnTS * hw1;
-    const int64_t sample = (int64_t)g.Cin * g.H * g.W;
 #pragma unroll 1
     for (int item = tid; item < 4 * per_g; item += 256) {
         const int ocg = item / per_g, rem = item % per_g;
         const int s = rem / hw1, pos = rem % hw1;
         const int pi = pos / g.w1, pj = pos % g.w1;
-        const float *xs = x0 + (int64_t)(s < ns ? s : 0) * sample;
+        const float *xs = xof(s);
         float acc[9][kGnOT];
 #pragma unroll
         for (int a = 0; a < 9; ++a)
@@ -4645,26 +4646,34 @@ __device__ __forceinline__ void gn_conv1_pool(const float *__restrict__ x0, int 
 #pragma unroll
         for (int o = 0; o < kGnOT; ++o) {
             float m = acc[0][o];
+            int am = 0;
 #pragma unroll
-            for (int a = 1; a < 9; ++a) m = gn_max(m, acc[a][o]);
+            for (int a = 1; a < 9; ++a) {
+                if (AM && (acc[a][o] > m || acc[a][o] != acc[a][o])) am = a;
+                m = gn_max(m, acc[a][o]);
+            }
             const int oc = ocg * kGnOT + o;
             out[(s * 32 + oc) * hw1 + pos] = m + th[g.c1b + oc];
+            if constexpr (AM) amax[(s * 32 + oc) * hw1 + pos] = (unsigned char)am;
         }
     }
     __syncthreads();
 }
 
-// 5 x 5 convolution, 32 -> CO channels, zero padding 2: in [kGnTS, 32, h, w] -> out [kGnTS, CO, h, w]
-// (bias added).  wg: the weights [CO, 32, 5, 5] of the job's row, bg the bias.  Every output is
+// 5 x 5 convolution, CI -> CO channels, zero padding 2: in [kGnTS, CI, h, w] -> out [kGnTS, CO, h, w]
+// (bias added).  wg: the weights [CO, CI, 5, 5] of the job's row, bg the bias.  Every output is
 // one fma chain over (input channel, ky, kx) from 0.
-template <int CO>
+// TR: the data gradient of such a convolution instead, a convolution with the flipped, transposed
+// weights: wg is the forward weight [CI, CO, 5, 5], tap k of (output o, input c) is
+// wg[c][o][24 - k], and there is no bias (bg is not read).
+template <int CO, int CI = 32, bool TR = false>
 __device__ __forceinline__ void gn_conv(const float *in, float *out, int h, int w,
                                         const float *__restrict__ wg, const float *__restrict__ bg,
                                         float *ws) {
     constexpr int ICB = kGnStage / (25 * CO);    // input channels per stage: 8 or 4
     constexpr int KR = ICB * 25;                 // k rows per stage
     constexpr int WS = CO + 4;
-    constexpr int NST = 32 / ICB;
+    constexpr int NST = CI / ICB;
     constexpr int NPRE = kGnStage / 256;
     static_assert(KR * WS <= kGnWFloats && NPRE * 256 == kGnStage, "stage size");
     const int tid = threadIdx.x;
@@ -4695,7 +4704,8 @@ __device__ __forceinline__ void gn_conv(const float *in, float *out, int h, int 
 #pragma unroll
             for (int q = 0; q < NPRE; ++q) {
                 const int e = q * 256 + tid;
-                pre[q] = wg[((e / KR) * 32 + st * ICB) * 25 + e % KR];
+                if constexpr (TR) pre[q] = wg[((st * ICB + (e % KR) / 25) * CO + e / KR) * 25 + 24 - (e % KR) % 25];
+                else pre[q] = wg[((e / KR) * CI + st * ICB) * 25 + e % KR];
             }
         };
         fetch(0);
@@ -4714,7 +4724,7 @@ __device__ __forceinline__ void gn_conv(const float *in, float *out, int h, int 
                 if (base + r * 256 >= n_items) continue;          // block-uniform
 #pragma unroll 1
                 for (int icl = 0; icl < ICB; ++icl) {
-                    const float *ip = in + ((is[r] * 32 + st * ICB + icl) * h) * w;
+                    const float *ip = in + ((is[r] * CI + st * ICB + icl) * h) * w;
 #pragma unroll
                     for (int ky = 0; ky < 5; ++ky) {
                         const int yy = iy[r] + ky - 2;
@@ -4750,10 +4760,12 @@ __device__ __forceinline__ void gn_conv(const float *in, float *out, int h, int 
 #pragma unroll
             for (int o = 0; o < kGnOT; ++o) {
                 const int oc = io[r] * kGnOT + o;
-                const float b = bg[oc];
+                float b = 0.f;
+                if constexpr (!TR) b = bg[oc];
 #pragma unroll
                 for (int p = 0; p < kGnPX; ++p)
-                    if (ix[r] + p < w) out[((is[r] * CO + oc) * h + iy[r]) * w + ix[r] + p] = acc[r][p][o] + b;
+                    if (ix[r] + p < w)
+                        out[((is[r] * CO + oc) * h + iy[r]) * w + ix[r] + p] = TR ? acc[r][p][o] : acc[r][p][o] + b;
             }
         }
     }
@@ -4809,6 +4821,30 @@ __device__ __forceinline__ void gn_norm_pool(const float *in, float *out, int h,
     __syncthreads();
 }
 
+// classifier: feat is [kGnTS, F] in (channel, row, column) order; logits to z [kGnTS, C]
+__device__ __forceinline__ void gn_linear(const float *feat, const GnShape &g, const float *__restrict__ th,
+                                          float *zout) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int c = wave; c < g.C; c += 4) {
+        const float *wr = th + g.fw + (int64_t)c * g.F;
+        float z[kGnTS];
+#pragma unroll
+        for (int s = 0; s < kGnTS; ++s) z[s] = 0.f;
+        for (int f = lane; f < g.F; f += 64) {
+            const float wv = wr[f];
+#pragma unroll
+            for (int s = 0; s < kGnTS; ++s) z[s] = __builtin_fmaf(feat[s * g.F + f], wv, z[s]);
+        }
+        const float b = th[g.fb + c];
+#pragma unroll
+        for (int s = 0; s < kGnTS; ++s) {
+            const float v = gn_wave_sum(z[s]) + b;
+            if (lane == 0) zout[s * g.C + c] = v;
+        }
+    }
+    __syncthreads();
+}
+
 template <bool LDS>
 __global__ __launch_bounds__(256) void k_gnl_eval(const float *__restrict__ theta, int64_t ld_t,
                                                   const float *__restrict__ data,
@@ -4840,7 +4876,8 @@ __global__ __launch_bounds__(256) void k_gnl_eval(const float *__restrict__ thet
         const int64_t s0 = (int64_t)seg_start[job] + (int64_t)t * kGnTS;
         const float *th = theta + (int64_t)rows[job] * ld_t;
 
-        gn_conv1_pool(data + s0 * sample, ns, g, th, buf_a, ws);
+        const float *x0 = data + s0 * sample;
+        gn_conv1_pool([&](int s) { return x0 + (int64_t)(s < ns ? s : 0) * sample; }, g, th, buf_a, ws);
         gn_stats<32>(buf_a, hw1, th + g.g1w, th + g.g1b, stat);
         for (int e = tid; e < a1; e += 256)
             buf_a[e] = gn_relu(__builtin_fmaf(buf_a[e], stat[16 + 2 * (e / hw1)], stat[16 + 2 * (e / hw1) + 1]));
@@ -4852,26 +4889,7 @@ __global__ __launch_bounds__(256) void k_gnl_eval(const float *__restrict__ thet
         gn_stats<64>(buf_b, g.h2 * g.w2, th + g.g3w, th + g.g3b, stat);
         gn_norm_pool<64>(buf_b, buf_a, g.h2, g.w2, g.h3, g.w3, stat);
 
-        // classifier: buf_a is [kGnTS, F] in (channel, row, column) order; logits to ws [kGnTS, C]
-        const int wave = tid >> 6, lane = tid & 63;
-        for (int c = wave; c < g.C; c += 4) {
-            const float *wr = th + g.fw + (int64_t)c * g.F;
-            float z[kGnTS];
-#pragma unroll
-            for (int s = 0; s < kGnTS; ++s) z[s] = 0.f;
-            for (int f = lane; f < g.F; f += 64) {
-                const float wv = wr[f];
-#pragma unroll
-                for (int s = 0; s < kGnTS; ++s) z[s] = __builtin_fmaf(buf_a[s * g.F + f], wv, z[s]);
-            }
-            const float b = th[g.fb + c];
-#pragma unroll
-            for (int s = 0; s < kGnTS; ++s) {
-                const float v = gn_wave_sum(z[s]) + b;
-                if (lane == 0) ws[s * g.C + c] = v;
-            }
-        }
-        __syncthreads();
+        gn_linear(buf_a, g, th, ws);
         if (logits)
             for (int e = tid; e < ns * g.C; e += 256)
                 logits[(job * ld_logits + (int64_t)t * kGnTS) * g.C + e] = ws[e];
@@ -4895,6 +4913,322 @@ __global__ __launch_bounds__(256) void k_gnl_eval(const float *__restrict__ thet
             part_cnt[wk] = c;
         }
         __syncthreads();                                              // ws, stat and the buffers are free
+    }
+}
+
+// ----------------------------------------------------------------------------------------------
+// Local training of GN-LeNet on listed rows (niidmix_gnlenet_nll_grad_rows_f32): the gradient of
+// F.nll_loss(model.forward(x), y) on a zeroed gradient, the forward being k_gnl_eval's.
+//   k_gnl_grad_sample   one workgroup per (row, tile of kGnTS samples).  The forward functions above
+//                       run on the batch's gathered samples with every activation buffer in the
+//                       tile's scratch slot (the backward needs them there in any case, so there is
+//                       no LDS variant and no size-dependent path), then the sample-local backward
+//                       chain: dz, the feature gradient, and per stage max-pool / ReLU, GroupNorm
+//                       and the convolution's data gradient (gn_conv<.., TR>).  The pool's backward
+//                       is a gather: a source position adds the output gradients of the at most 4
+//                       windows that cover it and whose first maximum (gn_max's rule, recomputed
+//                       from the same fmas as the forward) it is.  No atomics.
+//   k_gnl_grad_conv     one workgroup per (row, convolution output channel): the weight gradient of
+//                       its [CI, 5, 5] filter, the bias gradient and the channel's two GroupNorm
+//                       gradients.  Per sample one fma chain over the <= h w positions, the samples
+//                       then added in batch order.  conv1 reads the input at the argmax positions.
+//   k_gnl_grad_fc       a lane per classifier weight: one fma chain over the samples in batch order;
+//                       the bias; the mean loss.
+// Every value is a fixed-order chain or tree of one workgroup over one row's own data.
+struct GnGradLay {     // float offsets in a tile's scratch slot; every array is [kGnTS, ...]
+    int p1, x2, y2, dy2, dx2;     // [32, h1, w1]: pooled conv1, conv2's input, conv2's output, gradients
+    int x3, dx3, y3, dy3;         // [32, h2, w2] conv3's input, [64, h2, w2] its output, gradients
+    int feat, dfeat;              // [F]
+    int st1, st2, st3;            // gn_stats' stat array of each stage (kGnStat floats)
+    int gp1, gp2, gp3;            // [CO, 2]: per-sample (dgamma, dbeta)
+    int dz, nll;                  // [C], [1]
+    int amax;                     // bytes [32, h1, w1]: the first pool's argmax
+    int tile;                     // floats per slot
+};
+
+inline GnGradLay gn_grad_lay(const GnShape &g) {
+    GnGradLay L;
+    int o = 0;
+    auto take = [&](int n) { const int r = o; o += (n + 3) / 4 * 4; return r; };
+    const int a1 = kGnTS * 32 * g.h1 * g.w1, a2 = kGnTS * 32 * g.h2 * g.w2;
+    L.p1 = take(a1); L.x2 = take(a1); L.y2 = take(a1); L.dy2 = take(a1); L.dx2 = take(a1);
+    L.x3 = take(a2); L.dx3 = take(a2); L.y3 = take(2 * a2); L.dy3 = take(2 * a2);
+    L.feat = take(kGnTS * g.F); L.dfeat = take(kGnTS * g.F);
+    L.st1 = take(kGnStat); L.st2 = take(kGnStat); L.st3 = take(kGnStat);
+    L.gp1 = take(kGnTS * 64); L.gp2 = take(kGnTS * 64); L.gp3 = take(kGnTS * 128);
+    L.dz = take(kGnTS * g.C); L.nll = take(kGnTS);
+    L.amax = take((a1 + 3) / 4);
+    L.tile = o;                                   // < 2^19 floats at 64 x 64, C 1024
+    return L;
+}
+
+// Backward of relu(maxpool(3, 2)(y * scale + shift)): dn [kGnTS, CO, h, w] = the gradient with
+// respect to the normalised map, gathered per source position.  pooled is the forward's output
+// (after ReLU), dout its gradient, st the stage's saved stat array.
+template <int CO>
+__device__ __forceinline__ void gn_pool_bwd(const float *y, const float *pooled, const float *dout,
+                                            float *dn, int h, int w, int ho, int wo, const float *st) {
+    for (int e = threadIdx.x; e < kGnTS * CO * h * w; e += 256) {
+        const int x = e % w, yy = (e / w) % h, sc = e / (w * h);
+        const float scale = st[16 + 2 * sc], shift = st[16 + 2 * sc + 1];
+        const int i0 = yy < 2 ? 0 : (yy - 1) / 2, i1 = yy / 2 < ho - 1 ? yy / 2 : ho - 1;
+        const int j0 = x < 2 ? 0 : (x - 1) / 2, j1 = x / 2 < wo - 1 ? x / 2 : wo - 1;
+        float acc = 0.f;
+        for (int i = i0; i <= i1; ++i)
+            for (int j = j0; j <= j1; ++j) {
+                if (pooled[(sc * ho + i) * wo + j] <= 0.f) continue;     // ReLU; a NaN passes
+                const float *p = y + (sc * h + 2 * i) * w + 2 * j;
+                float m = __builtin_fmaf(p[0], scale, shift);
+                int am = 0;
+#pragma unroll
+                for (int a = 1; a < 9; ++a) {
+                    const float v = __builtin_fmaf(p[(a / 3) * w + a % 3], scale, shift);
+                    if (v > m || v != v) { m = v; am = a; }
+                }
+                if (am == (yy - 2 * i) * 3 + (x - 2 * j)) acc += dout[(sc * ho + i) * wo + j];
+            }
+        dn[e] = acc;
+    }
+    __syncthreads();
+}
+
+// Backward of GroupNorm(2, CO): dn [kGnTS, CO, hw] holds the gradient of the normalised map and
+// receives that of the input y.  gp [kGnTS, CO, 2] gets the sample's (dgamma, dbeta); red: 4 kGnTS
+// floats of LDS.  With xh = (y - mean) rstd, gh = dn gamma:
+//   dy = rstd (gh - mean(gh) - xh mean(gh xh)), the means over the (sample, group).
+template <int CO>
+__device__ __forceinline__ void gn_norm_bwd(const float *y, float *dn, int hw,
+                                            const float *__restrict__ gw, const float *st, float *gp,
+                                            float *red) {
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    for (int sc = wave; sc < kGnTS * CO; sc += 4) {       // a wave per (sample, channel)
+        const int pair = (sc / CO) * 2 + (sc % CO) / (CO / 2);
+        const float mean = st[pair * 2], rstd = st[pair * 2 + 1];
+        float a = 0.f, b = 0.f;
+        for (int i = lane; i < hw; i += 64) {
+            const float d = dn[sc * hw + i];
+            a += d;
+            b = __builtin_fmaf(d, (y[sc * hw + i] - mean) * rstd, b);
+        }
+        a = gn_wave_sum(a);
+        b = gn_wave_sum(b);
+        if (lane == 0) { gp[2 * sc] = b; gp[2 * sc + 1] = a; }
+    }
+    __syncthreads();
+    if (tid < kGnTS * 2) {                                // a lane per (sample, group)
+        const int s = tid / 2, c0 = (tid % 2) * (CO / 2);
+        float a = 0.f, b = 0.f;
+        for (int c = c0; c < c0 + CO / 2; ++c) {
+            a = __builtin_fmaf(gw[c], gp[2 * (s * CO + c) + 1], a);
+            b = __builtin_fmaf(gw[c], gp[2 * (s * CO + c)], b);
+        }
+        const float n = (float)((CO / 2) * hw);
+        red[2 * tid] = a / n;
+        red[2 * tid + 1] = b / n;
+    }
+    __syncthreads();
+    for (int e = tid; e < kGnTS * CO * hw; e += 256) {
+        const int sc = e / hw, c = sc % CO, pair = (sc / CO) * 2 + c / (CO / 2);
+        const float rstd = st[pair * 2 + 1];
+        const float xh = (y[e] - st[pair * 2]) * rstd;
+        dn[e] = rstd * ((dn[e] * gw[c] - red[2 * pair]) - xh * red[2 * pair + 1]);
+    }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(256) void k_gnl_grad_sample(const float *__restrict__ theta, int64_t ld_t,
+                                                         const float *__restrict__ data,
+                                                         const int32_t *__restrict__ labels,
+                                                         const int32_t *__restrict__ batch_idx,
+                                                         const int32_t *__restrict__ batch_len, int b_max,
+                                                         const int32_t *__restrict__ rows, int64_t n_rows,
+                                                         int n_tiles, const GnShape g, const GnGradLay L,
+                                                         float *scratch) {
+    extern __shared__ __attribute__((aligned(16))) float gn_smem[];
+    __shared__ float lse[kGnTS];
+    __shared__ int ys[kGnTS];
+    float *ws = gn_smem, *stat = gn_smem + kGnWFloats;
+    const int tid = threadIdx.x;
+    const int hw1 = g.h1 * g.w1, hw2 = g.h2 * g.w2, a1 = kGnTS * 32 * hw1;
+    const int64_t n_work = n_rows * n_tiles, sample = (int64_t)g.Cin * g.H * g.W;
+    for (int64_t wk = blockIdx.x; wk < n_work; wk += gridDim.x) {       // wk = row entry * n_tiles + tile
+        const int64_t i = wk / n_tiles;
+        const int t = (int)(wk % n_tiles);
+        const int len = lin_len(batch_len, i, b_max), left = len - t * kGnTS;
+        if (left <= 0) continue;                                      // block-uniform
+        const int ns = left < kGnTS ? left : kGnTS;
+        const float *th = theta + (int64_t)rows[i] * ld_t;
+        const int32_t *bi = batch_idx + i * b_max + t * kGnTS;
+        float *T = scratch + wk * L.tile;
+        auto save_stat = [&](int off) {
+            for (int e = tid; e < kGnStat; e += 256) T[off + e] = stat[e];
+        };
+
+        // forward, every map kept
+        gn_conv1_pool<true>([&](int s) { return data + (int64_t)bi[s < ns ? s : 0] * sample; }, g, th,
+                            T + L.p1, ws, reinterpret_cast<unsigned char *>(T + L.amax));
+        gn_stats<32>(T + L.p1, hw1, th + g.g1w, th + g.g1b, stat);
+        save_stat(L.st1);
+        for (int e = tid; e < a1; e += 256)
+            T[L.x2 + e] = gn_relu(__builtin_fmaf(T[L.p1 + e], stat[16 + 2 * (e / hw1)], stat[16 + 2 * (e / hw1) + 1]));
+        __syncthreads();
+        gn_conv<32>(T + L.x2, T + L.y2, g.h1, g.w1, th + g.c2w, th + g.c2b, ws);
+        gn_stats<32>(T + L.y2, hw1, th + g.g2w, th + g.g2b, stat);
+        save_stat(L.st2);
+        gn_norm_pool<32>(T + L.y2, T + L.x3, g.h1, g.w1, g.h2, g.w2, stat);
+        gn_conv<64>(T + L.x3, T + L.y3, g.h2, g.w2, th + g.c3w, th + g.c3b, ws);
+        gn_stats<64>(T + L.y3, hw2, th + g.g3w, th + g.g3b, stat);
+        save_stat(L.st3);
+        gn_norm_pool<64>(T + L.y3, T + L.feat, g.h2, g.w2, g.h3, g.w3, stat);
+        gn_linear(T + L.feat, g, th, ws);
+
+        // loss and dz = (softmax(z) - onehot(y)) / len; the tile's unused samples get 0
+        if (tid < ns) {
+            const int y = labels[bi[tid]];
+            EvState q;
+            ev_scan(ws + tid * g.C, g.C, 0, y, true, q);
+            const float l = q.best + logf(q.sum);
+            lse[tid] = l;
+            ys[tid] = y;
+            T[L.nll + tid] = l - q.zy;
+        }
+        __syncthreads();
+        const float flen = (float)len;
+        for (int e = tid; e < kGnTS * g.C; e += 256) {
+            const int s = e / g.C, c = e % g.C;
+            const float dz = s < ns ? (expf(ws[e] - lse[s]) - (c == ys[s] ? 1.f : 0.f)) / flen : 0.f;
+            ws[e] = dz;
+            T[L.dz + e] = dz;
+        }
+        __syncthreads();
+        for (int e = tid; e < kGnTS * g.F; e += 256) {                // the feature gradient
+            const int s = e / g.F, f = e % g.F;
+            const float *wc = th + g.fw + f;
+            float acc = 0.f;
+            for (int c = 0; c < g.C; ++c) acc = __builtin_fmaf(ws[s * g.C + c], wc[(int64_t)c * g.F], acc);
+            T[L.dfeat + e] = acc;
+        }
+        __syncthreads();
+
+        gn_pool_bwd<64>(T + L.y3, T + L.feat, T + L.dfeat, T + L.dy3, g.h2, g.w2, g.h3, g.w3, T + L.st3);
+        gn_norm_bwd<64>(T + L.y3, T + L.dy3, hw2, th + g.g3w, T + L.st3, T + L.gp3, stat);
+        gn_conv<32, 64, true>(T + L.dy3, T + L.dx3, g.h2, g.w2, th + g.c3w, nullptr, ws);
+        gn_pool_bwd<32>(T + L.y2, T + L.x3, T + L.dx3, T + L.dy2, g.h1, g.w1, g.h2, g.w2, T + L.st2);
+        gn_norm_bwd<32>(T + L.y2, T + L.dy2, hw1, th + g.g2w, T + L.st2, T + L.gp2, stat);
+        gn_conv<32, 32, true>(T + L.dy2, T + L.dx2, g.h1, g.w1, th + g.c2w, nullptr, ws);
+        for (int e = tid; e < a1; e += 256)
+            if (T[L.x2 + e] <= 0.f) T[L.dx2 + e] = 0.f;               // ReLU; a NaN passes
+        __syncthreads();
+        gn_norm_bwd<32>(T + L.p1, T + L.dx2, hw1, th + g.g1w, T + L.st1, T + L.gp1, stat);
+    }
+}
+
+constexpr int kGnMaxHW1 = ((kGnMaxHW - 3) / 2 + 1) * ((kGnMaxHW - 3) / 2 + 1);     // 31 x 31
+
+__global__ __launch_bounds__(256) void k_gnl_grad_conv(const float *__restrict__ data,
+                                                       const int32_t *__restrict__ batch_idx,
+                                                       const int32_t *__restrict__ batch_len, int b_max,
+                                                       const int32_t *__restrict__ rows, int n_tiles,
+                                                       const GnShape g, const GnGradLay L,
+                                                       const float *__restrict__ scratch,
+                                                       float *__restrict__ grad, int64_t ld_g) {
+    __shared__ float dys[kGnMaxHW1];
+    __shared__ unsigned char ams[kGnMaxHW1 + 3];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int64_t i = blockIdx.x / 128;
+    const int ch = (int)(blockIdx.x % 128);
+    const int layer = ch < 32 ? 1 : ch < 64 ? 2 : 3;
+    const int oc = layer == 1 ? ch : layer == 2 ? ch - 32 : ch - 64;
+    const int CO = layer == 3 ? 64 : 32, CI = layer == 1 ? g.Cin : 32;
+    const int h = layer == 3 ? g.h2 : g.h1, w = layer == 3 ? g.w2 : g.w1, hw = h * w;
+    const int nel = CI * 25;
+    const int o_dy = layer == 1 ? L.dx2 : layer == 2 ? L.dy2 : L.dy3;
+    const int o_x = layer == 2 ? L.x2 : L.x3, o_gp = layer == 1 ? L.gp1 : layer == 2 ? L.gp2 : L.gp3;
+    const int len = lin_len(batch_len, i, b_max);
+    const int64_t sample = (int64_t)g.Cin * g.H * g.W;
+    float tot[4] = {0.f, 0.f, 0.f, 0.f}, btot = 0.f;
+    for (int s = 0; s < len; ++s) {                                   // the samples in batch order
+        const float *T = scratch + (i * n_tiles + s / kGnTS) * L.tile;
+        const int sl = s % kGnTS;
+        __syncthreads();                                              // the last sample has been read
+        for (int p = tid; p < hw; p += 256) {
+            dys[p] = T[o_dy + (sl * CO + oc) * hw + p];
+            if (layer == 1) ams[p] = reinterpret_cast<const unsigned char *>(T + L.amax)[(sl * 32 + oc) * hw + p];
+        }
+        __syncthreads();
+        if (wave == 3) {                                              // the bias: lanes stride the map
+            float a = 0.f;
+            for (int p = lane; p < hw; p += 64) a += dys[p];
+            btot += gn_wave_sum(a);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int e = tid + 256 * q;
+            if (e >= nel) continue;
+            const int ic = e / 25, ky = (e % 25) / 5, kx = e % 5;
+            float acc = 0.f;
+            if (layer == 1) {                                         // the input at the argmax positions
+                const float *xin = data + (int64_t)batch_idx[i * b_max + s] * sample + (int64_t)ic * g.H * g.W;
+                for (int p = 0; p < hw; ++p) {
+                    const int a = ams[p];
+                    const int yy = 2 * (p / w) + a / 3 + ky - 2, xx = 2 * (p % w) + a % 3 + kx - 2;
+                    if ((unsigned)yy < (unsigned)g.H && (unsigned)xx < (unsigned)g.W)
+                        acc = __builtin_fmaf(dys[p], xin[yy * g.W + xx], acc);
+                }
+            } else {
+                const float *xin = T + o_x + (sl * 32 + ic) * hw;
+                const int y0 = ky < 2 ? 2 - ky : 0, y1 = ky > 2 ? h + 2 - ky : h;
+                const int x0 = kx < 2 ? 2 - kx : 0, x1 = kx > 2 ? w + 2 - kx : w;
+                for (int y = y0; y < y1; ++y)
+                    for (int x = x0; x < x1; ++x)
+                        acc = __builtin_fmaf(dys[y * w + x], xin[(y + ky - 2) * w + x + kx - 2], acc);
+            }
+            tot[q] += acc;
+        }
+    }
+    float *gr = grad + (int64_t)rows[i] * ld_g;
+    const int o_w = layer == 1 ? g.c1w : layer == 2 ? g.c2w : g.c3w;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+        if (tid + 256 * q < nel) gr[o_w + oc * nel + tid + 256 * q] = tot[q];
+    if (tid == 192) gr[o_w + CO * nel + oc] = btot;                   // the bias follows its weight
+    if (tid == 0) {                                                   // GroupNorm's weight and bias
+        float dg = 0.f, db = 0.f;
+        for (int s = 0; s < len; ++s) {
+            const float *gp = scratch + (i * n_tiles + s / kGnTS) * L.tile + o_gp + 2 * ((s % kGnTS) * CO + oc);
+            dg += gp[0];
+            db += gp[1];
+        }
+        gr[o_w + CO * nel + CO + oc] = dg;
+        gr[o_w + CO * nel + 2 * CO + oc] = db;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_gnl_grad_fc(const int32_t *__restrict__ batch_len, int b_max,
+                                                     const int32_t *__restrict__ rows, int n_tiles,
+                                                     int n_blk, const GnShape g, const GnGradLay L,
+                                                     const float *__restrict__ scratch,
+                                                     float *__restrict__ grad, int64_t ld_g,
+                                                     float *__restrict__ loss) {
+    const int64_t i = blockIdx.x / n_blk;
+    const int e = (int)(blockIdx.x % n_blk) * 256 + threadIdx.x;
+    const int len = lin_len(batch_len, i, b_max), nw = g.C * g.F;
+    const float *T0 = scratch + i * n_tiles * L.tile;
+    float *gr = grad + (int64_t)rows[i] * ld_g;
+    if (e < nw + g.C) {
+        const int c = e < nw ? e / g.F : e - nw, f = e % g.F;
+        float acc = 0.f;
+        for (int s = 0; s < len; ++s) {
+            const float *T = T0 + (int64_t)(s / kGnTS) * L.tile;
+            const float dz = T[L.dz + (s % kGnTS) * g.C + c];
+            acc = e < nw ? __builtin_fmaf(dz, T[L.feat + (s % kGnTS) * g.F + f], acc) : acc + dz;
+        }
+        gr[g.fw + e] = acc;
+    }
+    if (e == 0) {                                                     // the mean loss, in batch order
+        float a = 0.f;
+        for (int s = 0; s < len; ++s) a += T0[(int64_t)(s / kGnTS) * L.tile + L.nll + s % kGnTS];
+        loss[i] = a / (float)len;
     }
 }
 
@@ -6194,6 +6528,72 @@ int niidmix_gnlenet_eval_rows_f32(const float *theta, int64_t ld_t, const float 
                        seg_len, n_jobs, (int)max_len, (int)n_tiles, (const double *)part_loss,
                        (const int32_t *)part_cnt, loss_sum, correct);
     return check_launch("k_lin_eval_sum");
+}
+
+constexpr int64_t kGnGradMaxB = 1 << 24, kGnGradMaxRows = 1 << 24;
+
+// the gradient entry's size limits: int32 sample positions, 128 n_rows blocks, and fewer than 2^31
+// (row, tile) slots, so that the scratch size (< 2^21 bytes per slot) stays far inside int64
+static bool gn_grad_fits(int64_t n_rows, int64_t b_max) {
+    return b_max <= kGnGradMaxB && n_rows <= kGnGradMaxRows && n_rows * gn_tiles(b_max) <= 0x7fffffff;
+}
+
+int64_t niidmix_gnlenet_nll_grad_rows_scratch_bytes(int64_t n_rows, int64_t b_max, int64_t Cin, int64_t H,
+                                                    int64_t W, int64_t C) {
+    if (n_rows <= 0 || b_max <= 0 || !gn_grad_fits(n_rows, b_max) || !gn_supported(Cin, H, W, C)) return 0;
+    const GnShape g = gn_shape((int)Cin, (int)H, (int)W, (int)C);
+    // a slot per (row, tile of kGnTS samples): < 2^31 slots of < 2^21 bytes
+    return n_rows * gn_tiles(b_max) * gn_grad_lay(g).tile * 4;
+}
+
+int niidmix_gnlenet_nll_grad_rows_f32(const float *theta, int64_t ld_t, const float *data,
+                                      const int32_t *labels, const int32_t *batch_idx,
+                                      const int32_t *batch_len, int64_t b_max, const int32_t *rows,
+                                      int64_t n_rows, float *grad, int64_t ld_g, float *loss,
+                                      int64_t Cin, int64_t H, int64_t W, int64_t C, void *scratch,
+                                      int64_t scratch_bytes, void *stream) {
+    if (!theta || !data || !labels || !batch_idx || !batch_len || !rows || !grad || !loss || !scratch)
+        return set_error(NIIDMIX_EINVAL, "null pointer");
+    if (n_rows <= 0 || b_max <= 0 || Cin <= 0 || H <= 0 || W <= 0 || C <= 0)
+        return set_error(NIIDMIX_EINVAL, "n_rows, b_max, Cin, H, W and C must be >= 1");
+    if (C > kLinMaxC) return set_error(NIIDMIX_EUNSUPPORTED, "C %lld > %lld", (long long)C, (long long)kLinMaxC);
+    if (Cin > kGnMaxCin) return set_error(NIIDMIX_EUNSUPPORTED, "Cin %lld > %d", (long long)Cin, kGnMaxCin);
+    if (!gn_supported(Cin, H, W, C))
+        return set_error(NIIDMIX_EUNSUPPORTED, "H %lld, W %lld: the kernel holds %d <= H, W <= %d",
+                         (long long)H, (long long)W, kGnMinHW, kGnMaxHW);
+    if (b_max > kGnGradMaxB)
+        return set_error(NIIDMIX_EUNSUPPORTED, "b_max %lld > 2^24", (long long)b_max);
+    const GnShape g = gn_shape((int)Cin, (int)H, (int)W, (int)C);
+    const int64_t n_blk = (g.C * (int64_t)g.F + g.C + 255) / 256;
+    if (!gn_grad_fits(n_rows, b_max) || n_rows * n_blk > 0x7fffffff)
+        return set_error(NIIDMIX_EUNSUPPORTED, "n_rows %lld x b_max %lld: too many blocks or scratch slots",
+                         (long long)n_rows, (long long)b_max);
+    if (int rc = check_ld(ld_t, ld_g, g.P, "P")) return rc;
+    const int64_t need = niidmix_gnlenet_nll_grad_rows_scratch_bytes(n_rows, b_max, Cin, H, W, C);
+    if (scratch_bytes < need || (reinterpret_cast<uintptr_t>(scratch) & 7u))
+        return set_error(NIIDMIX_EINVAL, "scratch of %lld bytes (8-B aligned), %lld needed",
+                         (long long)scratch_bytes, (long long)need);
+    // `rows` lives on the device: n_rows distinct rows reach at least row n_rows - 1
+    float *sc = reinterpret_cast<float *>(scratch);
+    const int64_t t_ext = slab_extent(n_rows, ld_t, g.P);
+    if (int rc = check_overlap(theta, ld_t, grad, ld_g, n_rows, g.P, "theta and grad overlap")) return rc;
+    if (overlaps(loss, n_rows, theta, t_ext) || overlaps(sc, need / 4, theta, t_ext))
+        return set_error(NIIDMIX_EALIAS, "loss or scratch overlaps theta");
+    if (overlaps(sc, need / 4, grad, slab_extent(n_rows, ld_g, g.P)))
+        return set_error(NIIDMIX_EALIAS, "scratch overlaps grad");
+    const GnGradLay L = gn_grad_lay(g);
+    const int64_t n_tiles = gn_tiles(b_max), n_work = n_rows * n_tiles;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(k_gnl_grad_sample, dim3((unsigned)(n_work < kGnMaxGrid ? n_work : kGnMaxGrid)),
+                       dim3(256), (size_t)gn_lds_bytes_global(), s, theta, ld_t, data, labels, batch_idx,
+                       batch_len, (int)b_max, rows, n_rows, (int)n_tiles, g, L, sc);
+    if (int rc = check_launch("k_gnl_grad_sample")) return rc;
+    hipLaunchKernelGGL(k_gnl_grad_conv, dim3((unsigned)(n_rows * 128)), dim3(256), 0, s, data, batch_idx,
+                       batch_len, (int)b_max, rows, (int)n_tiles, g, L, (const float *)sc, grad, ld_g);
+    if (int rc = check_launch("k_gnl_grad_conv")) return rc;
+    hipLaunchKernelGGL(k_gnl_grad_fc, dim3((unsigned)(n_rows * n_blk)), dim3(256), 0, s, batch_len,
+                       (int)b_max, rows, (int)n_tiles, (int)n_blk, g, L, (const float *)sc, grad, ld_g, loss);
+    return check_launch("k_gnl_grad_fc");
 }
 
 int niidmix_update_rows_f32(const float *x, int64_t ld_x, float *y, int64_t ld_y, int64_t n_rows,

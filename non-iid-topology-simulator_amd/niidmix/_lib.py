@@ -101,6 +101,10 @@ SIGNATURES = {
     "niidmix_gnlenet_eval_rows_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64,
                                                      _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64,
                                                      _i64, _vp, _i64, _vp]),
+    "niidmix_gnlenet_nll_grad_rows_scratch_bytes": (_i64, [_i64, _i64, _i64, _i64, _i64, _i64]),
+    "niidmix_gnlenet_nll_grad_rows_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64,
+                                                         _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp,
+                                                         _i64, _vp]),
     "niidmix_sharded_create": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.POINTER(_vp)]),
     "niidmix_sharded_destroy": (ctypes.c_int, [_vp]),
     "niidmix_sharded_is_loopback": (ctypes.c_int, [_vp]),

@@ -20,7 +20,8 @@ NIIDMIX_MODE environment variable):
 Gradient averaging (--clique-gradient, --unbiased-gradient) also runs on the GPU, bit-identical
 (niidmix.gradient); local training, optimizer steps and sampling stay on the CPU as in the reference.
 With --device-training (params['algorithm']['device-training'], opt-in) a linear model's local
-training runs on the device too: gradient, step and mixing never leave HBM (niidmix.train).
+training runs on the device too: gradient, step and mixing never leave HBM (niidmix.train);
+--device-training-gn-lenet does the same for GN-LeNet models.
 With --device-evaluation (params['algorithm']['device-evaluation'], opt-in) the logger's accuracy
 and loss events of linear and GN-LeNet models are computed on the device as well (niidmix.evaluate).
 """
@@ -1097,9 +1098,15 @@ def main(argv=None):
     ap.add_argument("--mixing-mode", choices=["exact", "fast"], default="exact",
                     help="exact: bit-identical to the reference loop; fast: clique/MFMA kernels")
     ap.add_argument("--device-training", action="store_const", const=True, default=False,
-                    help="linear models only: local training (forward, loss, backward), the SGD step "
-                         "and the mixing all run on the device; same samples as the CPU path, "
-                         "gradients within 1e-5 (condition-aware) of it, not bit-identical")
+                    help="linear models only (GN-LeNet: --device-training-gn-lenet): local training "
+                         "(forward, loss, backward), the SGD step and the mixing all run on the "
+                         "device; same samples as the CPU path, gradients within 1e-5 "
+                         "(condition-aware) of it, not bit-identical")
+    ap.add_argument("--device-training-gn-lenet", action="store_const", const=True, default=False,
+                    help="--device-training for GN-LeNet models as well as linear ones (sets both "
+                         "keys): forward, loss and backward of every node in HIP kernels; same "
+                         "samples as the CPU path, gradients within 4 x the error of torch's own "
+                         "fp32 autograd, not bit-identical")
     ap.add_argument("--device-evaluation", action="store_const", const=True, default=False,
                     help="linear models only: the logger's train, test, validation and full-train "
                          "accuracy and loss of every logged node (and of the global model) are "
@@ -1127,7 +1134,8 @@ def main(argv=None):
         "batch-size": args.batch_size, "initial-averaging": args.initial_averaging,
         "clique-gradient": args.clique_gradient, "unbiased-gradient": args.unbiased_gradient,
         "mixing-mode": args.mixing_mode, "deferred-writeback": args.deferred_writeback,
-        **({"device-training": True} if args.device_training else {}),
+        **({"device-training": True} if args.device_training or args.device_training_gn_lenet else {}),
+        **({"device-training-gn-lenet": True} if args.device_training_gn_lenet else {}),
         **({"device-evaluation": True} if args.device_evaluation else {}),
     })
     if args.rundir is None:

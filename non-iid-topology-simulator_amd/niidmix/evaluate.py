@@ -7,7 +7,8 @@ tools/simulate/run_logger.py).  For the reference's linear model (setup/model/li
 nn.Linear(K, C), log_softmax) DeviceEvaluator computes the same numbers in one kernel call per
 set for all nodes at once (niidmix::linear_eval_rows):
 
-    parameters   a live DeviceTrainer's device slab, read in place (--device-training; no upload),
+    parameters   a live DeviceTrainer's device slab, read in place (--device-training and
+                 --device-training-gn-lenet; no upload),
                  else the models' parameters stacked and uploaded once per call
     sets         materialised once as [M, K] fp32 + int32 labels in HBM (register_sets); the
                  nodes' own train-sets are the trainer's when one is live
@@ -38,7 +39,7 @@ FLAG = "--device-evaluation"
 CHUNK = 1000          # Logger.log_train_accuracy's DataLoader batch size (logger.py:217)
 SET_NAMES = ("valid", "test", "full-train")
 # the GN-LeNet kernel's limits (include/niidmix.h)
-GN_MAX_CIN, GN_MIN_HW, GN_MAX_HW = 4, 15, 64
+GN_MAX_CIN, GN_MIN_HW, GN_MAX_HW = train.GN_MAX_CIN, train.GN_MIN_HW, train.GN_MAX_HW
 SCRATCH_FRACTION = 0.8   # of the free HBM, for one call's scratch (DeviceTrainer._check_fit's rule)
 
 
@@ -73,29 +74,8 @@ def fold_chunks(n_nodes, node, length, loss_sum, correct):
     return [(t[0] / t[1], t[2] / t[3]) if t[1] else (0.0, 0.0) for t in tot]
 
 
-def gn_lenet_shape(model):
-    """(Cin, C, F) when the model's parameters are exactly GN-LeNet's 14 tensors in registration
-    order (include/niidmix.h, niidmix_gnlenet_eval_rows_f32), fp32 and trainable, else None."""
-    ps = list(model.parameters())
-    if len(ps) != 14 or ps[0].dim() != 4 or ps[12].dim() != 2:
-        return None
-    if any(q.dtype != torch.float32 or not q.requires_grad for q in ps):
-        return None
-    cin, (c, f) = int(ps[0].shape[1]), (int(v) for v in ps[12].shape)
-    want = [(32, cin, 5, 5), (32,), (32,), (32,), (32, 32, 5, 5), (32,), (32,), (32,),
-            (64, 32, 5, 5), (64,), (64,), (64,), (c, f), (c,)]
-    if [tuple(q.shape) for q in ps] != want or cin < 1 or f < 64 or f % 64:
-        return None
-    return cin, c, f
-
-
-def gn_lenet_offsets(cin, c, f):
-    """Start of each of the 14 tensors in a flattened row, and P at the end (15 values)."""
-    sizes = [800 * cin, 32, 32, 32, 25600, 32, 32, 32, 51200, 64, 64, 64, c * f, c]
-    out = [0]
-    for v in sizes:
-        out.append(out[-1] + v)
-    return out
+# GN-LeNet's shape helpers live in niidmix.train (which this module imports); the names stay here
+gn_lenet_shape, gn_lenet_offsets = train.gn_lenet_shape, train.gn_lenet_offsets
 
 
 def check_eligible(nodes, params):
@@ -285,22 +265,18 @@ class DeviceEvaluator:
         from . import d_sgd
         spec = _shape(models)
         kind, shape = spec
-        if kind == "linear":
-            k, c = shape
-            p = c * k + c
-            hit = d_sgd.device_trainer(models)
-            if hit is not None:
-                tr, rows = hit
-                if self.device is None or tr.device == self.device:
-                    cur = tr.current()
-                    if cur is not None:
-                        self.device = tr.device
-                        self.last_source = "trainer"
-                        return cur, rows, spec, None
-        else:
+        p = shape[1] * shape[0] + shape[1] if kind == "linear" else gn_lenet_offsets(*shape)[-1]
+        hit = d_sgd.device_trainer(models)           # a live trainer's slab, of either kind
+        if hit is not None and hit[0].p == p:
+            tr, rows = hit
+            if self.device is None or tr.device == self.device:
+                cur = tr.current()
+                if cur is not None:
+                    self.device = tr.device
+                    self.last_source = "trainer"
+                    return cur, rows, spec, None
+        if kind != "linear":
             from . import logger as nl
-            cin, c, f = shape
-            p = gn_lenet_offsets(cin, c, f)[-1]
             hit = nl._fresh_resident(models)
             if hit is not None and len(hit[0].parts) == 1 and hit[0].p == p:
                 pt = hit[0].parts[0]

@@ -28,6 +28,9 @@ Ops (registered in the `niidmix` namespace, usable as torch.ops.niidmix.*):
                    K, C)                            k_lin_eval + k_lin_eval_sum (summed loss, correct
                                                     count and predictions of a linear model per
                                                     (row, sample segment), --device-evaluation)
+  gnlenet_nll_grad_rows(theta, data, labels, batch_idx, batch_len, rows, grad, loss, Cin, H, W, C)
+                                                    k_gnl_grad_sample + k_gnl_grad_conv + k_gnl_grad_fc
+                                                    (the same for GN-LeNet, --device-training-gn-lenet)
   gnlenet_eval_rows(theta, data, labels, rows, seg_start, seg_len, max_len, loss_sum, correct, pred,
                     logits, Cin, H, W, C)           k_gnl_eval + k_lin_eval_sum (the same for GN-LeNet)
 All ops launch on torch's current HIP stream of the input's device, never synchronise, and raise
@@ -734,6 +737,53 @@ def gnlenet_eval_rows(theta: torch.Tensor, data: torch.Tensor, labels: torch.Ten
         logits.shape[1] if logits is not None else 0,
         Cin, H, W, C, scratch.data_ptr(), nbytes, _stream(theta))
     _lib.check(rc, "niidmix::gnlenet_eval_rows")
+
+
+@torch.library.custom_op("niidmix::gnlenet_nll_grad_rows", mutates_args=("grad", "loss"))
+def gnlenet_nll_grad_rows(theta: torch.Tensor, data: torch.Tensor, labels: torch.Tensor,
+                          batch_idx: torch.Tensor, batch_len: torch.Tensor, rows: torch.Tensor,
+                          grad: torch.Tensor, loss: torch.Tensor,
+                          Cin: int, H: int, W: int, C: int) -> None:
+    """linear_nll_grad_rows for GN-LeNet (include/niidmix.h, niidmix_gnlenet_nll_grad_rows_f32): row
+    r of theta holds the model's 14 parameter tensors (P columns); batch_idx[i] lists the
+    batch_len[i] samples of data [S, Cin * H * W] / labels that rows[i] trains on; grad gets
+    F.nll_loss(forward(x), y).backward()'s gradient in the same layout, loss the mean batch loss.
+    The scratch buffer comes from torch's caching allocator.  The index tensors' CONTENTS are not
+    checked here (niidmix.train.DeviceTrainer checks them once)."""
+    Cin, H, W, C = int(Cin), int(H), int(W), int(C)
+    _req(Cin >= 1 and H >= 1 and W >= 1 and C >= 1, "Cin, H, W and C must be >= 1")
+    _req(C <= 1024 and Cin <= 4 and 15 <= H <= 64 and 15 <= W <= 64,
+         "unsupported shape: the kernel holds C <= 1024, Cin <= 4, 15 <= H, W <= 64")
+    _, p = gnlenet_sizes(Cin, H, W, C)
+    _slab("theta", theta)
+    _slab("grad", grad)
+    _req(theta.shape[1] == p and grad.shape[1] == p,
+         f"theta and grad: expected P = {p} columns, got {theta.shape[1]} and {grad.shape[1]}")
+    _slab("data", data, cols=Cin * H * W)
+    _req(data.is_contiguous(), "data: expected a contiguous [S, Cin * H * W] tensor")
+    dev = theta.device
+    _req(grad.device == dev and data.device == dev, "theta, grad and data must be on the same device")
+    _vec("labels", labels, torch.int32, dev, data.shape[0])
+    _vec("rows", rows, torch.int32, dev)
+    n = rows.numel()
+    _vec("batch_len", batch_len, torch.int32, dev, n)
+    _req(batch_idx.device == dev and batch_idx.dtype == torch.int32 and batch_idx.dim() == 2
+         and batch_idx.is_contiguous() and batch_idx.shape[0] == n,
+         f"batch_idx: expected a contiguous int32 [{n}, b_max] tensor on {dev}")
+    _vec("loss", loss, torch.float32, dev, n)
+    _req(n <= theta.shape[0] and n <= grad.shape[0], "more rows listed than theta or grad has")
+    _req(not _hits(grad, theta) and not _hits(loss, theta), "grad or loss overlaps theta")
+    if n == 0:
+        return
+    b_max = batch_idx.shape[1]
+    _req(b_max >= 1, "batch_idx: b_max must be >= 1")
+    nbytes = max(16, int(_lib.lib.niidmix_gnlenet_nll_grad_rows_scratch_bytes(n, b_max, Cin, H, W, C)))
+    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    rc = _lib.lib.niidmix_gnlenet_nll_grad_rows_f32(
+        theta.data_ptr(), _ld(theta), data.data_ptr(), labels.data_ptr(), batch_idx.data_ptr(),
+        batch_len.data_ptr(), b_max, rows.data_ptr(), n, grad.data_ptr(), _ld(grad), loss.data_ptr(),
+        Cin, H, W, C, scratch.data_ptr(), nbytes, _stream(theta))
+    _lib.check(rc, "niidmix::gnlenet_nll_grad_rows")
 
 
 # ------------------------------------------------------------------------------------------------

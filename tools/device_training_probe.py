@@ -16,6 +16,19 @@
     python tools/device_training_probe.py rounds --shape ref [--warmup 2] [--rounds 10]
     python tools/device_training_probe.py all        # every step as a child process of its own
 
+GN-LeNet (niidmix_gnlenet_nll_grad_rows_f32, --device-training-gn-lenet), at the two shapes
+    gn-cifar   N 1000, 3 x 32 x 32, C 10, B 20     gn-mnist   N 100, 1 x 28 x 28, C 10, B 128
+  gn-kernel  the gradient call against three yardsticks, all four alternating within every
+             repetition: the CPU loop (forward + nll_loss + backward of the module, torch's
+             threads as set, on a few nodes, scaled to N), torch autograd on the device (the
+             same module, looped over a few nodes, scaled to N), and niidmix_stream_copy_f32 over
+             the bytes the call must read (parameters and batch samples).  Device candidates by
+             device events, the CPU loop by the host clock.
+  gn-rounds  as `rounds`, for GN-LeNet models and the --device-training-gn-lenet flag.
+
+    python tools/device_training_probe.py gn-kernel --shape gn-cifar [--warmup 5] [--reps 20]
+    python tools/device_training_probe.py gn-rounds --shape gn-mnist [--warmup 2] [--rounds 10]
+
 `all` runs the four steps one after the other, each in a fresh process under its own time limit,
 and stops at the first that fails.  Every step prints one JSON line.
 """
@@ -32,7 +45,116 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [REPO, os.path.join(REPO, "non-iid-topology-simulator_amd")]
 
 SHAPES = {"ref": (1000, 784, 10, 125), "e2e": (1000, 1023, 1024, 16)}
+GN_SHAPES = {"gn-cifar": (1000, 3, 32, 32, 10, 20), "gn-mnist": (100, 1, 28, 28, 10, 128)}
 STEP_LIMIT_S = {"kernel": 180, "rounds": 420}
+
+
+def _gn_lenet(cin, h, w, c):
+    """A module with GN-LeNet's 14 parameter tensors and forward (setup/model/gn_lenet.py's
+    layers), built here so that the tool needs no dataset code."""
+    import torch
+    import torch.nn.functional as F
+    from niidmix import ops
+
+    class GNLeNet(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            gn = torch.nn.GroupNorm
+            self.features = torch.nn.Sequential(
+                torch.nn.Conv2d(cin, 32, 5, padding=2), torch.nn.MaxPool2d(3, 2), gn(2, 32),
+                torch.nn.ReLU(),
+                torch.nn.Conv2d(32, 32, 5, padding=2), gn(2, 32), torch.nn.MaxPool2d(3, 2),
+                torch.nn.ReLU(),
+                torch.nn.Conv2d(32, 64, 5, padding=2), gn(2, 64), torch.nn.MaxPool2d(3, 2),
+                torch.nn.ReLU())
+            self.classifier = torch.nn.Sequential(torch.nn.Linear(ops.gnlenet_sizes(cin, h, w, c)[0], c))
+
+        def forward(self, x, params):
+            return F.log_softmax(self.classifier(torch.flatten(self.features(x), 1)), dim=1)
+
+    return GNLeNet
+
+
+def gn_kernel(a):
+    import copy
+    import torch
+    import torch.nn.functional as F
+    from niidmix import _lib, ops, train
+    n, cin, h, w, c, b = GN_SHAPES[a.shape]
+    n = a.nodes or n
+    dev = torch.device("cuda:0")
+    k = cin * h * w
+    p = ops.gnlenet_sizes(cin, h, w, c)[1]
+    ld = train.padded_ld(p)
+    torch.manual_seed(3)
+    mdl = _gn_lenet(cin, h, w, c)()
+    row = torch.cat([q.detach().reshape(-1) for q in mdl.parameters()])
+    gen = torch.Generator(device=dev).manual_seed(1)
+    s = n * 2 * b
+    theta = torch.zeros(n, ld, device=dev)
+    theta[:, :p] = row.to(dev) * (1 + 0.01 * torch.randn(n, p, device=dev, generator=gen))
+    grad = torch.zeros(n, ld, device=dev)
+    data = torch.randn(s, k, device=dev, generator=gen)
+    labels = torch.randint(0, c, (s,), device=dev, generator=gen).to(torch.int32)
+    idx = torch.stack([torch.randperm(2 * b, device=dev, generator=gen)[:b] + 2 * b * i
+                       for i in range(n)]).to(torch.int32).contiguous()
+    blen = torch.full((n,), b, dtype=torch.int32, device=dev)
+    rows = torch.arange(n, dtype=torch.int32, device=dev)
+    loss = torch.empty(n, device=dev)
+    lib = _lib.lib
+    nbytes = int(lib.niidmix_gnlenet_nll_grad_rows_scratch_bytes(n, b, cin, h, w, c))
+    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    strm = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    read = n * p + n * b * k                           # floats the call must read
+    src, dst = torch.empty(read - read % 4, device=dev), torch.empty(read - read % 4, device=dev)
+
+    def grad_call():
+        _lib.check(lib.niidmix_gnlenet_nll_grad_rows_f32(
+            theta.data_ptr(), ld, data.data_ptr(), labels.data_ptr(), idx.data_ptr(), blen.data_ptr(),
+            b, rows.data_ptr(), n, grad.data_ptr(), ld, loss.data_ptr(), cin, h, w, c,
+            scratch.data_ptr(), nbytes, strm), "grad")
+
+    def copy_call():
+        _lib.check(lib.niidmix_stream_copy_f32(src.data_ptr(), dst.data_ptr(), src.numel(), strm), "copy")
+
+    def loop(model, x, y, nodes):
+        for i in range(nodes):                         # one node's CPU-path step, minus the optimizer
+            model.zero_grad(set_to_none=True)
+            F.nll_loss(model.forward(x[i], None), y[i]).backward()
+
+    n_dev, n_cpu = min(n, a.loop_nodes_device), min(n, a.loop_nodes_cpu)
+    xb = data[idx[:n_dev].long()].reshape(n_dev, b, cin, h, w)
+    yb = labels[idx[:n_dev].long()].long()
+    mdl_dev = copy.deepcopy(mdl).to(dev)
+    xc, yc = xb[:n_cpu].cpu(), yb[:n_cpu].cpu()
+    cands = [("copy", copy_call, 1.0, True), ("grad", grad_call, 1.0, True),
+             ("device_autograd", lambda: loop(mdl_dev, xb, yb, n_dev), n / n_dev, True),
+             ("cpu_loop", lambda: loop(mdl, xc, yc, n_cpu), n / n_cpu, False)]
+    times = {name: [] for name, _, _, _ in cands}
+    for rep_i in range(a.warmup + a.reps):
+        for name, fn, scale, on_dev in cands:
+            torch.cuda.synchronize(dev)
+            s0, e0 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0 = time.perf_counter()
+            s0.record()
+            fn()
+            e0.record()
+            e0.synchronize()
+            dt = s0.elapsed_time(e0) * 1e-3 if on_dev else time.perf_counter() - t0
+            if rep_i >= a.warmup:
+                times[name].append(dt * scale)
+    assert bool(torch.isfinite(loss).all())
+    out = {"step": "gn-kernel", "shape": a.shape, "n": n, "sample": [cin, h, w], "c": c, "b": b,
+           "warmup": a.warmup, "reps": a.reps, "threads": torch.get_num_threads(),
+           "loop_nodes_device": n_dev, "loop_nodes_cpu": n_cpu, "scratch_bytes": nbytes,
+           "read_bytes": 4 * read, "device": torch.cuda.get_device_name(dev),
+           "lib_sha16": _lib.lib_sha16()}
+    for name, _, _, _ in cands:
+        t = times[name]
+        out[name] = {"median_ms": statistics.median(t) * 1e3, "min_ms": min(t) * 1e3, "max_ms": max(t) * 1e3}
+    for name in ("copy", "device_autograd", "cpu_loop"):
+        out["grad_over_" + name] = out["grad"]["median_ms"] / out[name]["median_ms"]
+    print(json.dumps(out))
 
 
 def kernel(a):
@@ -99,7 +221,12 @@ def rounds(a):
     from niidmix import d_sgd
     from niidmix.generate import dcliques
     from niidmix.topology import mh_csr
-    n, k, c, b = SHAPES[a.shape]
+    gn = a.shape in GN_SHAPES
+    if gn:
+        n, cin, h, w, c, b = GN_SHAPES[a.shape]
+        k = cin * h * w
+    else:
+        n, k, c, b = SHAPES[a.shape]
     n = a.nodes or n
     per_node = 2 * b
 
@@ -115,6 +242,9 @@ def rounds(a):
     topo = {"edges": edges, "csr": mh_csr(n, edges), "weights": torch.tensor([]), "cliques": cliques}
     g = torch.Generator().manual_seed(5)
     x = torch.rand(per_node, k, generator=g)               # every node trains on the same samples
+    if gn:
+        Net = _gn_lenet(cin, h, w, c)
+        x = x.reshape(per_node, cin, h, w)
     y = torch.randint(0, c, (per_node,), generator=g)
     runs = {}
     for flag in (False, True):
@@ -127,6 +257,8 @@ def rounds(a):
                                 "initial-averaging": False, "clique-gradient": False,
                                 "unbiased-gradient": False, "deferred-writeback": True,
                                 "mixing-mode": a.mode, "device-training": flag}}
+        if gn and flag:
+            params["algorithm"]["device-training-gn-lenet"] = True
         ts = [(x[j], int(y[j])) for j in range(per_node)]
         nodes = []
         for r in range(n):
@@ -145,7 +277,7 @@ def rounds(a):
             runs[flag][0] = state
             if rnd >= a.warmup:
                 times.append(dt)
-    out = {"step": "rounds", "shape": a.shape, "n": n, "k": k, "c": c, "b": b, "mode": a.mode,
+    out = {"step": "gn-rounds" if gn else "rounds", "shape": a.shape, "n": n, "k": k, "c": c, "b": b, "mode": a.mode,
            "warmup": a.warmup, "rounds": a.rounds, "threads": torch.get_num_threads(),
            "device": torch.cuda.get_device_name(0)}
     for flag, key in ((False, "flag_off"), (True, "flag_on")):
@@ -168,8 +300,12 @@ def run_all(a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("step", choices=["kernel", "rounds", "all"])
-    ap.add_argument("--shape", choices=list(SHAPES), default="ref")
+    ap.add_argument("step", choices=["kernel", "rounds", "gn-kernel", "gn-rounds", "all"])
+    ap.add_argument("--shape", choices=list(SHAPES) + list(GN_SHAPES), default=None)
+    ap.add_argument("--loop-nodes-device", type=int, default=8,
+                    help="gn-kernel: nodes the device autograd loop runs per repetition (scaled to N)")
+    ap.add_argument("--loop-nodes-cpu", type=int, default=3,
+                    help="gn-kernel: nodes the CPU loop runs per repetition (scaled to N)")
     ap.add_argument("--nodes", type=int, default=0, help="override the shape's node count")
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--reps", type=int, default=20)
@@ -181,9 +317,14 @@ def main():
     import torch
     if not torch.cuda.is_available():
         sys.exit("device_training_probe: no GPU (a rate is only ever measured on one)")
+    gn = a.step.startswith("gn-")
+    if a.shape is None:
+        a.shape = "gn-cifar" if gn else "ref"
+    if (a.shape in GN_SHAPES) != gn:
+        sys.exit(f"device_training_probe: {a.step} does not take the shape {a.shape}")
     if a.warmup is None:
-        a.warmup = 5 if a.step == "kernel" else 2
-    (kernel if a.step == "kernel" else rounds)(a)
+        a.warmup = 5 if a.step.endswith("kernel") else 2
+    {"kernel": kernel, "rounds": rounds, "gn-kernel": gn_kernel, "gn-rounds": rounds}[a.step](a)
 
 
 if __name__ == "__main__":
