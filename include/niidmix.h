@@ -25,7 +25,9 @@
  * ABI 6 (this header): niidmix_sgd_momentum_step_rows_f32 added (the optimizer step of
  * --learning-momentum on the device); niidmix_linear_nll_grad_rows_f32 and its
  * niidmix_linear_nll_grad_rows_scratch_elems added (local training of a linear classifier on the
- * device: forward, loss and backward; a pure addition, the version is unchanged).
+ * device: forward, loss and backward; a pure addition, the version is unchanged);
+ * niidmix_grad_segment_mean_sgd_step_f32 added (the clique gradient mean fused with the optimizer
+ * step, for --clique-gradient under --device-training; a pure addition too).
  * ABI 5: niidmix_dense_split_elems / niidmix_dense_split_w /
  * niidmix_mix_dense_bf16x6_f32 added (the dense GEMM on the bf16 matrix cores, fp32-accurate by
  * three-term splitting); niidmix_mix_strip_f32 refuses a strip that does not fit the device's LDS.
@@ -413,6 +415,38 @@ int niidmix_sgd_momentum_step_rows_f32(float *p, int64_t ld_p, const float *g, i
                                        float *buf, int64_t ld_b, int64_t ncols,
                                        const int32_t *rows, int64_t n_rows, float neg_lr,
                                        float momentum, int first, void *stream);
+
+/* Segment gradient mean fused with the SGD step: --clique-gradient without removed clique edges on
+ * device-resident parameters (niidmix.train.DeviceTrainer), i.e. the reference's average_gradients,
+ * update_gradients and optimizer.step() of every clique member (d_sgd.py:56-65) in one pass.
+ * Segment s lists the member rows seg_row[seg_ptr[s] .. seg_ptr[s+1]) in clique order; segments are
+ * disjoint.  Per segment and column:
+ *   acc = +0; acc = fl(acc + g_m) in member order; gm = fl(+0 + fl(acc / len))
+ *   momentum == 0:  p_m = fma(neg_lr, gm, p_m)                  (buf may be NULL, first is ignored)
+ *   first != 0:     buf_m = gm (a copy; buf is not read);         p_m = fma(neg_lr, buf_m, p_m)
+ *   otherwise:      buf_m = fl(fl(momentum * buf_m) + gm);       p_m = fma(neg_lr, buf_m, p_m)
+ * for every member m: bit for bit niidmix_grad_segment_mean_f32 followed by
+ * niidmix_sgd_step_rows_f32 / niidmix_sgd_momentum_step_rows_f32 over the member rows, without the
+ * averaged gradient slab: g, p (and buf) are read and p (and buf) written once, 12 B per
+ * node-parameter without momentum, 16 B on the first momentum step and 20 B later, against 20 / 24
+ * / 28 B for the two calls.  g is not written.  Rows in no segment and columns from ncols to the
+ * leading dimension are untouched in p and buf; n_seg == 0 and empty segments are no-ops.
+ *   p   [*, ld_p] parameters (device, updated in place)
+ *   g   [*, ld_g] gradients (device)
+ *   buf [*, ld_b] momentum buffers (device, updated in place); NULL, 0 when momentum == 0
+ *   seg_ptr [n_seg+1], seg_row [n_members] int32 (device), n_members = seg_ptr[n_seg]
+ * float4 accesses when ncols and the leading dimensions are multiples of 4 and the pointers 16-B
+ * aligned, scalar ones otherwise.
+ * Range checks: the segment lists are on the device and are not read by the launcher, so each
+ * slab's extent is taken as the least n_members distinct rows can span, (n_members - 1) * ld +
+ * ncols elements from its base; any two of p, g, buf that overlap over those extents are refused
+ * (NIIDMIX_EALIAS; the rule of niidmix_sgd_momentum_step_rows_f32).  NIIDMIX_EINVAL: a null
+ * pointer (buf only when momentum != 0), a negative size, a leading dimension below ncols. */
+int niidmix_grad_segment_mean_sgd_step_f32(float *p, int64_t ld_p, const float *g, int64_t ld_g,
+                                           float *buf, int64_t ld_b, int64_t ncols, int64_t n_seg,
+                                           const int32_t *seg_ptr, const int32_t *seg_row,
+                                           int64_t n_members, float neg_lr, float momentum, int first,
+                                           void *stream);
 
 /* Local training of a linear classifier on the listed rows: forward, mean NLL loss and backward of
  * the reference's linear model (setup/model/linear.py: one nn.Linear(K, C), log_softmax, nll_loss)

@@ -4007,6 +4007,106 @@ __global__ __launch_bounds__(256) void k_sgd_momentum_step_rows(float *__restric
 }
 
 // ----------------------------------------------------------------------------------------------
+// Segment gradient mean fused with the SGD step (--clique-gradient under --device-training):
+// k_grad_segment_mean followed by k_sgd_step_rows / k_sgd_momentum_step_rows over the member rows,
+// bit for bit, without the averaged [N, P] slab in between.  Per segment and column
+//   acc = +0; acc = fl(acc + g_m) in member order; gm = fl(+0 + fl(acc / len))
+//   MOM 0 (momentum 0):   p_m = fma(neg_lr, gm, p_m)
+//   MOM 1 (first step):   buf_m = gm;                          p_m = fma(neg_lr, buf_m, p_m)
+//   MOM 2 (later steps):  buf_m = fl(fl(momentum * buf_m) + gm); p_m = fma(neg_lr, buf_m, p_m)
+// 12 / 16 / 20 B per node-parameter against 20 / 24 / 28 B for the two launches.  Work item and row
+// descriptors as in k_grad_segment_mean; the second walk keeps U members' p (and buf) loads in
+// flight.  g and buf are touched once per round: non-temporal; p is read by the mixing kernel
+// next: plain stores.  Every lane fetches the descriptors (v_readlane reads lanes that must be
+// active) and loads from a valid column; only the stores are masked by `ok`.
+template <int V, int U, int MOM>
+__global__ __launch_bounds__(256) void k_grad_segment_mean_sgd_step(
+        float *__restrict__ p, int64_t ld_p, const float *__restrict__ g, int64_t ld_g,
+        float *__restrict__ buf, int64_t ld_b, int64_t ncols, int64_t n_seg,
+        const int32_t *__restrict__ seg_ptr, const int32_t *__restrict__ seg_row, float neg_lr,
+        float momentum, int64_t n_chunks) {
+#pragma clang fp contract(off)           // the buffer update is a rounded multiply, then a rounded add
+    const int lane = threadIdx.x & (kWave - 1);
+    for (int64_t t = blockIdx.x; t < n_seg * n_chunks; t += gridDim.x) {
+        const int64_t seg = t / n_chunks;
+        const int64_t c = (t % n_chunks) * (256 * V) + (int64_t)threadIdx.x * V;
+        const bool ok = c < ncols;               // V == 4 only when ncols % 4 == 0: all-in or all-out
+        const int64_t cc = ok ? c : 0;           // loads stay unconditional
+        const int beg = seg_ptr[seg], end = seg_ptr[seg + 1];
+        float acc[V];
+#pragma unroll
+        for (int e = 0; e < V; ++e) acc[e] = 0.f;
+        for (int kb = beg; kb < end; kb += 64) {
+            const int cnt = end - kb < 64 ? end - kb : 64;
+            const int d_row = seg_row[kb + (lane < cnt ? lane : cnt - 1)];
+            for (int j = 0; j < cnt; j += U) {
+                float v[U][V];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const int jj = j + u < cnt ? j + u : cnt - 1;
+                    ldv_nt<V>(g + (int64_t)__builtin_amdgcn_readlane(d_row, jj) * ld_g + cc, v[u]);
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+                    if (j + u < cnt) {
+#pragma unroll
+                        for (int e = 0; e < V; ++e) acc[e] = acc[e] + v[u][e];
+                    }
+            }
+        }
+        const float len = (float)(end > beg ? end - beg : 1);
+        float gm[V];
+#pragma unroll
+        for (int e = 0; e < V; ++e) gm[e] = 0.f + acc[e] / len;
+        for (int kb = beg; kb < end; kb += 64) {
+            const int cnt = end - kb < 64 ? end - kb : 64;
+            const int d_row = seg_row[kb + (lane < cnt ? lane : cnt - 1)];
+            for (int j = 0; j < cnt; j += U) {
+                // the members of a segment are distinct rows: a batch's loads (the tail repeats
+                // member cnt - 1) all precede its stores, and no other item touches these rows
+                float pv[U][V], bv[U][V];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const int jj = j + u < cnt ? j + u : cnt - 1;
+                    const int64_t r = __builtin_amdgcn_readlane(d_row, jj);
+                    ldv<V>(p + r * ld_p + cc, pv[u]);
+                    if constexpr (MOM == 2) ldv_nt<V>(buf + r * ld_b + cc, bv[u]);
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const int jj = j + u < cnt ? j + u : cnt - 1;
+                    const int64_t r = __builtin_amdgcn_readlane(d_row, jj);
+#pragma unroll
+                    for (int e = 0; e < V; ++e) {
+                        if constexpr (MOM == 2) {
+                            const float mb = momentum * bv[u][e];   // rounded (contract off in this
+                            bv[u][e] = mb + gm[e];                  // function), then a rounded add
+                        } else {
+                            bv[u][e] = gm[e];
+                        }
+                        pv[u][e] = __builtin_fmaf(neg_lr, bv[u][e], pv[u][e]);
+                    }
+                    if (ok && j + u < cnt) {
+                        if constexpr (V == 4) {
+                            typedef float f4 __attribute__((ext_vector_type(4)));
+                            if constexpr (MOM != 0) {
+                                const f4 o = {bv[u][0], bv[u][1], bv[u][2], bv[u][3]};
+                                __builtin_nontemporal_store(o, reinterpret_cast<f4 *>(buf + r * ld_b + c));
+                            }
+                            *reinterpret_cast<float4 *>(p + r * ld_p + c) =
+                                make_float4(pv[u][0], pv[u][1], pv[u][2], pv[u][3]);
+                        } else {
+                            if constexpr (MOM != 0) __builtin_nontemporal_store(bv[u][0], buf + r * ld_b + c);
+                            p[r * ld_p + c] = pv[u][0];
+                        }
+                    }
+                }
+            }
+        }
+    }
+}
+
+// ----------------------------------------------------------------------------------------------
 // Local training of a linear classifier on listed rows (niidmix_linear_nll_grad_rows_f32): row r
 // of theta is W [C, K] then b [C]; for its batch of len samples x_s = data[batch_idx[s]],
 //   z[s,c] = sum_k x[s,k] W[c,k] + b[c],   loss = -(1/len) sum_s (z[s,y_s] - lse_s),
@@ -6305,6 +6405,34 @@ int niidmix_sgd_momentum_step_rows_f32(float *p, int64_t ld_p, const float *g, i
     hipLaunchKernelGGL(kfn, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, ld_p, g, ld_g,
                        buf, ld_b, ncols, rows, n_rows, neg_lr, momentum, n_chunks);
     return check_launch("k_sgd_momentum_step_rows");
+}
+
+int niidmix_grad_segment_mean_sgd_step_f32(float *p, int64_t ld_p, const float *g, int64_t ld_g,
+                                           float *buf, int64_t ld_b, int64_t ncols, int64_t n_seg,
+                                           const int32_t *seg_ptr, const int32_t *seg_row,
+                                           int64_t n_members, float neg_lr, float momentum, int first,
+                                           void *stream) {
+    if (ncols < 0 || n_seg < 0 || n_members < 0) return set_error(NIIDMIX_EINVAL, "negative size");
+    if (ncols == 0 || n_seg == 0 || n_members == 0) return NIIDMIX_OK;
+    const bool mom = momentum != 0.f;            // buf is neither read nor written without momentum
+    if (!p || !g || (mom && !buf) || !seg_ptr || !seg_row) return set_error(NIIDMIX_EINVAL, "null pointer");
+    if (int rc = check_ld(ld_p, ld_g, ncols, "ncols")) return rc;
+    // the segment lists live on the device: n_members distinct rows reach at least row n_members - 1
+    if (int rc = check_overlap(p, ld_p, g, ld_g, n_members, ncols, "p and g overlap")) return rc;
+    if (mom) {
+        if (int rc = check_ld(ld_b, ld_b, ncols, "ncols")) return rc;
+        if (int rc = check_overlap(p, ld_p, buf, ld_b, n_members, ncols, "p and buf overlap")) return rc;
+        if (int rc = check_overlap(g, ld_g, buf, ld_b, n_members, ncols, "g and buf overlap")) return rc;
+    }
+    const int vw = vec_width({ncols, ld_p, ld_g, mom ? ld_b : 0}, {p, g, mom ? buf : nullptr}) == 4 ? 4 : 1;
+    int64_t n_chunks;
+    const dim3 grid = row_chunk_grid(n_seg, ncols, vw == 4, &n_chunks);
+    const int mcase = !mom ? 0 : first != 0 ? 1 : 2;
+    auto kfn = pick<4, 1>(vw, [&](auto V) { return pick<0, 1, 2>(mcase, [&](auto M) {
+        return k_grad_segment_mean_sgd_step<V(), V() == 4 ? 8 : 16, M()>; }); });
+    hipLaunchKernelGGL(kfn, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, ld_p, g, ld_g,
+                       mom ? buf : nullptr, ld_b, ncols, n_seg, seg_ptr, seg_row, neg_lr, momentum, n_chunks);
+    return check_launch("k_grad_segment_mean_sgd_step");
 }
 
 // K-chunks of k_lin_logits at most: enough (row, chunk) blocks to fill the device at few rows; a

@@ -890,7 +890,7 @@ def init(nodes, topology, params):
         evaluate.check_eligible(nodes, params)            # refusals: ValueError naming the flag
     if params["algorithm"].get("device-training"):
         from . import train
-        train.check_eligible(nodes, params)               # refusals: ValueError naming the flag
+        train.check_eligible(nodes, params, topology)     # refusals: ValueError naming the flag
         for n in nodes:
             n["train-iterator"] = train.index_loader(n, params)
     else:

@@ -19,6 +19,12 @@ gradient is left alone; here it gets a one-member segment / row (its own gradien
 only differs from "untouched" by turning a -0.0 entry into +0.0 — a gradient that is never
 applied).  Overlapping cliques (which no reference generator produces) would make the reference's
 clique loop order-dependent and are refused.
+
+Under --device-training the parameters live on the device and nothing reads the averaged gradients
+back, so whole cliques take the mean and the optimizer step in one kernel there
+(k_grad_segment_mean_sgd_step over niidmix.train.clique_segments(plan): the cliques alone, a node
+in no clique is not stepped), and the per-row kinds run GradMean into a slab of the trainer's; the
+drop-in rounds keep k_grad_segment_mean, whose output they write back to .grad.
 """
 from dataclasses import dataclass
 

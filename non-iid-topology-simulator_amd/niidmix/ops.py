@@ -20,6 +20,9 @@ Ops (registered in the `niidmix` namespace, usable as torch.ops.niidmix.*):
   sgd_step_rows(p, g, rows, neg_lr)                 k_sgd_step_rows (the optimizer step, fused round)
   sgd_momentum_step_rows(p, g, buf, rows, neg_lr, momentum, first)
                                                     k_sgd_momentum_step_rows (--learning-momentum)
+  grad_segment_mean_sgd_step(p, g, buf_or_None, seg_ptr, seg_row, neg_lr, momentum, first)
+                                                    k_grad_segment_mean_sgd_step (the two above in one
+                                                    pass, --clique-gradient under --device-training)
   mix_csr(..., mode | MEAN)                         per-row gradient mean (unbiased / removed edges)
   linear_nll_grad_rows(theta, data, labels, batch_idx, batch_len, rows, grad, loss, K, C)
                                                     k_lin_logits + k_lin_softmax + k_lin_dw (local
@@ -566,6 +569,33 @@ def sgd_momentum_step_rows(p: torch.Tensor, g: torch.Tensor, buf: torch.Tensor, 
         p.data_ptr(), _ld(p), g.data_ptr(), _ld(g), buf.data_ptr(), _ld(buf), p.shape[1],
         rows.data_ptr(), rows.numel(), float(neg_lr), float(momentum), int(bool(first)), _stream(p))
     _lib.check(rc, "niidmix::sgd_momentum_step_rows")
+
+
+@torch.library.custom_op("niidmix::grad_segment_mean_sgd_step", mutates_args=("p", "buf"))
+def grad_segment_mean_sgd_step(p: torch.Tensor, g: torch.Tensor, buf: Optional[torch.Tensor],
+                               seg_ptr: torch.Tensor, seg_row: torch.Tensor, neg_lr: float,
+                               momentum: float, first: bool) -> None:
+    """grad_segment_mean fused with the optimizer step, in place: every member row of a segment
+    takes its step with the segment's mean gradient (sgd_step_rows when momentum == 0, buf None;
+    else sgd_momentum_step_rows), bit for bit the two ops in sequence, without the averaged
+    gradient slab (include/niidmix.h, niidmix_grad_segment_mean_sgd_step_f32)."""
+    _slab("p", p)
+    _slab("g", g, rows=p.shape[0], cols=p.shape[1])
+    _req(g.device == p.device, "p and g must be on the same device")
+    _req(buf is not None or float(momentum) == 0.0, "buf: required when momentum != 0")
+    if buf is not None:
+        _slab("buf", buf, rows=p.shape[0], cols=p.shape[1])
+        _req(buf.device == p.device, "p, g and buf must be on the same device")
+    _vec("seg_ptr", seg_ptr, torch.int32, p.device)
+    _vec("seg_row", seg_row, torch.int32, p.device)
+    _req(seg_ptr.numel() >= 1, "seg_ptr: expected [n_seg + 1]")
+    _req(seg_row.numel() <= p.shape[0], "seg_row: disjoint segments list at most p's rows")
+    rc = _lib.lib.niidmix_grad_segment_mean_sgd_step_f32(
+        p.data_ptr(), _ld(p), g.data_ptr(), _ld(g), buf.data_ptr() if buf is not None else None,
+        _ld(buf) if buf is not None else 0, p.shape[1], seg_ptr.numel() - 1, seg_ptr.data_ptr(),
+        seg_row.data_ptr(), seg_row.numel(), float(neg_lr), float(momentum), int(bool(first)),
+        _stream(p))
+    _lib.check(rc, "niidmix::grad_segment_mean_sgd_step")
 
 
 @torch.library.custom_op("niidmix::linear_nll_grad_rows", mutates_args=("grad", "loss"))

@@ -24,6 +24,20 @@ niidmix::gnlenet_nll_grad_rows as its gradient op, under a flag of its own,
 GN-LeNet).  The kernel's scratch is about 180 KB per sample, so the row list of a round is cut into
 several calls when one call's scratch would exceed a budget (a row's bits do not depend on the
 cut).
+
+Gradient averaging (--clique-gradient, --unbiased-gradient; d_sgd.py:47-94) runs under both flags,
+between the gradient op and the mixing, on the lists of niidmix.gradient.build_grad_plan:
+
+    whole cliques            niidmix::grad_segment_mean_sgd_step in place of the step op: the
+                             clique's mean gradient and the step of every member in one kernel; a
+                             node in no clique is not stepped (clique_segments drops its segment)
+    removed clique edges,    GradMean (mix_csr | MEAN) into one more [N, P] slab, then the step op
+    neighbourhoods           on the rows the reference steps (GradPlan.stepped)
+
+Either way the round equals, bit for bit, the gradient op followed by the reference's
+average_gradients, update_gradients and optimizer.step() on the CPU, then the mixing
+(tests/test_gpu_train_gradavg.py).  check_eligible needs the topology for this and refuses, naming
+the flag, when the lists cannot be built.
 """
 import copy
 import os
@@ -165,23 +179,52 @@ def sample_sizes(sh, shape, flag, what):
     return cin, h, w, c
 
 
-def check_eligible(nodes, params):
+def grad_plan(n, topology, params, flag):
+    """gradient.build_grad_plan for n nodes under --clique-gradient / --unbiased-gradient (clique
+    wins when both are set, as in the reference), None without either; every reason it cannot be
+    built is a ValueError naming `flag`."""
+    from .gradient import build_grad_plan
+    alg = params["algorithm"]
+    name, key = ("clique-gradient", "cliques") if alg.get("clique-gradient") else \
+        ("unbiased-gradient", "neighbourhoods") if alg.get("unbiased-gradient") else (None, None)
+    if name is None:
+        return None
+    if topology is None:
+        raise ValueError(f"{flag}: --{name} needs the run's topology, none was given")
+    if key not in topology:
+        raise ValueError(f"{flag}: --{name} needs a topology with '{key}'")
+    try:
+        return build_grad_plan(n, topology, params)
+    except (ValueError, KeyError, IndexError, TypeError) as e:
+        raise ValueError(f"{flag}: --{name}: the averaging lists cannot be built "
+                         f"({type(e).__name__}: {e})")
+
+
+def clique_segments(plan):
+    """(seg_ptr, seg_row) of a "clique" plan's cliques alone.  build_grad_plan appends a one-member
+    segment for every node in no clique (its gradient mean is its own gradient); the reference does
+    not step such a node, so the fused mean + step must not see it."""
+    n_seg = len(plan.seg_ptr) - 1 - (plan.n - len(plan.stepped))
+    return plan.seg_ptr[:n_seg + 1].copy(), plan.seg_row[:len(plan.stepped)].copy()
+
+
+def check_eligible(nodes, params, topology=None):
     """The refusals that need no GPU (d_sgd.init calls this): raises ValueError naming the flag.
     Returns (K, C) for linear models and, under --device-training-gn-lenet, (Cin, C, F) for
-    GN-LeNet."""
+    GN-LeNet.  --clique-gradient / --unbiased-gradient are accepted when `topology` gives their
+    averaging lists (grad_plan)."""
     from . import d_sgd
     alg = params["algorithm"]
     gn_flag = gn_enabled(params)
     flag = FLAG_GN if gn_flag else FLAG
     if params["topology"]["name"] == "sample":
         raise ValueError(f"{flag} does not support the 'sample' topology")
-    if alg.get("clique-gradient") or alg.get("unbiased-gradient"):
-        raise ValueError(f"{flag} does not support --clique-gradient / --unbiased-gradient")
     env = os.environ.get("NIIDMIX_DEVICES")
     if env and len([i for i in env.split(",") if i.strip()]) > 1:
         raise ValueError(f"{flag} runs on one device; NIIDMIX_DEVICES lists several")
     if not nodes:
         raise ValueError(f"{flag}: no nodes")
+    grad_plan(len(nodes), topology, params, flag)
     shape = linear_shape(nodes[0]["model"])
     gn_shape = gn_lenet_shape(nodes[0]["model"]) if shape is None else None
     lr, mom = float(alg["learning-rate"]), d_sgd._momentum(params)
@@ -376,7 +419,7 @@ class DeviceTrainer:
 
     def __init__(self, nodes, topology, params, device):
         from . import d_sgd
-        shape = check_eligible(nodes, params)
+        shape = check_eligible(nodes, params, topology)
         self.kind = "linear" if len(shape) == 2 else "gn-lenet"
         self.flag = FLAG_GN if gn_enabled(params) else FLAG
         self.scratch_budget = None       # bytes of scratch per GN-LeNet gradient call (None:
@@ -400,16 +443,22 @@ class DeviceTrainer:
         if self.momentum != 0.0 and d_sgd._momentum_state(nodes) != "none":
             raise ValueError(f"{self.flag} was switched on while the CPU optimizers hold momentum "
                              "buffers: handing them to the device mid-run is not supported")
+        self.params = params
+        plan = grad_plan(self.n, topology, params, self.flag)
+        self.grad_kind = plan.kind if plan is not None else None     # fixed by params for the run
+        # the per-row kinds average into a slab of their own; the clique kind needs none
+        self.n_buf = 3 + (self.momentum != 0.0) + (self.grad_kind in ("clique-removed", "unbiased"))
         xs, ys, self.offsets = self._materialise(nodes)
         self._check_fit(xs)
         dev = self.device
         self.data = xs.to(dev)
         self.labels = ys.to(dev)
-        n_buf = 3 + (self.momentum != 0.0)
-        slabs = [torch.zeros((self.n, self.ld), dtype=torch.float32, device=dev) for _ in range(n_buf)]
+        slabs = [torch.zeros((self.n, self.ld), dtype=torch.float32, device=dev)
+                 for _ in range(self.n_buf)]
         self.theta = [s[:, :self.p] for s in slabs[:2]]      # ping-pong: mixing is out-of-place
         self.grad = slabs[2][:, :self.p]
         self.mbuf = slabs[3][:, :self.p] if self.momentum != 0.0 else None
+        self.gavg = slabs[-1][:, :self.p] if self.grad_kind in ("clique-removed", "unbiased") else None
         self.cur = 0
         self.mom_steps = 0
         self.rows = torch.arange(self.n, dtype=torch.int32, device=dev)
@@ -458,7 +507,7 @@ class DeviceTrainer:
         """ResidentRound.fits-style arithmetic: slabs, data and the kernel's scratch against the
         free HBM.  No fit is an error: there is no silent CPU fallback under an explicit flag."""
         from ._lib import lib
-        n_buf = 3 + (self.momentum != 0.0)
+        n_buf = self.n_buf
         need = n_buf * self.n * self.ld * 4 + xs.numel() * 4
         if self.kind == "linear":
             need += 4 * int(lib.niidmix_linear_nll_grad_rows_scratch_elems(self.n, self.b_max, self.c))
@@ -504,6 +553,27 @@ class DeviceTrainer:
                                       self.grad, self.loss[a:b], *self.sizes)
             self.last_calls += 1
 
+    def _step(self, x):
+        """The optimizer step of the round on the parameters x, after the gradient averaging the
+        run asks for.  Whole cliques: the mean and the step of every clique member in one kernel
+        (a node in no clique is not stepped, as in the reference); per-row lists: the mean into a
+        slab of its own, then the step op on the rows the reference steps.  `first` is right
+        because every stepped row steps every round."""
+        first = self.mom_steps == 0
+        if self.grad_kind == "clique":
+            ops.grad_segment_mean_sgd_step(x, self.grad, self.mbuf, *self.segments, -self.lr,
+                                           self.momentum, first)
+        else:
+            g, rows = self.grad, self.rows
+            if self.gmean is not None:
+                g, rows = self.gmean(self.grad, out=self.gavg), self.step_rows
+            if self.momentum != 0.0:
+                ops.sgd_momentum_step_rows(x, g, self.mbuf, rows, -self.lr, self.momentum, first)
+            else:
+                ops.sgd_step_rows(x, g, rows, -self.lr)
+        if self.momentum != 0.0:
+            self.mom_steps += 1
+
     def _probe(self, nodes, params):
         """probe_forward / probe_gn_lenet on node 0's first samples."""
         ts = nodes[0]["train-set"]
@@ -529,8 +599,24 @@ class DeviceTrainer:
         csr = to_csr(topology)
         if csr.n != self.n:
             raise ValueError(f"topology has {csr.n} nodes, {self.n} models given")
+        plan = grad_plan(self.n, topology, self.params, self.flag)
+        if (plan.kind if plan is not None else None) != self.grad_kind:
+            raise ValueError(f"{self.flag}: the gradient averaging changed from {self.grad_kind} to "
+                             f"{plan.kind if plan is not None else None} during the run")
+        stepped = None if plan is None else frozenset(plan.stepped)
+        if self.mom_steps and stepped != self.stepped:
+            raise ValueError(f"{self.flag}: the new topology changes which nodes take the optimizer "
+                             "step while momentum buffers live on the device: not supported")
         torch.cuda.synchronize(self.device)      # nothing reads the old descriptors any more
         self.mixer = ops.Mixer(csr=csr, cliques=topology.get("cliques"), device=self.device)
+        self.stepped = stepped
+        self.segments = self.gmean = self.step_rows = None
+        if self.grad_kind == "clique":
+            self.segments = tuple(torch.from_numpy(a).to(self.device) for a in clique_segments(plan))
+        elif plan is not None:
+            from .gradient import GradMean
+            self.gmean = GradMean(plan, self.device)
+            self.step_rows = torch.tensor(plan.stepped, dtype=torch.int32, device=self.device)
         self.topology = topology
         self.weights_id = id(topology.get("weights"))
 
@@ -582,12 +668,7 @@ class DeviceTrainer:
         self.idx_dev.copy_(self.idx_host, non_blocking=True)           # one H2D copy
         x, y = self.theta[self.cur], self.theta[1 - self.cur]
         self._gradient(x, self.idx_dev[:nb].view(self.n, self.b_max), self.idx_dev[nb:])
-        if self.momentum != 0.0:
-            ops.sgd_momentum_step_rows(x, self.grad, self.mbuf, self.rows, -self.lr, self.momentum,
-                                       self.mom_steps == 0)
-            self.mom_steps += 1
-        else:
-            ops.sgd_step_rows(x, self.grad, self.rows, -self.lr)
+        self._step(x)
         self.mixer(x, out=y, mode=mode)
         self.cur = 1 - self.cur
         loss = self.loss.cpu().tolist()

@@ -29,6 +29,21 @@ GN-LeNet (niidmix_gnlenet_nll_grad_rows_f32, --device-training-gn-lenet), at the
     python tools/device_training_probe.py gn-kernel --shape gn-cifar [--warmup 5] [--reps 20]
     python tools/device_training_probe.py gn-rounds --shape gn-mnist [--warmup 2] [--rounds 10]
 
+Gradient averaging (--clique-gradient under --device-training):
+  fused-step  niidmix_grad_segment_mean_sgd_step_f32 against its two-launch composition
+              (niidmix_grad_segment_mean_f32, then niidmix_sgd_step_rows_f32 or
+              niidmix_sgd_momentum_step_rows_f32) on 1000 rows in 10 cliques of 100, at P = 2^20
+              (--shape e2e) or GN-LeNet's P for 3 x 32 x 32, C = 10 (--shape gn-cifar), momentum 0
+              and 0.9 (a later step: buf is read), all four alternating within every repetition;
+              device events; each against its algorithmic bytes as a share of 8 TB/s, and the
+              measured time ratio next to the ratio of the byte counts.  The two results are
+              compared bit for bit at the end.
+  rounds / gn-rounds take --clique-gradient and --momentum M: both paths then average the
+              cliques' gradients.
+
+    python tools/device_training_probe.py fused-step --shape e2e [--warmup 5] [--reps 20]
+    python tools/device_training_probe.py gn-rounds --shape gn-cifar --clique-gradient --momentum 0.9
+
 `all` runs the four steps one after the other, each in a fresh process under its own time limit,
 and stops at the first that fails.  Every step prints one JSON line.
 """
@@ -215,6 +230,84 @@ def kernel(a):
     print(json.dumps(out))
 
 
+def fused_step(a):
+    import torch
+    from niidmix import _lib, ops, train
+    n = a.nodes or 1000
+    p = ops.gnlenet_sizes(3, 32, 32, 10)[1] if a.shape == "gn-cifar" else 1 << 20
+    ld = train.padded_ld(p)
+    dev = torch.device("cuda:0")
+    gen = torch.Generator(device=dev).manual_seed(1)
+    size = min(100, n)
+    cliques = [list(range(s0, min(s0 + size, n))) for s0 in range(0, n, size)]
+    seg_ptr = torch.tensor([0] + [c[-1] + 1 for c in cliques], dtype=torch.int32, device=dev)
+    rows = torch.arange(n, dtype=torch.int32, device=dev)                  # seg_row and the step's rows
+    g = torch.randn(n, ld, device=dev, generator=gen)
+    p0 = torch.randn(n, ld, device=dev, generator=gen)
+    b0 = torch.randn(n, ld, device=dev, generator=gen)
+    slabs = {k: torch.empty(n, ld, device=dev) for k in ("p_f", "b_f", "p_c", "b_c", "avg")}
+    lib = _lib.lib
+    strm = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    ptr = {k: v.data_ptr() for k, v in slabs.items()}
+    n_seg, lr = len(cliques), -0.05
+
+    def fused(m):
+        return lib.niidmix_grad_segment_mean_sgd_step_f32(
+            ptr["p_f"], ld, g.data_ptr(), ld, ptr["b_f"] if m else None, ld if m else 0, p, n_seg,
+            seg_ptr.data_ptr(), rows.data_ptr(), n, lr, m, 0, strm)
+
+    def parts(m):
+        rc = lib.niidmix_grad_segment_mean_f32(g.data_ptr(), ld, ptr["avg"], ld, n, p, n_seg,
+                                               seg_ptr.data_ptr(), rows.data_ptr(), strm)
+        if rc:
+            return rc
+        if m:
+            return lib.niidmix_sgd_momentum_step_rows_f32(ptr["p_c"], ld, ptr["avg"], ld, ptr["b_c"], ld,
+                                                          p, rows.data_ptr(), n, lr, m, 0, strm)
+        return lib.niidmix_sgd_step_rows_f32(ptr["p_c"], ld, ptr["avg"], ld, p, rows.data_ptr(), n, lr, strm)
+
+    # bytes per node-parameter: include/niidmix.h, niidmix_grad_segment_mean_sgd_step_f32
+    cands = [("fused_m0", fused, 0.0, 12), ("parts_m0", parts, 0.0, 20),
+             ("fused_m09", fused, 0.9, 20), ("parts_m09", parts, 0.9, 28)]
+    times = {name: [] for name, _, _, _ in cands}
+    for k, v in slabs.items():
+        v.copy_(b0 if k.startswith("b_") else p0)
+    for r in range(a.warmup + a.reps):
+        for name, fn, m, _ in cands:
+            s0, e0 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s0.record()
+            _lib.check(fn(m), name)
+            e0.record()
+            e0.synchronize()
+            if r >= a.warmup:
+                times[name].append(s0.elapsed_time(e0) * 1e-3)
+    same = {}
+    for m in (0.0, 0.9):                       # the timed calls ran on drifting values: compare afresh
+        for k in ("p_f", "p_c"):
+            slabs[k].copy_(p0)
+        for k in ("b_f", "b_c"):
+            slabs[k].copy_(b0)
+        _lib.check(fused(m), "fused")
+        _lib.check(parts(m), "parts")
+        torch.cuda.synchronize(dev)
+        same[str(m)] = bool(torch.equal(slabs["p_f"].view(torch.int32), slabs["p_c"].view(torch.int32)) and
+                            torch.equal(slabs["b_f"].view(torch.int32), slabs["b_c"].view(torch.int32)))
+    out = {"step": "fused-step", "shape": a.shape, "n": n, "p": p, "cliques": n_seg, "warmup": a.warmup,
+           "reps": a.reps, "device": torch.cuda.get_device_name(dev), "lib_sha16": _lib.lib_sha16(),
+           "bitwise_equal": same}
+    for name, _, _, bpe in cands:
+        t = times[name]
+        med = statistics.median(t)
+        out[name] = {"bytes": bpe * n * p, "median_ms": med * 1e3, "min_ms": min(t) * 1e3,
+                     "max_ms": max(t) * 1e3, "share_of_8TBps": bpe * n * p / med / 8e12}
+    for tag, pred in (("m0", 12 / 20), ("m09", 20 / 28)):
+        out["ratio_" + tag] = {"measured": out["fused_" + tag]["median_ms"] / out["parts_" + tag]["median_ms"],
+                               "predicted_from_bytes": pred}
+    print(json.dumps(out))
+    if not all(same.values()):
+        sys.exit("device_training_probe: the fused kernel and the two launches differ")
+
+
 def rounds(a):
     import torch
     import torch.nn.functional as F
@@ -253,8 +346,8 @@ def rounds(a):
                   "topology": {"name": "d-cliques", "remove-clique-edges": 0},
                   "logger": {"accuracy-logging-interval": 0, "accuracy-logging-interval-steps": 0,
                              "log-consensus-distance": False},
-                  "algorithm": {"learning-rate": 0.01, "learning-momentum": 0.0, "batch-size": b,
-                                "initial-averaging": False, "clique-gradient": False,
+                  "algorithm": {"learning-rate": 0.01, "learning-momentum": a.momentum, "batch-size": b,
+                                "initial-averaging": False, "clique-gradient": a.clique_gradient,
                                 "unbiased-gradient": False, "deferred-writeback": True,
                                 "mixing-mode": a.mode, "device-training": flag}}
         if gn and flag:
@@ -278,6 +371,7 @@ def rounds(a):
             if rnd >= a.warmup:
                 times.append(dt)
     out = {"step": "gn-rounds" if gn else "rounds", "shape": a.shape, "n": n, "k": k, "c": c, "b": b, "mode": a.mode,
+           "clique_gradient": a.clique_gradient, "momentum": a.momentum,
            "warmup": a.warmup, "rounds": a.rounds, "threads": torch.get_num_threads(),
            "device": torch.cuda.get_device_name(0)}
     for flag, key in ((False, "flag_off"), (True, "flag_on")):
@@ -300,7 +394,7 @@ def run_all(a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("step", choices=["kernel", "rounds", "gn-kernel", "gn-rounds", "all"])
+    ap.add_argument("step", choices=["kernel", "rounds", "gn-kernel", "gn-rounds", "fused-step", "all"])
     ap.add_argument("--shape", choices=list(SHAPES) + list(GN_SHAPES), default=None)
     ap.add_argument("--loop-nodes-device", type=int, default=8,
                     help="gn-kernel: nodes the device autograd loop runs per repetition (scaled to N)")
@@ -311,6 +405,9 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=10)
     ap.add_argument("--mode", choices=["exact", "fast"], default="exact")
+    ap.add_argument("--clique-gradient", action="store_true",
+                    help="rounds / gn-rounds: both paths average the cliques' gradients")
+    ap.add_argument("--momentum", type=float, default=0.0, help="rounds / gn-rounds: --learning-momentum")
     a = ap.parse_args()
     if a.step == "all":
         return run_all(a)
@@ -318,12 +415,17 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("device_training_probe: no GPU (a rate is only ever measured on one)")
     gn = a.step.startswith("gn-")
+    if a.warmup is None:
+        a.warmup = 2 if a.step.endswith("rounds") else 5
+    if a.step == "fused-step":
+        a.shape = a.shape or "e2e"
+        if a.shape not in ("e2e", "gn-cifar"):
+            sys.exit(f"device_training_probe: fused-step takes the shapes e2e and gn-cifar, not {a.shape}")
+        return fused_step(a)
     if a.shape is None:
         a.shape = "gn-cifar" if gn else "ref"
     if (a.shape in GN_SHAPES) != gn:
         sys.exit(f"device_training_probe: {a.step} does not take the shape {a.shape}")
-    if a.warmup is None:
-        a.warmup = 5 if a.step.endswith("kernel") else 2
     {"kernel": kernel, "rounds": rounds, "gn-kernel": gn_kernel, "gn-rounds": rounds}[a.step](a)
 
 
