@@ -21,8 +21,12 @@ The reference's other model, GN-LeNet (setup/model/gn_lenet.py: three 5 x 5 conv
 GroupNorm(2), max-pooling and ReLU, then one Linear), goes through niidmix::gnlenet_eval_rows the
 same way.  Its parameters are read in place from a fresh single-stripe resident round's output slab
 (niidmix.slab.ResidentRound, on its mixing stream), else stacked and uploaded; the job list of a
-call is cut so that the kernel's scratch stays within a fraction of the free HBM (a job's results
-do not depend on the cut).
+call is cut (niidmix.train.cut_rows) so that the kernel's scratch stays within a fraction of the
+free HBM (a job's results do not depend on the cut).
+
+What depends on the model family -- shapes, limits, the sample check, the evaluation op and its
+scratch, the forward probe -- is niidmix.family's; DeviceEvaluator calls through the family of the
+models it is given.
 
 Not bit-identical to the CPU loops (another summation order; tests/test_gpu_eval.py and
 tests/test_gpu_eval_gnlenet.py state the bounds), so the path is opt-in.  A model that is neither
@@ -33,13 +37,12 @@ import sys
 
 import torch
 
-from . import ops, train
+from . import family, train
+from .model import flatten
 
 FLAG = "--device-evaluation"
 CHUNK = 1000          # Logger.log_train_accuracy's DataLoader batch size (logger.py:217)
 SET_NAMES = ("valid", "test", "full-train")
-# the GN-LeNet kernel's limits (include/niidmix.h)
-GN_MAX_CIN, GN_MIN_HW, GN_MAX_HW = train.GN_MAX_CIN, train.GN_MIN_HW, train.GN_MAX_HW
 SCRATCH_FRACTION = 0.8   # of the free HBM, for one call's scratch (DeviceTrainer._check_fit's rule)
 
 
@@ -74,10 +77,6 @@ def fold_chunks(n_nodes, node, length, loss_sum, correct):
     return [(t[0] / t[1], t[2] / t[3]) if t[1] else (0.0, 0.0) for t in tot]
 
 
-# GN-LeNet's shape helpers live in niidmix.train (which this module imports); the names stay here
-gn_lenet_shape, gn_lenet_offsets = train.gn_lenet_shape, train.gn_lenet_offsets
-
-
 def check_eligible(nodes, params):
     """The refusals that need no GPU (d_sgd.init calls this): raises ValueError naming the flag.
     Returns (K, C) for linear models and (Cin, C, F) for GN-LeNet."""
@@ -87,23 +86,16 @@ def check_eligible(nodes, params):
 
 
 def _shape(models):
-    """(kind, shape) of a model list that is all-linear ("linear", (K, C)) or all-GN-LeNet
-    ("gn-lenet", (Cin, C, F)), of one shape."""
-    kind, shape = "linear", train.linear_shape(models[0])
-    if shape is None:
-        kind, shape = "gn-lenet", gn_lenet_shape(models[0])
-    of = train.linear_shape if kind == "linear" else gn_lenet_shape
+    """(family, shape) of a model list that is all-linear (family.LINEAR, (K, C)) or all-GN-LeNet
+    (family.GN_LENET, (Cin, C, F)), of one shape."""
+    fam, shape = family.family_of(models[0]) or (None, None)
     for i, mdl in enumerate(models):
-        if shape is None or of(mdl) != shape:
+        if fam is None or fam.shape(mdl) != shape:
             raise ValueError(f"{FLAG} needs models whose parameters are exactly a [C, K] weight and "
                              f"a [C] bias, or exactly GN-LeNet's 14 tensors, the same on every model "
                              f"(model {i} differs)")
-    if shape[1] > train.MAX_C:
-        raise ValueError(f"{FLAG}: C = {shape[1]} exceeds the kernel's limit (C <= {train.MAX_C})")
-    if kind == "gn-lenet" and shape[0] > GN_MAX_CIN:
-        raise ValueError(f"{FLAG}: {shape[0]} input channels exceed the kernel's limit "
-                         f"(Cin <= {GN_MAX_CIN})")
-    return kind, shape
+    fam.limits(shape, FLAG)
+    return fam, shape
 
 
 class _Set:
@@ -114,7 +106,6 @@ class _Set:
     def __init__(self, data, labels, lo, hi, probe):
         self.data, self.labels, self.lo, self.hi, self.probe = data, labels, lo, hi, probe
         self.m = int(labels.shape[0])
-        self.k = int(data.shape[1]) if self.m else None
         self.shape = tuple(probe[0].shape[1:]) if probe is not None else None
 
 
@@ -126,7 +117,7 @@ def _materialise(source, device, what):
     for x, y in loader:
         x, y = torch.as_tensor(x), torch.as_tensor(y)
         if probe is None:
-            probe = (x[:train.PROBE_SAMPLES].clone(), y[:train.PROBE_SAMPLES].to(torch.int64).clone())
+            probe = (x[:family.PROBE_SAMPLES].clone(), y[:family.PROBE_SAMPLES].to(torch.int64).clone())
         xs.append(x.reshape(x.shape[0], -1).to(torch.float32))
         ys.append(y.reshape(-1).to(torch.int64))
     dev = torch.device(device)
@@ -187,39 +178,18 @@ class DeviceEvaluator:
     def _check(self, st, spec, what):
         """Refuses a set the models do not take; returns the kernel's size arguments: (K, C) for
         linear models, (Cin, H, W, C) for GN-LeNet."""
-        kind, shape = spec
+        fam, shape = spec
         c = shape[1]
         if st.m and (st.lo < 0 or st.hi >= c):
             raise ValueError(f"{FLAG}: {what} has a label outside [0, {c})")
-        if kind == "linear":
-            if st.m and st.k != shape[0]:
-                raise ValueError(f"{FLAG}: the samples of {what} flatten to {st.k} values, the model "
-                                 f"takes K = {shape[0]}")
-            return shape
-        cin, _, f = shape
-        sh = st.shape
-        if sh is None or len(sh) != 3 or sh[0] != cin:
-            raise ValueError(f"{FLAG}: the samples of {what} have shape {sh}, GN-LeNet takes "
-                             f"[{cin}, H, W]")
-        h, w = int(sh[1]), int(sh[2])
-        if not (GN_MIN_HW <= h <= GN_MAX_HW and GN_MIN_HW <= w <= GN_MAX_HW):
-            raise ValueError(f"{FLAG}: samples of {h} x {w} in {what}: the kernel takes "
-                             f"{GN_MIN_HW} <= H, W <= {GN_MAX_HW}")
-        if ops.gnlenet_sizes(cin, h, w, c)[0] != f:
-            raise ValueError(f"{FLAG}: samples of shape {tuple(sh)} in {what} give GN-LeNet "
-                             f"{ops.gnlenet_sizes(cin, h, w, c)[0]} features, the model's classifier "
-                             f"takes F = {f}")
-        return cin, h, w, c
+        return fam.sizes(st.shape, shape, FLAG, what)
 
     def _probe(self, model, st, spec, sizes):
-        key = (type(model), spec[0]) + tuple(sizes)
+        key = (type(model), spec[0].kind) + tuple(sizes)
         if key in self._probed or st.probe is None:
             return
         try:
-            if spec[0] == "linear":
-                train.probe_forward(model, st.probe[0], st.probe[1], self.params, self._dev(), FLAG)
-            else:
-                self._probe_gn_lenet(model, st.probe[0], st.probe[1], sizes)
+            spec[0].probe_eval(model, st.probe[0], st.probe[1], self.params, self._dev(), sizes, FLAG)
         except ValueError:
             raise
         except Exception as e:         # a forward that does not take these samples at all
@@ -228,44 +198,13 @@ class DeviceEvaluator:
                              "evaluated")
         self._probed.add(key)
 
-    def _probe_gn_lenet(self, model, x, y, sizes):
-        """The group count and the layer order cannot be read from parameter shapes: require that
-        the kernel's log-softmaxed logits on the set's first samples agree with model.forward on
-        the CPU within 1e-3 max(1, max |z|) (another architecture differs by O(0.1))."""
-        from . import d_sgd
-        d_sgd.synchronize()
-        cin, h, w, c = sizes
-        dev, nb = self._dev(), int(x.shape[0])
-        with torch.no_grad():
-            want = model.forward(x, self.params).detach().to(torch.float32)
-        p = ops.gnlenet_sizes(cin, h, w, c)[1]
-        theta = torch.zeros((1, train.padded_ld(p)), dtype=torch.float32, device=dev)[:, :p]
-        theta.copy_(train._flat_params([model]))
-        z = torch.zeros((1, nb, c), dtype=torch.float32, device=dev)
-        idx = torch.tensor([[0], [0], [nb]], dtype=torch.int32).to(dev)
-        ops.gnlenet_eval_rows(theta, x.reshape(nb, -1).to(torch.float32).contiguous().to(dev),
-                              y.to(torch.int32).to(dev), idx[0], idx[1], idx[2], nb,
-                              torch.empty(1, dtype=torch.float64, device=dev),
-                              torch.empty(1, dtype=torch.int32, device=dev), None, z, cin, h, w, c)
-        z = z[0].cpu()
-        got = torch.log_softmax(z, 1)
-        bound = 1e-3 * max(1.0, float(z.abs().max()))
-        worst = float((got - want).abs().max()) if tuple(want.shape) == tuple(got.shape) else float("nan")
-        if not worst <= bound:
-            raise ValueError(
-                f"{FLAG}: the model's forward is not GN-LeNet's (5 x 5 convolutions of 32 / 32 / 64 "
-                f"channels, GroupNorm(2), conv-pool-norm then conv-norm-pool twice, one Linear): on "
-                f"the first {nb} samples the kernel's log-probabilities differ from forward on the "
-                f"CPU by {worst:.3g} (bound {bound:.3g})")
-
     # -------------------------------------------------------------------------------------------
     def _theta(self, models):
-        """(theta slab [*, P] on the device, row of each model, (kind, shape), the stream the slab
+        """(theta slab [*, P] on the device, row of each model, (family, shape), the stream the slab
         must be read on or None for the current one)."""
         from . import d_sgd
         spec = _shape(models)
-        kind, shape = spec
-        p = shape[1] * shape[0] + shape[1] if kind == "linear" else gn_lenet_offsets(*shape)[-1]
+        p = spec[0].P(spec[1])
         hit = d_sgd.device_trainer(models)           # a live trainer's slab, of either kind
         if hit is not None and hit[0].p == p:
             tr, rows = hit
@@ -275,7 +214,7 @@ class DeviceEvaluator:
                     self.device = tr.device
                     self.last_source = "trainer"
                     return cur, rows, spec, None
-        if kind != "linear":
+        if spec[0].reads_resident:
             from . import logger as nl
             hit = nl._fresh_resident(models)
             if hit is not None and len(hit[0].parts) == 1 and hit[0].p == p:
@@ -287,44 +226,40 @@ class DeviceEvaluator:
         d_sgd.synchronize()              # the models must hold the last round's rows
         theta = torch.zeros((len(models), train.padded_ld(p)), dtype=torch.float32,
                             device=self._dev())[:, :p]
-        theta.copy_(train._flat_params(models))
+        theta.copy_(flatten(models, "cpu"))
         self.last_source = "stacked"
         return theta, list(range(len(models))), spec, None
 
-    def _gn_cut(self, n, max_len, sizes, dev):
-        """Jobs per call of the GN-LeNet kernel: as many as keep its scratch within the budget."""
-        from ._lib import lib
+    def _cut(self, fam, n, max_len, sizes, dev):
+        """Jobs per call of the family's kernel: all of them for a family whose calls are not cut,
+        else as many as keep the call's scratch within the budget (train.cut_rows)."""
+        if not fam.cut:
+            return n
         budget = self.scratch_budget
         if budget is None:
             budget = SCRATCH_FRACTION * torch.cuda.mem_get_info(dev)[0]
-        need = lambda k: int(lib.niidmix_gnlenet_eval_rows_scratch_bytes(k, max_len, *sizes))  # noqa: E731
-        if need(1) > budget:
+        need = lambda k: fam.eval_scratch_bytes(k, max_len, sizes)  # noqa: E731
+        k = train.cut_rows(n, need, budget)
+        if k is None:
             raise RuntimeError(f"{FLAG}: {need(1) / 2**30:.2f} GiB of scratch for one job of "
                                f"{max_len} samples exceed the budget of {budget / 2**30:.2f} GiB")
-        k = n
-        while need(k) > budget:          # the size grows with the jobs: halve until it fits
-            k = (k + 1) // 2
         return k
 
     def _run(self, theta, st, rows, start, length, spec, sizes, stream=None):
-        dev = theta.device
+        dev, fam = theta.device, spec[0]
         with torch.cuda.device(dev), torch.cuda.stream(stream or torch.cuda.current_stream(dev)):
             n = len(rows)
             idx = torch.tensor([rows, start, length], dtype=torch.int32).to(dev)
             loss = torch.empty(n, dtype=torch.float64, device=dev)
             correct = torch.empty(n, dtype=torch.int32, device=dev)
-            if spec[0] == "linear":
-                ops.linear_eval_rows(theta, st.data, st.labels, idx[0], idx[1], idx[2], max(length),
-                                     loss, correct, None, *sizes)
-            else:
-                cut = self._gn_cut(n, max(length), sizes, dev)
-                self.last_calls = 0
-                for a in range(0, n, cut):
-                    b = min(n, a + cut)
-                    ops.gnlenet_eval_rows(theta, st.data, st.labels, idx[0, a:b], idx[1, a:b],
-                                          idx[2, a:b], max(length[a:b]), loss[a:b], correct[a:b],
-                                          None, None, *sizes)
-                    self.last_calls += 1
+            cut = self._cut(fam, n, max(length), sizes, dev)
+            starts = range(0, n, cut)
+            if fam.cut:                  # as it was: a list that is never cut leaves the count alone
+                self.last_calls = len(starts)
+            for a in starts:
+                b = min(n, a + cut)
+                fam.eval_rows(theta, st.data, st.labels, idx[0, a:b], idx[1, a:b], idx[2, a:b],
+                              max(length[a:b]), loss[a:b], correct[a:b], sizes)
             # read back on the same stream: a copy on another one would not wait for the kernel
             return loss.cpu().tolist(), correct.cpu().tolist()
 
@@ -358,7 +293,7 @@ class DeviceEvaluator:
             ts = nodes[0]["train-set"]
             probe = None
             if len(ts):
-                items = [ts[j] for j in range(min(train.PROBE_SAMPLES, len(ts)))]
+                items = [ts[j] for j in range(min(family.PROBE_SAMPLES, len(ts)))]
                 probe = (torch.stack([torch.as_tensor(s[0]) for s in items]),
                          torch.as_tensor([int(s[1]) for s in items], dtype=torch.int64))
             st = _Set(tr.data, tr.labels, 0, tr.c - 1, probe)

@@ -41,6 +41,7 @@ RuntimeError (TORCH_CHECK-style) on bad arguments.  They accept HIP tensors only
 implementation and no fallback.
 """
 import ctypes
+import math
 import os
 from typing import Optional
 
@@ -598,48 +599,6 @@ def grad_segment_mean_sgd_step(p: torch.Tensor, g: torch.Tensor, buf: Optional[t
     _lib.check(rc, "niidmix::grad_segment_mean_sgd_step")
 
 
-@torch.library.custom_op("niidmix::linear_nll_grad_rows", mutates_args=("grad", "loss"))
-def linear_nll_grad_rows(theta: torch.Tensor, data: torch.Tensor, labels: torch.Tensor,
-                         batch_idx: torch.Tensor, batch_len: torch.Tensor, rows: torch.Tensor,
-                         grad: torch.Tensor, loss: torch.Tensor, K: int, C: int) -> None:
-    """Mean-NLL gradient and loss of a linear classifier on the listed rows (include/niidmix.h,
-    niidmix_linear_nll_grad_rows_f32): row r of theta is W [C, K] then b [C]; batch_idx[i] lists
-    the batch_len[i] samples of data / labels that rows[i] trains on.  The scratch buffer comes
-    from torch's caching allocator.  The index tensors' CONTENTS are not checked here
-    (niidmix.train.DeviceTrainer checks them once)."""
-    K, C = int(K), int(C)
-    _req(K >= 1 and C >= 1, "K and C must be >= 1")
-    p = C * K + C
-    _slab("theta", theta)
-    _slab("grad", grad)
-    _req(theta.shape[1] == p and grad.shape[1] == p,
-         f"theta and grad: expected C * K + C = {p} columns, got {theta.shape[1]} and {grad.shape[1]}")
-    _slab("data", data, cols=K)
-    _req(data.is_contiguous(), "data: expected a contiguous [S, K] tensor")
-    dev = theta.device
-    _req(grad.device == dev and data.device == dev, "theta, grad and data must be on the same device")
-    _vec("labels", labels, torch.int32, dev, data.shape[0])
-    _vec("rows", rows, torch.int32, dev)
-    n = rows.numel()
-    _vec("batch_len", batch_len, torch.int32, dev, n)
-    _req(batch_idx.device == dev and batch_idx.dtype == torch.int32 and batch_idx.dim() == 2
-         and batch_idx.is_contiguous() and batch_idx.shape[0] == n,
-         f"batch_idx: expected a contiguous int32 [{n}, b_max] tensor on {dev}")
-    _vec("loss", loss, torch.float32, dev, n)
-    _req(n <= theta.shape[0] and n <= grad.shape[0], "more rows listed than theta or grad has")
-    if n == 0:
-        return
-    b_max = batch_idx.shape[1]
-    _req(b_max >= 1, "batch_idx: b_max must be >= 1")
-    elems = int(_lib.lib.niidmix_linear_nll_grad_rows_scratch_elems(n, b_max, C))
-    scratch = torch.empty(elems, dtype=torch.float32, device=dev)
-    rc = _lib.lib.niidmix_linear_nll_grad_rows_f32(
-        theta.data_ptr(), _ld(theta), data.data_ptr(), labels.data_ptr(), batch_idx.data_ptr(),
-        batch_len.data_ptr(), b_max, rows.data_ptr(), n, grad.data_ptr(), _ld(grad), loss.data_ptr(),
-        K, C, scratch.data_ptr(), elems, _stream(theta))
-    _lib.check(rc, "niidmix::linear_nll_grad_rows")
-
-
 def _hits(a, b):
     """Tensors a and b share a byte (extents from their own strides)."""
     if a.numel() == 0 or b.numel() == 0 or \
@@ -653,85 +612,77 @@ def _hits(a, b):
     return a0 < b1 and b0 < a1
 
 
-@torch.library.custom_op("niidmix::linear_eval_rows", mutates_args=("loss_sum", "correct", "pred"))
-def linear_eval_rows(theta: torch.Tensor, data: torch.Tensor, labels: torch.Tensor,
-                     rows: torch.Tensor, seg_start: torch.Tensor, seg_len: torch.Tensor,
-                     max_len: int, loss_sum: torch.Tensor, correct: torch.Tensor,
-                     pred: Optional[torch.Tensor], K: int, C: int) -> None:
-    """Summed NLL, correct count and (optionally) predictions of a linear classifier, one job per
-    (slab row, contiguous sample segment) (include/niidmix.h, niidmix_linear_eval_rows_f32): job i
-    scores row rows[i] of theta (W [C, K] then b [C]) on data[seg_start[i] .. + seg_len[i]), lengths
-    clamped to max_len.  loss_sum is float64, correct int32, pred None or int32 [n_jobs, >= max_len].
-    The scratch buffer comes from torch's caching allocator.  The index tensors' CONTENTS are not
-    checked here (niidmix.evaluate.DeviceEvaluator builds and checks them)."""
-    K, C, max_len = int(K), int(C), int(max_len)
-    _req(K >= 1 and C >= 1, "K and C must be >= 1")
-    _req(max_len >= 0, "max_len must be >= 0")
-    p = C * K + C
-    _slab("theta", theta)
-    _req(theta.shape[1] == p, f"theta: expected C * K + C = {p} columns, got {theta.shape[1]}")
-    _slab("data", data, cols=K)
-    _req(data.is_contiguous(), "data: expected a contiguous [S, K] tensor")
-    dev = theta.device
-    _req(data.device == dev, "theta and data must be on the same device")
-    _vec("labels", labels, torch.int32, dev, data.shape[0])
-    _vec("rows", rows, torch.int32, dev)
-    n = rows.numel()
-    _req(n >= 1, "rows: at least one job")
-    _vec("seg_start", seg_start, torch.int32, dev, n)
-    _vec("seg_len", seg_len, torch.int32, dev, n)
-    _vec("loss_sum", loss_sum, torch.float64, dev, n)
-    _vec("correct", correct, torch.int32, dev, n)
-    outs = [loss_sum, correct]
-    if pred is not None:
-        _req(pred.device == dev and pred.dtype == torch.int32 and pred.dim() == 2
-             and pred.shape[0] == n and pred.shape[1] >= max_len
-             and (pred.stride(1) == 1 or pred.shape[1] <= 1),
-             f"pred: expected an int32 [{n}, >= {max_len}] tensor on {dev} with contiguous rows")
-        outs.append(pred)
-    for o in outs:
-        _req(not _hits(o, theta), "an output overlaps theta")
-    nbytes = max(16, int(_lib.lib.niidmix_linear_eval_rows_scratch_bytes(n, max_len, C)))
-    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
-    rc = _lib.lib.niidmix_linear_eval_rows_f32(
-        theta.data_ptr(), _ld(theta), data.data_ptr(), labels.data_ptr(), rows.data_ptr(),
-        seg_start.data_ptr(), seg_len.data_ptr(), n, max_len, loss_sum.data_ptr(), correct.data_ptr(),
-        pred.data_ptr() if pred is not None else None, _ld(pred) if pred is not None else 0,
-        K, C, scratch.data_ptr(), nbytes, _stream(theta))
-    _lib.check(rc, "niidmix::linear_eval_rows")
+# The limits of the training and evaluation kernels (include/niidmix.h), stated here only:
+# niidmix.family's refusals read them too.
+MAX_C = 1024
+MAX_BC = 32768
+GN_MAX_CIN, GN_MIN_HW, GN_MAX_HW = 4, 15, 64
+GN_CHANNELS = (32, 32, 64)          # output channels of GN-LeNet's three convolutions
+
+
+def gnlenet_shapes(Cin, C, F):
+    """The one table of a GN-LeNet row: its 14 tensors in registration order (include/niidmix.h,
+    niidmix_gnlenet_eval_rows_f32): per convolution its weight and bias and its GroupNorm's weight
+    and bias, then the classifier's weight and bias."""
+    out = []
+    for inp, ch in zip((Cin,) + GN_CHANNELS, GN_CHANNELS):
+        out += [(ch, inp, 5, 5), (ch,), (ch,), (ch,)]
+    return out + [(C, F), (C,)]
 
 
 def gnlenet_sizes(Cin, H, W, C):
-    """(F, P) of a GN-LeNet row (include/niidmix.h, niidmix_gnlenet_eval_rows_f32): the classifier's
-    input size and the parameter count."""
+    """(F, P) of a GN-LeNet row: the classifier's input size (the last convolution's channels on
+    what the three 3 x 3 / 2 poolings leave of H x W) and the parameter count, from the table."""
     def down(h):
         return (h - 3) // 2 + 1
-    f = 64 * down(down(down(H))) * down(down(down(W)))
-    return f, 800 * Cin + 77184 + C * f + C
+    f = GN_CHANNELS[-1] * down(down(down(H))) * down(down(down(W)))
+    return f, sum(math.prod(sh) for sh in gnlenet_shapes(Cin, C, f))
 
 
-@torch.library.custom_op("niidmix::gnlenet_eval_rows",
-                         mutates_args=("loss_sum", "correct", "pred", "logits"))
-def gnlenet_eval_rows(theta: torch.Tensor, data: torch.Tensor, labels: torch.Tensor,
-                      rows: torch.Tensor, seg_start: torch.Tensor, seg_len: torch.Tensor,
-                      max_len: int, loss_sum: torch.Tensor, correct: torch.Tensor,
-                      pred: Optional[torch.Tensor], logits: Optional[torch.Tensor],
-                      Cin: int, H: int, W: int, C: int) -> None:
-    """linear_eval_rows for GN-LeNet (include/niidmix.h, niidmix_gnlenet_eval_rows_f32): job i scores
-    row rows[i] of theta (the model's 14 parameter tensors, P columns) on data[seg_start[i] .. +
-    seg_len[i]), data [S, Cin * H * W].  logits: None or fp32 [n_jobs, >= max_len, C], the
-    classifier's output before log_softmax.  The scratch buffer comes from torch's caching
-    allocator.  The index tensors' CONTENTS are not checked here."""
-    Cin, H, W, C, max_len = int(Cin), int(H), int(W), int(C), int(max_len)
-    _req(Cin >= 1 and H >= 1 and W >= 1 and C >= 1, "Cin, H, W and C must be >= 1")
-    _req(max_len >= 0, "max_len must be >= 0")
-    _req(C <= 1024 and Cin <= 4 and 15 <= H <= 64 and 15 <= W <= 64,
-         "unsupported shape: the kernel holds C <= 1024, Cin <= 4, 15 <= H, W <= 64")
-    _, p = gnlenet_sizes(Cin, H, W, C)
+def _gnlenet_limits(Cin, H, W, C):
+    lo, hi = GN_MIN_HW, GN_MAX_HW
+    _req(C <= MAX_C and Cin <= GN_MAX_CIN and lo <= H <= hi and lo <= W <= hi,
+         f"unsupported shape: the kernel holds C <= {MAX_C}, Cin <= {GN_MAX_CIN}, {lo} <= H, W <= {hi}")
+
+
+def _grad_rows_args(theta, data, labels, batch_idx, batch_len, rows, grad, loss, p_text, p,
+                    cols_text, cols, apart):
+    """The checks the two *_nll_grad_rows ops share, after those of their size arguments: theta and
+    grad of `p` columns (`p_text` names the count), data of `cols` columns, the index tensors, and
+    -- `apart` -- grad and loss off theta.  Returns the number of listed rows."""
     _slab("theta", theta)
-    _req(theta.shape[1] == p, f"theta: expected P = {p} columns, got {theta.shape[1]}")
-    _slab("data", data, cols=Cin * H * W)
-    _req(data.is_contiguous(), "data: expected a contiguous [S, Cin * H * W] tensor")
+    _slab("grad", grad)
+    _req(theta.shape[1] == p and grad.shape[1] == p,
+         f"theta and grad: expected {p_text} columns, got {theta.shape[1]} and {grad.shape[1]}")
+    _slab("data", data, cols=cols)
+    _req(data.is_contiguous(), f"data: expected a contiguous [S, {cols_text}] tensor")
+    dev = theta.device
+    _req(grad.device == dev and data.device == dev, "theta, grad and data must be on the same device")
+    _vec("labels", labels, torch.int32, dev, data.shape[0])
+    _vec("rows", rows, torch.int32, dev)
+    n = rows.numel()
+    _vec("batch_len", batch_len, torch.int32, dev, n)
+    _req(batch_idx.device == dev and batch_idx.dtype == torch.int32 and batch_idx.dim() == 2
+         and batch_idx.is_contiguous() and batch_idx.shape[0] == n,
+         f"batch_idx: expected a contiguous int32 [{n}, b_max] tensor on {dev}")
+    _vec("loss", loss, torch.float32, dev, n)
+    _req(n <= theta.shape[0] and n <= grad.shape[0], "more rows listed than theta or grad has")
+    if apart:
+        _req(not _hits(grad, theta) and not _hits(loss, theta), "grad or loss overlaps theta")
+    if n:
+        _req(batch_idx.shape[1] >= 1, "batch_idx: b_max must be >= 1")
+    return n
+
+
+def _eval_rows_args(theta, data, labels, rows, seg_start, seg_len, max_len, loss_sum, correct, pred,
+                    logits, C, p_text, p, cols_text, cols):
+    """The checks the two *_eval_rows ops share, after those of their size arguments: theta of `p`
+    columns (`p_text` names the count), data of `cols` columns, the job list, and every output
+    (`logits` is the GN-LeNet op's alone) off theta.  Returns the number of jobs."""
+    _slab("theta", theta)
+    _req(theta.shape[1] == p, f"theta: expected {p_text} columns, got {theta.shape[1]}")
+    _slab("data", data, cols=cols)
+    _req(data.is_contiguous(), f"data: expected a contiguous [S, {cols_text}] tensor")
     dev = theta.device
     _req(data.device == dev, "theta and data must be on the same device")
     _vec("labels", labels, torch.int32, dev, data.shape[0])
@@ -757,6 +708,82 @@ def gnlenet_eval_rows(theta: torch.Tensor, data: torch.Tensor, labels: torch.Ten
         outs.append(logits)
     for o in outs:
         _req(not _hits(o, theta), "an output overlaps theta")
+    return n
+
+
+@torch.library.custom_op("niidmix::linear_nll_grad_rows", mutates_args=("grad", "loss"))
+def linear_nll_grad_rows(theta: torch.Tensor, data: torch.Tensor, labels: torch.Tensor,
+                         batch_idx: torch.Tensor, batch_len: torch.Tensor, rows: torch.Tensor,
+                         grad: torch.Tensor, loss: torch.Tensor, K: int, C: int) -> None:
+    """Mean-NLL gradient and loss of a linear classifier on the listed rows (include/niidmix.h,
+    niidmix_linear_nll_grad_rows_f32): row r of theta is W [C, K] then b [C]; batch_idx[i] lists
+    the batch_len[i] samples of data / labels that rows[i] trains on.  The scratch buffer comes
+    from torch's caching allocator.  The index tensors' CONTENTS are not checked here
+    (niidmix.train.DeviceTrainer checks them once)."""
+    K, C = int(K), int(C)
+    _req(K >= 1 and C >= 1, "K and C must be >= 1")
+    # as it always was: unlike the GN-LeNet op, this one does not refuse a grad or loss on theta
+    n = _grad_rows_args(theta, data, labels, batch_idx, batch_len, rows, grad, loss,
+                        f"C * K + C = {C * K + C}", C * K + C, "K", K, apart=False)
+    if n == 0:
+        return
+    dev, b_max = theta.device, batch_idx.shape[1]
+    elems = int(_lib.lib.niidmix_linear_nll_grad_rows_scratch_elems(n, b_max, C))
+    scratch = torch.empty(elems, dtype=torch.float32, device=dev)
+    rc = _lib.lib.niidmix_linear_nll_grad_rows_f32(
+        theta.data_ptr(), _ld(theta), data.data_ptr(), labels.data_ptr(), batch_idx.data_ptr(),
+        batch_len.data_ptr(), b_max, rows.data_ptr(), n, grad.data_ptr(), _ld(grad), loss.data_ptr(),
+        K, C, scratch.data_ptr(), elems, _stream(theta))
+    _lib.check(rc, "niidmix::linear_nll_grad_rows")
+
+
+@torch.library.custom_op("niidmix::linear_eval_rows", mutates_args=("loss_sum", "correct", "pred"))
+def linear_eval_rows(theta: torch.Tensor, data: torch.Tensor, labels: torch.Tensor,
+                     rows: torch.Tensor, seg_start: torch.Tensor, seg_len: torch.Tensor,
+                     max_len: int, loss_sum: torch.Tensor, correct: torch.Tensor,
+                     pred: Optional[torch.Tensor], K: int, C: int) -> None:
+    """Summed NLL, correct count and (optionally) predictions of a linear classifier, one job per
+    (slab row, contiguous sample segment) (include/niidmix.h, niidmix_linear_eval_rows_f32): job i
+    scores row rows[i] of theta (W [C, K] then b [C]) on data[seg_start[i] .. + seg_len[i]), lengths
+    clamped to max_len.  loss_sum is float64, correct int32, pred None or int32 [n_jobs, >= max_len].
+    The scratch buffer comes from torch's caching allocator.  The index tensors' CONTENTS are not
+    checked here (niidmix.evaluate.DeviceEvaluator builds and checks them)."""
+    K, C, max_len = int(K), int(C), int(max_len)
+    _req(K >= 1 and C >= 1, "K and C must be >= 1")
+    _req(max_len >= 0, "max_len must be >= 0")
+    n = _eval_rows_args(theta, data, labels, rows, seg_start, seg_len, max_len, loss_sum, correct,
+                        pred, None, C, f"C * K + C = {C * K + C}", C * K + C, "K", K)
+    dev = theta.device
+    nbytes = max(16, int(_lib.lib.niidmix_linear_eval_rows_scratch_bytes(n, max_len, C)))
+    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    rc = _lib.lib.niidmix_linear_eval_rows_f32(
+        theta.data_ptr(), _ld(theta), data.data_ptr(), labels.data_ptr(), rows.data_ptr(),
+        seg_start.data_ptr(), seg_len.data_ptr(), n, max_len, loss_sum.data_ptr(), correct.data_ptr(),
+        pred.data_ptr() if pred is not None else None, _ld(pred) if pred is not None else 0,
+        K, C, scratch.data_ptr(), nbytes, _stream(theta))
+    _lib.check(rc, "niidmix::linear_eval_rows")
+
+
+@torch.library.custom_op("niidmix::gnlenet_eval_rows",
+                         mutates_args=("loss_sum", "correct", "pred", "logits"))
+def gnlenet_eval_rows(theta: torch.Tensor, data: torch.Tensor, labels: torch.Tensor,
+                      rows: torch.Tensor, seg_start: torch.Tensor, seg_len: torch.Tensor,
+                      max_len: int, loss_sum: torch.Tensor, correct: torch.Tensor,
+                      pred: Optional[torch.Tensor], logits: Optional[torch.Tensor],
+                      Cin: int, H: int, W: int, C: int) -> None:
+    """linear_eval_rows for GN-LeNet (include/niidmix.h, niidmix_gnlenet_eval_rows_f32): job i scores
+    row rows[i] of theta (the model's 14 parameter tensors, P columns) on data[seg_start[i] .. +
+    seg_len[i]), data [S, Cin * H * W].  logits: None or fp32 [n_jobs, >= max_len, C], the
+    classifier's output before log_softmax.  The scratch buffer comes from torch's caching
+    allocator.  The index tensors' CONTENTS are not checked here."""
+    Cin, H, W, C, max_len = int(Cin), int(H), int(W), int(C), int(max_len)
+    _req(Cin >= 1 and H >= 1 and W >= 1 and C >= 1, "Cin, H, W and C must be >= 1")
+    _req(max_len >= 0, "max_len must be >= 0")
+    _gnlenet_limits(Cin, H, W, C)
+    p = gnlenet_sizes(Cin, H, W, C)[1]
+    n = _eval_rows_args(theta, data, labels, rows, seg_start, seg_len, max_len, loss_sum, correct,
+                        pred, logits, C, f"P = {p}", p, "Cin * H * W", Cin * H * W)
+    dev = theta.device
     nbytes = max(16, int(_lib.lib.niidmix_gnlenet_eval_rows_scratch_bytes(n, max_len, Cin, H, W, C)))
     scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
     rc = _lib.lib.niidmix_gnlenet_eval_rows_f32(
@@ -782,31 +809,13 @@ def gnlenet_nll_grad_rows(theta: torch.Tensor, data: torch.Tensor, labels: torch
     checked here (niidmix.train.DeviceTrainer checks them once)."""
     Cin, H, W, C = int(Cin), int(H), int(W), int(C)
     _req(Cin >= 1 and H >= 1 and W >= 1 and C >= 1, "Cin, H, W and C must be >= 1")
-    _req(C <= 1024 and Cin <= 4 and 15 <= H <= 64 and 15 <= W <= 64,
-         "unsupported shape: the kernel holds C <= 1024, Cin <= 4, 15 <= H, W <= 64")
-    _, p = gnlenet_sizes(Cin, H, W, C)
-    _slab("theta", theta)
-    _slab("grad", grad)
-    _req(theta.shape[1] == p and grad.shape[1] == p,
-         f"theta and grad: expected P = {p} columns, got {theta.shape[1]} and {grad.shape[1]}")
-    _slab("data", data, cols=Cin * H * W)
-    _req(data.is_contiguous(), "data: expected a contiguous [S, Cin * H * W] tensor")
-    dev = theta.device
-    _req(grad.device == dev and data.device == dev, "theta, grad and data must be on the same device")
-    _vec("labels", labels, torch.int32, dev, data.shape[0])
-    _vec("rows", rows, torch.int32, dev)
-    n = rows.numel()
-    _vec("batch_len", batch_len, torch.int32, dev, n)
-    _req(batch_idx.device == dev and batch_idx.dtype == torch.int32 and batch_idx.dim() == 2
-         and batch_idx.is_contiguous() and batch_idx.shape[0] == n,
-         f"batch_idx: expected a contiguous int32 [{n}, b_max] tensor on {dev}")
-    _vec("loss", loss, torch.float32, dev, n)
-    _req(n <= theta.shape[0] and n <= grad.shape[0], "more rows listed than theta or grad has")
-    _req(not _hits(grad, theta) and not _hits(loss, theta), "grad or loss overlaps theta")
+    _gnlenet_limits(Cin, H, W, C)
+    p = gnlenet_sizes(Cin, H, W, C)[1]
+    n = _grad_rows_args(theta, data, labels, batch_idx, batch_len, rows, grad, loss, f"P = {p}", p,
+                        "Cin * H * W", Cin * H * W, apart=True)
     if n == 0:
         return
-    b_max = batch_idx.shape[1]
-    _req(b_max >= 1, "batch_idx: b_max must be >= 1")
+    dev, b_max = theta.device, batch_idx.shape[1]
     nbytes = max(16, int(_lib.lib.niidmix_gnlenet_nll_grad_rows_scratch_bytes(n, b_max, Cin, H, W, C)))
     scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
     rc = _lib.lib.niidmix_gnlenet_nll_grad_rows_f32(

@@ -102,11 +102,11 @@ def test_float64_forward_reproduces_the_reference(name):
 
 
 def test_fixtures_perturb_every_bias_and_affine():
-    from niidmix import evaluate
+    from niidmix import family
     for name in ("gn_lenet_mnist", "gn_lenet_cifar"):
         d = load_fixture(name)
         cin, h, w, c = (int(v) for v in d["shape"])
-        off = evaluate.gn_lenet_offsets(cin, c, sizes(cin, h, w, c)[0])
+        off = family.gn_lenet_offsets(cin, c, sizes(cin, h, w, c)[0])
         for i in (1, 2, 3, 5, 6, 7, 9, 10, 11, 13):
             v = d["theta"][off[i]:off[i + 1]]
             default = 1.0 if i in (2, 6, 10) else 0.0
@@ -114,14 +114,14 @@ def test_fixtures_perturb_every_bias_and_affine():
 
 
 def test_gn_lenet_shape_and_offsets():
-    from niidmix import evaluate, ops, train
+    from niidmix import family, ops
     for cin, c, hw, f, p in [(1, 10, (28, 28), 256, 80554), (1, 10, (24, 24), 256, 80554),
                              (3, 10, (32, 32), 576, 85354), (1, 3, (15, 15), 64, None),
                              (3, 10, (17, 15), 64, None)]:
         mdl = GNLeNet(cin, c, hw)
-        assert evaluate.gn_lenet_shape(mdl) == (cin, c, f)
-        assert train.linear_shape(mdl) is None
-        off = evaluate.gn_lenet_offsets(cin, c, f)
+        assert family.gn_lenet_shape(mdl) == (cin, c, f)
+        assert family.linear_shape(mdl) is None
+        off = family.gn_lenet_offsets(cin, c, f)
         ps = list(mdl.parameters())
         assert len(off) == 15 and off[0] == 0
         assert [off[i + 1] - off[i] for i in range(14)] == [q.numel() for q in ps]
@@ -129,19 +129,19 @@ def test_gn_lenet_shape_and_offsets():
         assert ops.gnlenet_sizes(cin, hw[0], hw[1], c) == (f, off[-1])
         if p is not None:
             assert off[-1] == p
-    assert evaluate.gn_lenet_shape(torch.nn.Linear(4, 3)) is None
+    assert family.gn_lenet_shape(torch.nn.Linear(4, 3)) is None
     mdl = GNLeNet()
     mdl.features[2].weight.requires_grad_(False)
-    assert evaluate.gn_lenet_shape(mdl) is None                    # not trainable
-    assert evaluate.gn_lenet_shape(GNLeNet().double()) is None     # not fp32
+    assert family.gn_lenet_shape(mdl) is None                    # not trainable
+    assert family.gn_lenet_shape(GNLeNet().double()) is None     # not fp32
     mdl = GNLeNet()
     mdl.features[4] = torch.nn.Conv2d(32, 32, 3, padding=1)
-    assert evaluate.gn_lenet_shape(mdl) is None                    # a 3 x 3 convolution
+    assert family.gn_lenet_shape(mdl) is None                    # a 3 x 3 convolution
     mdl = GNLeNet()
     mdl.extra = torch.nn.Parameter(torch.ones(1))
-    assert evaluate.gn_lenet_shape(mdl) is None                    # a fifteenth tensor
+    assert family.gn_lenet_shape(mdl) is None                    # a fifteenth tensor
     # the group count is not in the shapes: the forward probe's business (test_gpu_eval_gnlenet)
-    assert evaluate.gn_lenet_shape(GNLeNet(groups=4)) == (1, 10, 256)
+    assert family.gn_lenet_shape(GNLeNet(groups=4)) == (1, 10, 256)
 
 
 class Net(torch.nn.Module):
@@ -194,9 +194,9 @@ def test_mixed_and_misshapen_lists_are_refused():
 
 def test_wrong_sample_shape_is_refused():
     """A set's samples must be [Cin, H, W] images that give the classifier's F."""
-    from niidmix import evaluate
+    from niidmix import evaluate, family
     ev = evaluate.DeviceEvaluator(_params(), device="cpu")
-    spec = ("gn-lenet", (1, 10, 256))
+    spec = (family.GN_LENET, (1, 10, 256))
 
     def st(shape, m=3):
         x = torch.zeros((m,) + shape)
@@ -212,9 +212,9 @@ def test_wrong_sample_shape_is_refused():
     bad.hi = 10
     with pytest.raises(ValueError, match="device-evaluation.*label"):
         ev._check(bad, spec, "the test set")
-    assert ev._check(st((784,)), ("linear", (784, 10)), "the test set") == (784, 10)
+    assert ev._check(st((784,)), (family.LINEAR, (784, 10)), "the test set") == (784, 10)
     with pytest.raises(ValueError, match="device-evaluation"):
-        ev._check(st((1, 28, 28)), ("linear", (783, 10)), "the test set")
+        ev._check(st((1, 28, 28)), (family.LINEAR, (783, 10)), "the test set")
 
 
 def test_gnlenet_eval_argument_errors_without_gpu():

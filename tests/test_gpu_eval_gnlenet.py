@@ -190,11 +190,11 @@ def test_determinism_and_independence(shape, gpu):
 def test_nan_stays_in_its_row(gpu):
     """A NaN in row 1's conv2.w: a NaN loss in the jobs that list row 1, the others bitwise as
     without it."""
-    from niidmix import evaluate, ops  # noqa: F401
+    from niidmix import family, ops  # noqa: F401
     d = _case((1, 28, 28, 10))
     clean = _launch(d, gpu)
     theta = d["theta"].clone()
-    off = evaluate.gn_lenet_offsets(1, 10, 256)
+    off = family.gn_lenet_offsets(1, 10, 256)
     theta[1, off[4] + 12345] = float("nan")
     loss, correct, pred, logits, _, _ = _launch(d, gpu, theta=theta)
     for i, (r, s, n) in enumerate(JOBS):
@@ -207,9 +207,9 @@ def test_nan_stays_in_its_row(gpu):
 
 def test_ties_take_the_lowest_index(gpu):
     """Classes 1 and 3 with identical classifier rows and a bias that wins every sample."""
-    from niidmix import evaluate, ops  # noqa: F401
+    from niidmix import family, ops  # noqa: F401
     d = _case((1, 28, 28, 10))
-    off = evaluate.gn_lenet_offsets(1, 10, 256)
+    off = family.gn_lenet_offsets(1, 10, 256)
     theta = d["theta"].clone()
     theta[0, off[12] + 3 * 256:off[12] + 4 * 256] = theta[0, off[12] + 256:off[12] + 2 * 256]
     theta[0, off[13] + 1] = theta[0, off[13] + 3] = 50.0
@@ -332,14 +332,14 @@ def test_resident_slab_is_read_in_place(gpu):
 
 def test_probe_refuses_another_group_count(gpu):
     """GroupNorm(4, .) has GN-LeNet's parameter shapes: only the forward probe can tell."""
-    from niidmix import evaluate
+    from niidmix import evaluate, family
 
     class FourGroups(th.GNLeNet):
         def __init__(self):
             super().__init__(groups=4)
     params = _params()
     nodes, tests = _nodes(params, FourGroups)
-    assert evaluate.gn_lenet_shape(nodes[0]["model"]) == (1, 10, 256)
+    assert family.gn_lenet_shape(nodes[0]["model"]) == (1, 10, 256)
     ev = evaluate.DeviceEvaluator(params).register_sets(test=tests)
     with pytest.raises(ValueError, match="device-evaluation.*GroupNorm"):
         ev.accuracy(nodes, "test")

@@ -249,13 +249,12 @@ def test_row_list_chunking():
 
 
 def test_header_and_signatures_declare_the_entry():
-    from niidmix import _lib, evaluate, train
+    from niidmix import _lib, evaluate
     assert _lib.lib.niidmix_abi_version() == 6
     text = open(os.path.join(REPO, "include", "niidmix.h")).read()
     assert re.search(r"^int niidmix_gnlenet_nll_grad_rows_f32\(", text, re.M)
     assert re.search(r"^int64_t niidmix_gnlenet_nll_grad_rows_scratch_bytes\(", text, re.M)
     assert "niidmix_gnlenet_nll_grad_rows_f32" in _lib.SIGNATURES
     assert "niidmix_gnlenet_nll_grad_rows_scratch_bytes" in _lib.SIGNATURES
-    # the shape helpers moved to niidmix.train; evaluate's names stay importable
-    assert evaluate.gn_lenet_shape is train.gn_lenet_shape
-    assert evaluate.gn_lenet_offsets is train.gn_lenet_offsets
+    # the shape helpers live in niidmix.family; evaluate keeps no alias of them
+    assert not hasattr(evaluate, "gn_lenet_shape") and not hasattr(evaluate, "gn_lenet_offsets")
