@@ -6,6 +6,7 @@ The library is compiled with hipcc for gfx950 only, -ffp-contract=off (the exact
 separate mul/add roundings; fast kernels use explicit fmaf).  The .so lands next to this file so it
 travels with the repository snapshot to the GPU box (it is git-ignored, not gpurun-ignored).
 """
+import glob
 import os
 import shutil
 import subprocess
@@ -16,7 +17,7 @@ ROOT = os.path.dirname(PKG_DIR)                       # non-iid-topology-simulat
 REPO = os.path.dirname(ROOT)
 CSRC = os.path.join(ROOT, "csrc")
 LIB = os.path.join(PKG_DIR, "libniidmix.so")
-SOURCES = [os.path.join(CSRC, "niidmix.hip")]
+SOURCES = [os.path.join(CSRC, "niidmix.hip")]      # the one translation unit; it includes csrc/*.inc
 HEADERS = [os.path.join(REPO, "include", "niidmix.h")]
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
@@ -30,11 +31,17 @@ def _hipcc():
     raise RuntimeError("hipcc not found: the niidmix HIP library cannot be built")
 
 
+def dependencies():
+    """Every file the library is compiled from: the root source, the csrc/*.inc it includes and
+    the public header."""
+    return SOURCES + sorted(glob.glob(os.path.join(CSRC, "*.inc"))) + HEADERS
+
+
 def needs_build():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    return any(os.path.getmtime(s) > t for s in SOURCES + HEADERS)
+    return any(os.path.getmtime(s) > t for s in dependencies())
 
 
 def build(force=False, verbose=True):

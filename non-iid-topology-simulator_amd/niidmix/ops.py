@@ -1257,7 +1257,7 @@ class Mixer:
 
 
 def b6_fits(n, x=None):
-    """The bf16x6 GEMM's limits (niidmix_mix_dense_bf16x6_f32, niidmix.hip:4428): the split W
+    """The bf16x6 GEMM's limits (niidmix_mix_dense_bf16x6_f32 in csrc/niidmix.hip): the split W
     (2 B x niidmix_dense_split_elems(n)) and 16 rows of x's leading dimension below 2^31 B.  Host
     arithmetic only (no GPU call)."""
     lim = 0x7fffffff
