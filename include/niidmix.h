@@ -27,7 +27,9 @@
  * niidmix_linear_nll_grad_rows_scratch_elems added (local training of a linear classifier on the
  * device: forward, loss and backward; a pure addition, the version is unchanged);
  * niidmix_grad_segment_mean_sgd_step_f32 added (the clique gradient mean fused with the optimizer
- * step, for --clique-gradient under --device-training; a pure addition too).
+ * step, for --clique-gradient under --device-training; a pure addition too);
+ * niidmix_sample_step_mean_update_f32 added (the 'sample' topology's step, average and broadcast
+ * in one launch, for --device-training-sample; a pure addition too).
  * ABI 5: niidmix_dense_split_elems / niidmix_dense_split_w /
  * niidmix_mix_dense_bf16x6_f32 added (the dense GEMM on the bf16 matrix cores, fp32-accurate by
  * three-term splitting); niidmix_mix_strip_f32 refuses a strip that does not fit the device's LDS.
@@ -447,6 +449,53 @@ int niidmix_grad_segment_mean_sgd_step_f32(float *p, int64_t ld_p, const float *
                                            const int32_t *seg_ptr, const int32_t *seg_row,
                                            int64_t n_members, float neg_lr, float momentum, int first,
                                            void *stream);
+
+/* The 'sample' topology's round on device-resident parameters (niidmix.train.DeviceTrainer under
+ * --device-training-sample) in one launch: the optimizer step of the k sampled rows, their average
+ * setup.model.average(models, [1/k]*k) in the sample's order, and update_models of EVERY row
+ * (d_sgd.py:236-250).  Per column:
+ *   for j in 0..k-1, r = active[j]:
+ *     b   = g[r]                                if momentum == 0 or first[j] != 0
+ *         = fl(fl(momentum * buf[r]) + g[r])    otherwise       (two roundings, no FMA)
+ *     if momentum != 0: buf[r] = b                              (a copy keeps -0.0)
+ *     t_j = fma(neg_lr, b, x[r])                                (one rounding)
+ *   acc = fl(t_0 * 0);  for j in 0..k-1: acc = fl(acc + fl(w * t_j))     (no FMA, in this order)
+ *   for every row i: y[i] = fl(fl(s_i * 0) + acc),  s_i = t_j if i == active[j], else x[i]
+ * with w = fp32(1/k) (1/k computed in double, then rounded).  Bit for bit
+ * niidmix_sgd_step_rows_f32 / niidmix_sgd_momentum_step_rows_f32 over the active rows, then
+ * niidmix_mix_csr_f32 (NIIDMIX_MODE_EXACT | NIIDMIX_FLAG_AVERAGE_ONLY, one output row) over them,
+ * then niidmix_update_rows_f32, except that x is not written: the stepped parameters exist only
+ * inside the launch.  g is not written either; rows of buf that are not listed, and columns from
+ * ncols to the leading dimension of y and buf, are untouched.
+ *   x      [n_rows, ld_x] parameters before the round (device)
+ *   y      [n_rows, ld_y] parameters after it (device), must not overlap x
+ *   g      [*, ld_g] gradients (device), buf [*, ld_b] momentum buffers (device; NULL, 0 when
+ *          momentum == 0)
+ *   active [k] int32 distinct rows in the sample's order (device)
+ *   first  [k] int32, non-zero where the row takes its first momentum step (device; NULL when
+ *          momentum == 0)
+ * How the last line gets s_i of a sampled row: a thread owns its columns and walks the rows
+ * itself, so every element of y and buf has exactly one writer and no thread reads what another
+ * writes.  fl(s_i * 0) matters only through its sign and finiteness, and those can show only
+ * when acc is +-0, inf or NaN: a finite non-zero acc means every t_j (hence every sampled x[r])
+ * was finite, and fl(+-0 + acc) = acc for sampled and other rows alike.  So the walk over all
+ * rows uses x[i] for every row, and only a thread whose acc is +-0, inf or NaN goes over the
+ * sample once more and recomputes t_j from x[r] and b (g[r], or buf[r] as it has just written it).
+ * There is neither a row -> slot map nor a stash in y.  Traffic per node-parameter: 4 (2 n_rows +
+ * 2k) B without momentum, + 4k B for the buffer written, + 4k B more where it is read, against
+ * 4 (2 n_rows + 4k / 5k / 6k) B for the three calls.
+ * float4 accesses when ncols and the leading dimensions are multiples of 4 and the pointers 16-B
+ * aligned, scalar ones otherwise.
+ * Range checks: the lists are on the device and are not read by the launcher.  x and y are taken
+ * over all n_rows rows; g and buf over the least k distinct rows can span, (k - 1) * ld + ncols
+ * elements.  NIIDMIX_EALIAS: y overlaps x, g or buf, or buf overlaps x or g.  NIIDMIX_EINVAL: a null
+ * pointer (buf and first only when momentum != 0), a negative size, k < 1, k > n_rows, a leading
+ * dimension below ncols. */
+int niidmix_sample_step_mean_update_f32(const float *x, int64_t ld_x, float *y, int64_t ld_y,
+                                        const float *g, int64_t ld_g, float *buf, int64_t ld_b,
+                                        const int32_t *active, const int32_t *first, float w,
+                                        float neg_lr, float momentum, int64_t ncols, int64_t n_rows,
+                                        int64_t k, void *stream);
 
 /* Local training of a linear classifier on the listed rows: forward, mean NLL loss and backward of
  * the reference's linear model (setup/model/linear.py: one nn.Linear(K, C), log_softmax, nll_loss)

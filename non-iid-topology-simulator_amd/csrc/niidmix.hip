@@ -32,8 +32,9 @@
 //   row utilities      k_stream_copy, k_mean_cols, k_row_dist2,    niidmix_stream_copy_f32, _mean_rows_f32,
 //                      k_grad_segment_mean, k_update_rows,         _grad_segment_mean[_blocked]_f32,
 //                      k_sgd_step_rows, k_sgd_momentum_step_rows,  _update_rows_f32, _sgd_step_rows_f32,
-//                      k_grad_segment_mean_sgd_step                _sgd_momentum_step_rows_f32,
-//                                                                  _grad_segment_mean_sgd_step_f32
+//                      k_grad_segment_mean_sgd_step,               _sgd_momentum_step_rows_f32,
+//                      k_sample_step_mean_update                   _grad_segment_mean_sgd_step_f32,
+//                                                                  _sample_step_mean_update_f32
 //   linear model       k_lin_logits, k_lin_softmax, k_lin_dw,      niidmix_linear_nll_grad_rows_f32,
 //                      k_lin_eval, k_lin_eval_sum                  niidmix_linear_eval_rows_f32
 //   model_gnlenet.inc  k_gnl_eval, k_gnl_grad_sample / _conv / _fc niidmix_gnlenet_eval_rows_f32,
@@ -4006,6 +4007,143 @@ __global__ __launch_bounds__(256) void k_sgd_momentum_step_rows(float *__restric
 }
 
 // ----------------------------------------------------------------------------------------------
+// The 'sample' topology's round under --device-training-sample in one launch: the optimizer step of
+// the k active rows, their weighted average in sample order and update_models of EVERY row, bit
+// for bit k_sgd_step_rows / k_sgd_momentum_step_rows over `active`, then k_mix_csr (EXACT |
+// AVERAGE_ONLY, one output row) over them, then k_update_rows.  Per column
+//   for j < k, r = active[j]:  b = g[r] (momentum 0, or first[j]) else fl(fl(momentum * buf[r]) + g[r])
+//                              buf[r] = b (MOM);  t_j = fma(neg_lr, b, x[r])
+//   acc = fl(t_0 * 0);  acc = fl(acc + fl(w * t_j)) in order
+//   y[i] = fl(fl(s_i * 0) + acc) for every row, s_i = t_j when i == active[j], else x[i]
+// A thread owns V columns and walks the rows itself, so every element of y and buf has one writer
+// and no thread reads what another one writes; x and g are only read.  The last line needs t_j
+// again, but only its sign and finiteness, and only when they can show:
+//   acc finite and non-zero  =>  every t_j, hence every active x[r], is finite (one that is not
+//                                makes acc inf or NaN for good), so fl(+-0 + acc) = acc on active
+//                                and inactive rows alike: the walk over all rows reads x[i] and
+//                                needs to know nothing about the sample
+//   otherwise (acc +-0, inf or NaN)  the same walk, then the active rows once more: t_j again from
+//                                x[r] and b (g[r], or buf[r] as this thread has just written it)
+// so there is neither a row -> slot map nor a stash in y; the second walk over the sample is taken
+// by a wave when any of its lanes needs it (the descriptors are fetched by every lane) and stores
+// from those lanes only.  U rows' loads are in flight at a time.  Traffic per node-parameter:
+// 4 (2N + 2k) B, + 4k B for the buffer written, + 4k B more where it is read (first[j] == 0).
+template <int V, int U, bool MOM>
+__global__ __launch_bounds__(256) void k_sample_step_mean_update(
+        const float *__restrict__ x, int64_t ld_x, float *__restrict__ y, int64_t ld_y,
+        const float *__restrict__ g, int64_t ld_g, float *buf, int64_t ld_b,
+        const int32_t *__restrict__ active, const int32_t *__restrict__ first, float w, float neg_lr,
+        float momentum, int64_t ncols, int64_t n_rows, int64_t k, int64_t n_chunks) {
+#pragma clang fp contract(off)           // every product and sum below is rounded on its own
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    const int lane = threadIdx.x & (kWave - 1);
+    for (int64_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
+        const int64_t c = (chunk * blockDim.x + threadIdx.x) * V;
+        const bool ok = c < ncols;               // V == 4 only when ncols % 4 == 0: all-in or all-out
+        const int64_t cc = ok ? c : 0;           // loads stay unconditional
+        float acc[V];
+#pragma unroll
+        for (int e = 0; e < V; ++e) acc[e] = 0.f;
+        for (int64_t kb = 0; kb < k; kb += 64) {
+            const int cnt = k - kb < 64 ? (int)(k - kb) : 64;
+            const int d_row = active[kb + (lane < cnt ? lane : cnt - 1)];
+            const int d_first = MOM ? first[kb + (lane < cnt ? lane : cnt - 1)] : 1;
+            for (int j = 0; j < cnt; j += U) {
+                // the sample's rows are distinct: a batch's loads (the tail repeats row cnt - 1)
+                // all precede its stores
+                float xv[U][V], bv[U][V], mv[U][V];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const int jj = j + u < cnt ? j + u : cnt - 1;
+                    const int64_t r = __builtin_amdgcn_readlane(d_row, jj);
+                    ldv<V>(x + r * ld_x + cc, xv[u]);
+                    ldv_nt<V>(g + r * ld_g + cc, bv[u]);
+                    if constexpr (MOM)
+                        if (__builtin_amdgcn_readlane(d_first, jj) == 0) ldv_nt<V>(buf + r * ld_b + cc, mv[u]);
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    if (j + u >= cnt) continue;
+                    const int64_t r = __builtin_amdgcn_readlane(d_row, j + u);
+                    if constexpr (MOM) {
+                        if (__builtin_amdgcn_readlane(d_first, j + u) == 0) {
+#pragma unroll
+                            for (int e = 0; e < V; ++e) {
+                                const float mb = momentum * mv[u][e];    // rounded, then a rounded add
+                                bv[u][e] = mb + bv[u][e];
+                            }
+                        }
+                        if (ok) {
+                            if constexpr (V == 4) {
+                                const f4 o = {bv[u][0], bv[u][1], bv[u][2], bv[u][3]};
+                                __builtin_nontemporal_store(o, reinterpret_cast<f4 *>(buf + r * ld_b + c));
+                            } else {
+                                __builtin_nontemporal_store(bv[u][0], buf + r * ld_b + c);
+                            }
+                        }
+                    }
+#pragma unroll
+                    for (int e = 0; e < V; ++e) {
+                        const float t = __builtin_fmaf(neg_lr, bv[u][e], xv[u][e]);
+                        if (kb == 0 && j + u == 0) acc[e] = t * 0.f;
+                        const float wt = w * t;
+                        acc[e] = acc[e] + wt;
+                    }
+                }
+            }
+        }
+        bool plain = true;                       // fl(+-0 + acc) == acc whatever the row holds;
+                                                 // (a lane past ncols stores nothing: plain too)
+#pragma unroll
+        for (int e = 0; e < V; ++e) plain = plain && acc[e] != 0.f && __builtin_fabsf(acc[e]) < __builtin_inff();
+        plain = plain || !ok;
+        for (int64_t i = 0; i < n_rows; i += U) {
+            float xv[U][V];
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                ldv_nt<V>(x + (i + u < n_rows ? i + u : n_rows - 1) * ld_x + cc, xv[u]);
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+#pragma unroll
+                for (int e = 0; e < V; ++e) xv[u][e] = xv[u][e] * 0.f + acc[e];
+                if (ok && i + u < n_rows) {
+                    if constexpr (V == 4) {
+                        const f4 o = {xv[u][0], xv[u][1], xv[u][2], xv[u][3]};
+                        __builtin_nontemporal_store(o, reinterpret_cast<f4 *>(y + (i + u) * ld_y + c));
+                    } else {
+                        __builtin_nontemporal_store(xv[u][0], y + (i + u) * ld_y + c);
+                    }
+                }
+            }
+        }
+        if (__builtin_amdgcn_ballot_w64(!plain) == 0) continue;      // wave-uniform
+        for (int64_t kb = 0; kb < k; kb += 64) {
+            const int cnt = k - kb < 64 ? (int)(k - kb) : 64;
+            const int d_row = active[kb + (lane < cnt ? lane : cnt - 1)];
+            for (int j = 0; j < cnt; ++j) {
+                const int64_t r = __builtin_amdgcn_readlane(d_row, j);
+                float xv[V], bv[V];
+                ldv<V>(x + r * ld_x + cc, xv);
+                ldv<V>((MOM ? buf + r * ld_b : g + r * ld_g) + cc, bv);
+#pragma unroll
+                for (int e = 0; e < V; ++e) {
+                    const float t = __builtin_fmaf(neg_lr, bv[e], xv[e]);
+                    xv[e] = t * 0.f + acc[e];
+                }
+                if (ok && !plain) {
+                    if constexpr (V == 4) {
+                        const f4 o = {xv[0], xv[1], xv[2], xv[3]};
+                        __builtin_nontemporal_store(o, reinterpret_cast<f4 *>(y + r * ld_y + c));
+                    } else {
+                        __builtin_nontemporal_store(xv[0], y + r * ld_y + c);
+                    }
+                }
+            }
+        }
+    }
+}
+
+// ----------------------------------------------------------------------------------------------
 // Segment gradient mean fused with the SGD step (--clique-gradient under --device-training):
 // k_grad_segment_mean followed by k_sgd_step_rows / k_sgd_momentum_step_rows over the member rows,
 // bit for bit, without the averaged [N, P] slab in between.  Per segment and column
@@ -5713,6 +5851,42 @@ int niidmix_grad_segment_mean_sgd_step_f32(float *p, int64_t ld_p, const float *
     hipLaunchKernelGGL(kfn, grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p, ld_p, g, ld_g,
                        mom ? buf : nullptr, ld_b, ncols, n_seg, seg_ptr, seg_row, neg_lr, momentum, n_chunks);
     return check_launch("k_grad_segment_mean_sgd_step");
+}
+
+int niidmix_sample_step_mean_update_f32(const float *x, int64_t ld_x, float *y, int64_t ld_y,
+                                        const float *g, int64_t ld_g, float *buf, int64_t ld_b,
+                                        const int32_t *active, const int32_t *first, float w,
+                                        float neg_lr, float momentum, int64_t ncols, int64_t n_rows,
+                                        int64_t k, void *stream) {
+    if (ncols < 0 || n_rows < 0 || k < 0) return set_error(NIIDMIX_EINVAL, "negative size");
+    if (k < 1 || k > n_rows) return set_error(NIIDMIX_EINVAL, "k %lld not in 1..n_rows", (long long)k);
+    const bool mom = momentum != 0.f;            // buf and first are not touched without momentum
+    if (!x || !y || !g || !active || (mom && (!buf || !first))) return set_error(NIIDMIX_EINVAL, "null pointer");
+    if (ncols == 0) return NIIDMIX_OK;
+    if (int rc = check_ld(ld_x, ld_y, ncols, "ncols")) return rc;
+    if (int rc = check_ld(ld_g, mom ? ld_b : ld_g, ncols, "ncols")) return rc;
+    // x and y are walked over all n_rows rows; `active` lives on the device: k distinct rows of g
+    // and buf reach at least row k - 1
+    const int64_t ext_x = slab_extent(n_rows, ld_x, ncols), ext_y = slab_extent(n_rows, ld_y, ncols);
+    const int64_t ext_g = slab_extent(k, ld_g, ncols), ext_b = mom ? slab_extent(k, ld_b, ncols) : 0;
+    if (overlaps(x, ext_x, y, ext_y)) return set_error(NIIDMIX_EALIAS, "x and y overlap: the round is out-of-place");
+    if (overlaps(g, ext_g, y, ext_y)) return set_error(NIIDMIX_EALIAS, "g and y overlap");
+    if (mom && overlaps(buf, ext_b, y, ext_y)) return set_error(NIIDMIX_EALIAS, "buf and y overlap");
+    if (mom && overlaps(buf, ext_b, x, ext_x)) return set_error(NIIDMIX_EALIAS, "buf and x overlap");
+    if (mom && overlaps(buf, ext_b, g, ext_g)) return set_error(NIIDMIX_EALIAS, "buf and g overlap");
+    const int vw = vec_width({ncols, ld_x, ld_y, ld_g, mom ? ld_b : 0}, {x, y, g, mom ? buf : nullptr}) == 4 ? 4 : 1;
+    // a thread per vw columns walks every row: one-wave blocks until there are columns for 512
+    // blocks of four waves
+    const int64_t lanes = (ncols + vw - 1) / vw;
+    const int tpb = lanes >= 256 * 512 ? 256 : 64;
+    const int64_t n_chunks = (lanes + tpb - 1) / tpb;
+    auto kfn = pick<4, 1>(vw, [&](auto V) { return pick<true, false>(mom, [&](auto M) {
+        return k_sample_step_mean_update<V(), V() == 4 ? 8 : 16, M()>; }); });
+    hipLaunchKernelGGL(kfn, dim3((unsigned)(n_chunks < kMaxGrid ? n_chunks : kMaxGrid)), dim3(tpb), 0,
+                       reinterpret_cast<hipStream_t>(stream), x, ld_x, y, ld_y, g, ld_g,
+                       mom ? buf : nullptr, ld_b, active, mom ? first : nullptr, w, neg_lr, momentum,
+                       ncols, n_rows, k, n_chunks);
+    return check_launch("k_sample_step_mean_update");
 }
 
 // K-chunks of k_lin_logits at most: enough (row, chunk) blocks to fill the device at few rows; a

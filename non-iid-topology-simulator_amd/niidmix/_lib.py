@@ -94,6 +94,9 @@ SIGNATURES = {
     "niidmix_grad_segment_mean_sgd_step_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64,
                                                               _i64, _vp, _vp, _i64, ctypes.c_float,
                                                               ctypes.c_float, ctypes.c_int, _vp]),
+    "niidmix_sample_step_mean_update_f32": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
+                                                           _vp, _vp, ctypes.c_float, ctypes.c_float,
+                                                           ctypes.c_float, _i64, _i64, _i64, _vp]),
     "niidmix_linear_nll_grad_rows_scratch_elems": (_i64, [_i64, _i64, _i64]),
     "niidmix_linear_nll_grad_rows_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64,
                                                         _vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp]),

@@ -21,7 +21,8 @@ Gradient averaging (--clique-gradient, --unbiased-gradient) also runs on the GPU
 (niidmix.gradient); local training, optimizer steps and sampling stay on the CPU as in the reference.
 With --device-training (params['algorithm']['device-training'], opt-in) a linear model's local
 training runs on the device too: gradient, step and mixing never leave HBM (niidmix.train);
---device-training-gn-lenet does the same for GN-LeNet models.
+--device-training-gn-lenet does the same for GN-LeNet models, and --device-training-sample for
+rounds of the 'sample' topology (the other two flags refuse it).
 With --device-evaluation (params['algorithm']['device-evaluation'], opt-in) the logger's accuracy
 and loss events of linear and GN-LeNet models are computed on the device as well (niidmix.evaluate).
 """
@@ -769,6 +770,18 @@ def _device_training_step(state, params, rundir):
     nodes = state["nodes"]
     synchronize()
     tr = _trainer(nodes, state["topology"], params)
+    if tr.sample != train.sample_run(params):
+        raise ValueError(f"{train.FLAG_SAMPLE}: the run changed between a sample round and a graph "
+                         "round under a live device trainer: not supported")
+    if tr.sample:
+        # --device-training-sample (d_sgd.py:236-250): only the sample trains and steps, its
+        # average replaces every model (niidmix.train.DeviceTrainer.sample_round)
+        active = get_sample(state, params, state["step"])
+        logging.info("  gradient + SGD step + average of %d sampled nodes (GPU, device training)",
+                     len(active))
+        losses, epoch_done = tr.sample_round(nodes, active, params)
+        state["step"] += 1
+        return state, losses, epoch_done, active
     logging.info("  gradient + SGD step + mixing (GPU, %s, device training)", _mode(params))
     losses, epoch_done = tr.round(nodes, state["topology"], params, _mode(params))
     if params["topology"]["name"] == "random-graph" and params["topology"]["randomize"]:
@@ -1098,7 +1111,8 @@ def main(argv=None):
     ap.add_argument("--mixing-mode", choices=["exact", "fast"], default="exact",
                     help="exact: bit-identical to the reference loop; fast: clique/MFMA kernels")
     ap.add_argument("--device-training", action="store_const", const=True, default=False,
-                    help="linear models only (GN-LeNet: --device-training-gn-lenet): local training "
+                    help="linear models only (GN-LeNet: --device-training-gn-lenet; the 'sample' "
+                         "topology: --device-training-sample): local training "
                          "(forward, loss, backward), the SGD step and the mixing all run on the "
                          "device; same samples as the CPU path, gradients within 1e-5 "
                          "(condition-aware) of it, not bit-identical")
@@ -1107,6 +1121,14 @@ def main(argv=None):
                          "keys): forward, loss and backward of every node in HIP kernels; same "
                          "samples as the CPU path, gradients within 4 x the error of torch's own "
                          "fp32 autograd, not bit-identical")
+    ap.add_argument("--device-training-sample", action="store_const", const=True, default=False,
+                    help="--device-training for runs of the 'sample' topology (sets both keys; "
+                         "the other two flags refuse 'sample'): each round the sampled nodes train "
+                         "and step on the device and their average replaces every model, in HIP "
+                         "kernels; same samples, batches and RNG stream as the CPU path; combines "
+                         "with --device-training-gn-lenet, ignores --clique-gradient and "
+                         "--unbiased-gradient as the reference's sample rounds do; on another "
+                         "topology it is plain --device-training")
     ap.add_argument("--device-evaluation", action="store_const", const=True, default=False,
                     help="linear models only: the logger's train, test, validation and full-train "
                          "accuracy and loss of every logged node (and of the global model) are "
@@ -1134,8 +1156,10 @@ def main(argv=None):
         "batch-size": args.batch_size, "initial-averaging": args.initial_averaging,
         "clique-gradient": args.clique_gradient, "unbiased-gradient": args.unbiased_gradient,
         "mixing-mode": args.mixing_mode, "deferred-writeback": args.deferred_writeback,
-        **({"device-training": True} if args.device_training or args.device_training_gn_lenet else {}),
+        **({"device-training": True} if args.device_training or args.device_training_gn_lenet
+           or args.device_training_sample else {}),
         **({"device-training-gn-lenet": True} if args.device_training_gn_lenet else {}),
+        **({"device-training-sample": True} if args.device_training_sample else {}),
         **({"device-evaluation": True} if args.device_evaluation else {}),
     })
     if args.rundir is None:

@@ -23,6 +23,10 @@ Ops (registered in the `niidmix` namespace, usable as torch.ops.niidmix.*):
   grad_segment_mean_sgd_step(p, g, buf_or_None, seg_ptr, seg_row, neg_lr, momentum, first)
                                                     k_grad_segment_mean_sgd_step (the two above in one
                                                     pass, --clique-gradient under --device-training)
+  sample_step_mean_update(x, out, g, buf_or_None, active, first_or_None, neg_lr, momentum)
+                                                    k_sample_step_mean_update (the 'sample' round:
+                                                    step, average and broadcast in one launch,
+                                                    --device-training-sample)
   mix_csr(..., mode | MEAN)                         per-row gradient mean (unbiased / removed edges)
   linear_nll_grad_rows(theta, data, labels, batch_idx, batch_len, rows, grad, loss, K, C)
                                                     k_lin_logits + k_lin_softmax + k_lin_dw (local
@@ -597,6 +601,41 @@ def grad_segment_mean_sgd_step(p: torch.Tensor, g: torch.Tensor, buf: Optional[t
         seg_row.data_ptr(), seg_row.numel(), float(neg_lr), float(momentum), int(bool(first)),
         _stream(p))
     _lib.check(rc, "niidmix::grad_segment_mean_sgd_step")
+
+
+@torch.library.custom_op("niidmix::sample_step_mean_update", mutates_args=("out", "buf"))
+def sample_step_mean_update(x: torch.Tensor, out: torch.Tensor, g: torch.Tensor,
+                            buf: Optional[torch.Tensor], active: torch.Tensor,
+                            first: Optional[torch.Tensor], neg_lr: float, momentum: float) -> None:
+    """The 'sample' topology's round in one launch: the optimizer step of the rows `active` lists
+    (sgd_step_rows when momentum == 0, buf and first None; else sgd_momentum_step_rows with a
+    per-row `first` flag), their average with weights fp32(1/k) in that order, and update_models
+    of every row, from x into out; bit for bit those ops, mix_csr(EXACT | AVERAGE_ONLY) and
+    update_rows in sequence, but x is not written (include/niidmix.h,
+    niidmix_sample_step_mean_update_f32)."""
+    _slab("x", x)
+    _slab("out", out, rows=x.shape[0], cols=x.shape[1])
+    _slab("g", g, rows=x.shape[0], cols=x.shape[1])
+    _req(out.device == x.device and g.device == x.device, "x, out and g must be on the same device")
+    _vec("active", active, torch.int32, x.device)
+    k = active.numel()
+    _req(1 <= k <= x.shape[0], f"active: expected 1..{x.shape[0]} rows, got {k}")
+    mom = float(momentum) != 0.0
+    _req(not mom or (buf is not None and first is not None), "buf and first: required when momentum != 0")
+    _no_overlap(x, out)
+    _req(not _hits(out, g), "out and g overlap")
+    if mom:
+        _slab("buf", buf, rows=x.shape[0], cols=x.shape[1])
+        _req(buf.device == x.device, "x and buf must be on the same device")
+        _vec("first", first, torch.int32, x.device, n=k)
+        _req(not (_hits(buf, out) or _hits(buf, x) or _hits(buf, g)), "buf overlaps x, out or g")
+    w = float(np.float32(1.0 / k))           # 1/k in double, rounded once (SampleAverage.set_active)
+    rc = _lib.lib.niidmix_sample_step_mean_update_f32(
+        x.data_ptr(), _ld(x), out.data_ptr(), _ld(out), g.data_ptr(), _ld(g),
+        buf.data_ptr() if mom else None, _ld(buf) if mom else 0, active.data_ptr(),
+        first.data_ptr() if mom else None, w, float(neg_lr), float(momentum), x.shape[1], x.shape[0],
+        k, _stream(x))
+    _lib.check(rc, "niidmix::sample_step_mean_update")
 
 
 def _hits(a, b):

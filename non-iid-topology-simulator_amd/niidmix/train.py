@@ -44,6 +44,25 @@ Either way the round equals, bit for bit, the gradient op followed by the refere
 average_gradients, update_gradients and optimizer.step() on the CPU, then the mixing
 (tests/test_gpu_train_gradavg.py).  check_eligible needs the topology for this and refuses, naming
 the flag, when the lists cannot be built.
+
+The 'sample' topology (the reference's federated-averaging baseline, d_sgd.py:157-175, :236-250)
+runs under a third flag, `--device-training-sample` (it sets 'device-training' too and combines
+with the GN-LeNet flag; the other two flags keep refusing 'sample').  DeviceTrainer.sample_round:
+
+    d_sgd.get_sample -> draw() on the active nodes, in the sample's order (inactive nodes draw
+                        nothing) -> indices, active rows and `first` flags in the one H2D copy
+    -> the family's gradient op over the k active rows (jobs in sample order)
+    -> niidmix::sample_step_mean_update      the step of the active rows, their average in sample
+                                             order and update_models of every row in one launch,
+                                             theta[cur] -> theta[1 - cur]; narrow slabs and small
+                                             samples (SAMPLE_FUSED_MIN_COLS, _MIN_SHARE) take the
+                                             three ops it restates, which measure faster there
+                                             (step op, mix_csr | AVERAGE_ONLY, update_rows)
+    -> losses of the active nodes D2H, parameters D2H (synchronous)
+
+A node's first momentum step falls in whichever round first samples it, so the trainer keeps on
+the host which rows have stepped (first_flags) and sends the k flags with the indices.  Gradient
+averaging does not apply and no Mixer is built (the topology is {'edges': {}, 'weights': []}).
 """
 import os
 
@@ -57,7 +76,17 @@ from .topology import to_csr
 
 FLAG = "--device-training"
 FLAG_GN = "--device-training-gn-lenet"
+FLAG_SAMPLE = "--device-training-sample"
 SCRATCH_FRACTION = 0.4   # of the free HBM, for one GN-LeNet gradient call's scratch
+# When a sample round takes the one-launch step + average + broadcast
+# (niidmix::sample_step_mean_update) instead of the three ops it restates: slabs of at least
+# SAMPLE_FUSED_MIN_COLS columns (a thread of that kernel walks all rows of its columns, so few
+# columns cannot fill the device) and a sample of at least SAMPLE_FUSED_MIN_SHARE of the nodes (the
+# launch saves 8 B per sampled node-parameter but streams at about 0.87 of the three kernels'
+# rate).  Measured on one MI355X at N = 1000: slower than the sequence at k = 100 for every width
+# tried, 0.67 x / 0.81 x its time at k = 1000 and 2^20 columns ("The sample round").
+SAMPLE_FUSED_MIN_COLS = 1 << 18
+SAMPLE_FUSED_MIN_SHARE = 0.5
 
 
 def enabled(params):
@@ -66,6 +95,18 @@ def enabled(params):
 
 def gn_enabled(params):
     return bool(params.get("algorithm", {}).get("device-training-gn-lenet"))
+
+
+def sample_run(params):
+    """A run of the 'sample' topology under --device-training-sample: the round of
+    DeviceTrainer.sample_round.  The key alone, on another topology, changes nothing."""
+    return bool(params.get("algorithm", {}).get("device-training-sample")) and \
+        params.get("topology", {}).get("name") == "sample"
+
+
+def flag_of(params):
+    """The flag a refusal names: GN-LeNet's when set, the sample flag on a sample run."""
+    return FLAG_GN if gn_enabled(params) else FLAG_SAMPLE if sample_run(params) else FLAG
 
 
 def padded_ld(p):
@@ -91,7 +132,7 @@ def draw(nodes, params):
     for node in nodes:
         idx = next(node["train-iterator"])
         if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int64 or idx.dim() != 1:
-            raise ValueError(f"{FLAG_GN if gn_enabled(params) else FLAG}: node {node['rank']}'s "
+            raise ValueError(f"{flag_of(params)}: node {node['rank']}'s "
                              "train-iterator yields samples, not "
                              "indices: the flag must be set when init() creates the loaders")
         batches.append(idx)
@@ -104,6 +145,15 @@ def draw(nodes, params):
             node["train-iterator"] = rest
         epoch_done[node["rank"]] = done
     return batches, epoch_done
+
+
+def first_flags(stepped, rows):
+    """Sample rounds with momentum: per row of `rows`, 1 when it has taken no optimizer step yet
+    (torch's SGD clones the gradient into a fresh momentum buffer), else 0; the rows are then
+    recorded in the set `stepped`, which the trainer keeps on the host."""
+    flags = [int(r not in stepped) for r in rows]
+    stepped.update(rows)
+    return flags
 
 
 def grad_plan(n, topology, params, flag):
@@ -139,19 +189,28 @@ def check_eligible(nodes, params, topology=None):
     """The refusals that need no GPU (d_sgd.init calls this): raises ValueError naming the flag.
     Returns (K, C) for linear models and, under --device-training-gn-lenet, (Cin, C, F) for
     GN-LeNet.  --clique-gradient / --unbiased-gradient are accepted when `topology` gives their
-    averaging lists (grad_plan)."""
+    averaging lists (grad_plan).  The 'sample' topology is accepted under --device-training-sample
+    only; such a run ignores the two gradient-averaging flags, as the reference's sample branch
+    does, and needs nothing of `topology`."""
     from . import d_sgd
     alg = params["algorithm"]
     gn_flag = gn_enabled(params)
-    flag = FLAG_GN if gn_flag else FLAG
-    if params["topology"]["name"] == "sample":
-        raise ValueError(f"{flag} does not support the 'sample' topology")
+    flag = flag_of(params)
+    sample = sample_run(params)
+    if params["topology"]["name"] == "sample" and not sample:
+        raise ValueError(f"{flag} does not support the 'sample' topology: it trains on the device "
+                         f"under {FLAG_SAMPLE}")
     env = os.environ.get("NIIDMIX_DEVICES")
     if env and len([i for i in env.split(",") if i.strip()]) > 1:
         raise ValueError(f"{flag} runs on one device; NIIDMIX_DEVICES lists several")
     if not nodes:
         raise ValueError(f"{flag}: no nodes")
-    grad_plan(len(nodes), topology, params, flag)
+    if sample:
+        size = params["topology"].get("sample-size")
+        if not isinstance(size, int) or not 1 <= size <= len(nodes):
+            raise ValueError(f"{flag}: sample-size {size!r} is not in 1..{len(nodes)}")
+    else:
+        grad_plan(len(nodes), topology, params, flag)
     fam, shape = family.family_of(nodes[0]["model"]) or (None, None)
     gn = fam is family.GN_LENET
     lr, mom = float(alg["learning-rate"]), d_sgd._momentum(params)
@@ -202,8 +261,9 @@ class DeviceTrainer:
         from . import d_sgd
         self.shape = check_eligible(nodes, params, topology)
         self.family = family.family_of(nodes[0]["model"])[0]
-        self.flag = FLAG_GN if gn_enabled(params) else FLAG
-        self.scratch_budget = None       # bytes of scratch per GN-LeNet gradient call (None:
+        self.flag = flag_of(params)
+        self.sample = sample_run(params)     # fixed for the trainer's life (d_sgd._trainer)
+        self.scratch_budget = None      # bytes of scratch per GN-LeNet gradient call (None:
         self.last_calls = 0              # SCRATCH_FRACTION of the free HBM); calls of the last round
         self.sizes = None                # the kernel's size arguments (family.sizes), set by _materialise
         self._free_budget = None         # the default budget, measured before the first gradient call
@@ -220,7 +280,8 @@ class DeviceTrainer:
             raise ValueError(f"{self.flag} was switched on while the CPU optimizers hold momentum "
                              "buffers: handing them to the device mid-run is not supported")
         self.params = params
-        plan = grad_plan(self.n, topology, params, self.flag)
+        # a sample run ignores --clique-gradient / --unbiased-gradient (d_sgd.py:236-250)
+        plan = None if self.sample else grad_plan(self.n, topology, params, self.flag)
         self.grad_kind = plan.kind if plan is not None else None     # fixed by params for the run
         # the per-row kinds average into a slab of their own; the clique kind needs none
         self.n_buf = 3 + (self.momentum != 0.0) + (self.grad_kind in ("clique-removed", "unbiased"))
@@ -239,8 +300,15 @@ class DeviceTrainer:
         self.mom_steps = 0
         self.rows = torch.arange(self.n, dtype=torch.int32, device=dev)
         self.loss = torch.empty(self.n, dtype=torch.float32, device=dev)
-        self.idx_host = torch.zeros(self.n * self.b_max + self.n, dtype=torch.int32).pin_memory()
+        # one round's indices, one H2D copy: [n, b_max] sample indices, [n] batch lengths and, for
+        # a sample round (sample_layout), the active rows, their `first` flags and the step lists
+        self.idx_host = torch.zeros(self.n * self.b_max + (4 if self.sample else 1) * self.n,
+                                    dtype=torch.int32).pin_memory()
         self.idx_dev = torch.empty_like(self.idx_host, device=dev)
+        self.stepped_rows = set()     # sample rounds: rows that have taken an optimizer step
+        self.last_first = []          # the `first` flags of the last sample round (tests)
+        self._avg = None              # sample rounds, three-op sequence: the CSR row and the average
+        self.sample_fused = None      # the last sample round took the one launch (sample_round)
         self.fresh = False            # the device parameters are the models' current values
         self.version = None           # NodeSlab.version() the device copy corresponds to
         self.slab = None
@@ -291,30 +359,34 @@ class DeviceTrainer:
     def _gn_need(self, rows):
         return self.family.grad_scratch_bytes(rows, self.b_max, self.sizes)
 
-    def _cut(self):
-        """Rows per call of the gradient kernel: all of them for a family whose calls are not cut,
-        else as many as keep the call's scratch within the budget."""
+    def _cut(self, n):
+        """Rows per call of the gradient kernel over n jobs: all of them for a family whose calls
+        are not cut, else as many as keep the call's scratch within the budget."""
         if not self.family.cut:
-            return self.n
+            return n
         budget = self.scratch_budget
         if budget is None:           # taken once: later rounds see the cached scratch block as used
             if self._free_budget is None:
                 self._free_budget = SCRATCH_FRACTION * torch.cuda.mem_get_info(self.device)[0]
             budget = self._free_budget
-        k = cut_rows(self.n, self._gn_need, budget)
+        k = cut_rows(n, self._gn_need, budget)
         if k is None:
             raise RuntimeError(f"{self.flag}: {self._gn_need(1) / 2**30:.2f} GiB of scratch for one "
                                f"row of {self.b_max} samples exceed the budget of "
                                f"{budget / 2**30:.2f} GiB")
         return k
 
-    def _gradient(self, x, bi, bl):
-        """Gradient and loss of every row of x on this round's batches."""
-        cut = self._cut()
+    def _gradient(self, x, bi, bl, rows=None):
+        """Gradient and loss of the rows `rows` of x (default: every row) on this round's batches,
+        one job per row in the list's order: job j's gradient goes to row rows[j] of self.grad, its
+        loss to self.loss[j]."""
+        rows = self.rows if rows is None else rows
+        n = rows.numel()
+        cut = self._cut(n)
         self.last_calls = 0
-        for a in range(0, self.n, cut):
-            b = min(self.n, a + cut)
-            self.family.grad_rows(x, self.data, self.labels, bi[a:b], bl[a:b], self.rows[a:b],
+        for a in range(0, n, cut):
+            b = min(n, a + cut)
+            self.family.grad_rows(x, self.data, self.labels, bi[a:b], bl[a:b], rows[a:b],
                                   self.grad, self.loss[a:b], self.sizes)
             self.last_calls += 1
 
@@ -358,6 +430,11 @@ class DeviceTrainer:
         return any(id(nd["model"]) in mine for nd in nodes)
 
     def set_topology(self, topology):
+        if self.sample:              # {'edges': {}, 'weights': []}: no graph, no Mixer, no lists
+            self.stepped = self.segments = self.gmean = self.step_rows = None
+            self.topology = topology
+            self.weights_id = id(topology.get("weights")) if topology is not None else None
+            return
         csr = to_csr(topology)
         if csr.n != self.n:
             raise ValueError(f"topology has {csr.n} nodes, {self.n} models given")
@@ -409,8 +486,87 @@ class DeviceTrainer:
     def write_back(self):
         self._host().copy_(self.theta[self.cur])     # D2H, synchronous: the models are current
 
+    def _fill_batches(self, nodes, rows, batches):
+        """The batches of the nodes at slab rows `rows` into the pinned index block, job j = the
+        j-th of them: sample indices offset by the node's own data offset, and the lengths."""
+        nb = self.n * self.b_max
+        bi = self.idx_host[:nb].view(self.n, self.b_max).numpy()
+        bl = self.idx_host[nb:nb + self.n].numpy()
+        for j, (i, idx) in enumerate(zip(rows, batches)):
+            k = idx.numel()
+            if k < 1 or k > self.b_max or int(idx.max()) >= self.offsets[i + 1] - self.offsets[i]:
+                raise ValueError(f"{self.flag}: node {nodes[j]['rank']} drew a batch its train-set or "
+                                 "the batch size does not allow")
+            bi[j, :k] = idx.numpy() + self.offsets[i]
+            bl[j] = k
+
+    def _sample_sequence(self, x, y, active, lists, n_first):
+        """Step, average and broadcast of a sample round as the three ops in sequence (x is
+        stepped in place): what niidmix::sample_step_mean_update restates in one launch."""
+        k = active.numel()
+        if self.momentum != 0.0:
+            for rows, first in ((lists[:n_first], True), (lists[n_first:], False)):
+                if rows.numel():
+                    ops.sgd_momentum_step_rows(x, self.grad, self.mbuf, rows, -self.lr, self.momentum, first)
+        else:
+            ops.sgd_step_rows(x, self.grad, active, -self.lr)
+        if self._avg is None or self._avg[0] != k:
+            import numpy as np
+            self._avg = (k, torch.tensor([0, k], dtype=torch.int64, device=self.device),
+                         torch.full((k,), float(np.float32(1.0 / k)), dtype=torch.float32, device=self.device),
+                         torch.empty((1, self.ld), dtype=torch.float32, device=self.device)[:, :self.p])
+        _, row_ptr, val, avg = self._avg
+        ops.mix_csr(x, row_ptr, active, val, avg, ops.EXACT | ops.AVERAGE_ONLY)
+        ops.update_rows(x, avg[0], y)
+
+    def sample_round(self, nodes, active, params):
+        """One round of the 'sample' topology (d_sgd.py:236-250): the nodes `active` (d_sgd.get_sample,
+        in its order) draw, train and step; their uniform average then replaces every node's model.
+        Returns ({rank: loss}, {rank: epoch_done}) of the active nodes.  Inactive nodes draw
+        nothing and their momentum buffers are not touched; a node's first momentum step falls in
+        the round that first samples it (first_flags)."""
+        if not self.sample:
+            raise ValueError(f"{self.flag}: this trainer was not built for a sample run")
+        pos = {id(nd): i for i, nd in enumerate(nodes)}
+        rows = [pos[id(nd)] for nd in active]
+        k = len(rows)
+        if k < 1 or len(set(rows)) != k:
+            raise ValueError(f"{self.flag}: a sample of {k} nodes with {len(set(rows))} distinct ones")
+        batches, epoch_done = draw(active, params)
+        self._host()
+        if not self.fresh or self.version != self.slab.version():
+            self.upload()
+        self._fill_batches(active, rows, batches)
+        first = first_flags(self.stepped_rows, rows)
+        self.last_first = first
+        nb, n = self.n * self.b_max, self.n
+        tail = self.idx_host[nb + n:].view(3, n)
+        tail[0, :k] = torch.tensor(rows, dtype=torch.int32)
+        tail[1, :k] = torch.tensor(first, dtype=torch.int32)
+        tail[2, :k] = torch.tensor([r for r, f in zip(rows, first) if f] +
+                                   [r for r, f in zip(rows, first) if not f], dtype=torch.int32)
+        self.idx_dev.copy_(self.idx_host, non_blocking=True)           # one H2D copy
+        dev = self.idx_dev[nb + n:].view(3, n)
+        x, y = self.theta[self.cur], self.theta[1 - self.cur]
+        self._gradient(x, self.idx_dev[:nb].view(n, self.b_max)[:k], self.idx_dev[nb:nb + k], dev[0, :k])
+        self.sample_fused = self.ld >= SAMPLE_FUSED_MIN_COLS and k >= SAMPLE_FUSED_MIN_SHARE * n
+        if self.sample_fused:
+            mom = self.momentum != 0.0
+            ops.sample_step_mean_update(x, y, self.grad, self.mbuf, dev[0, :k], dev[1, :k] if mom else None,
+                                        -self.lr, self.momentum)
+        else:
+            self._sample_sequence(x, y, dev[0, :k], dev[2, :k], sum(first))
+        if self.momentum != 0.0:
+            self.mom_steps += 1
+        self.cur = 1 - self.cur
+        loss = self.loss[:k].cpu().tolist()
+        self.write_back()
+        return {nd["rank"]: float(v) for nd, v in zip(active, loss)}, epoch_done
+
     def round(self, nodes, topology, params, mode):
         """One round of every node; returns ({rank: loss}, {rank: epoch_done})."""
+        if self.sample:
+            raise ValueError(f"{self.flag}: a sample run's rounds are sample_round's")
         if topology is not self.topology or id(topology.get("weights")) != self.weights_id:
             self.set_topology(topology)
         batches, epoch_done = draw(nodes, params)
@@ -418,15 +574,7 @@ class DeviceTrainer:
         if not self.fresh or self.version != self.slab.version():
             self.upload()
         nb = self.n * self.b_max
-        bi = self.idx_host[:nb].view(self.n, self.b_max).numpy()
-        bl = self.idx_host[nb:].numpy()
-        for i, idx in enumerate(batches):
-            k = idx.numel()
-            if k < 1 or k > self.b_max or int(idx.max()) >= self.offsets[i + 1] - self.offsets[i]:
-                raise ValueError(f"{self.flag}: node {nodes[i]['rank']} drew a batch its train-set or "
-                                 "the batch size does not allow")
-            bi[i, :k] = idx.numpy() + self.offsets[i]
-            bl[i] = k
+        self._fill_batches(nodes, range(self.n), batches)
         self.idx_dev.copy_(self.idx_host, non_blocking=True)           # one H2D copy
         x, y = self.theta[self.cur], self.theta[1 - self.cur]
         self._gradient(x, self.idx_dev[:nb].view(self.n, self.b_max), self.idx_dev[nb:])
