@@ -29,7 +29,9 @@
  * niidmix_grad_segment_mean_sgd_step_f32 added (the clique gradient mean fused with the optimizer
  * step, for --clique-gradient under --device-training; a pure addition too);
  * niidmix_sample_step_mean_update_f32 added (the 'sample' topology's step, average and broadcast
- * in one launch, for --device-training-sample; a pure addition too).
+ * in one launch, for --device-training-sample; a pure addition too); niidmix_draw_batches_i32 and
+ * its niidmix_draw_batches_max_len added (training batches drawn on the device, for
+ * --device-sampling; a pure addition too).
  * ABI 5: niidmix_dense_split_elems / niidmix_dense_split_w /
  * niidmix_mix_dense_bf16x6_f32 added (the dense GEMM on the bf16 matrix cores, fp32-accurate by
  * three-term splitting); niidmix_mix_strip_f32 refuses a strip that does not fit the device's LDS.
@@ -727,6 +729,41 @@ int niidmix_gnlenet_nll_grad_rows_f32(const float *theta, int64_t ld_t, const fl
                                       int64_t n_rows, float *grad, int64_t ld_g, float *loss,
                                       int64_t Cin, int64_t H, int64_t W, int64_t C, void *scratch,
                                       int64_t scratch_bytes, void *stream);
+
+/* Training batches drawn on the device (the drop-in's --device-sampling): job j writes the batch
+ * that starts at position cursor[j] of epoch epoch[j]'s permutation of the segment
+ * [seg_start[j], seg_start[j] + seg_len[j]) of the caller's concatenated data, in the layout
+ * niidmix_linear_nll_grad_rows_f32 and niidmix_gnlenet_nll_grad_rows_f32 read:
+ *     batch_len[j]     = min(b_max, seg_len[j] - cursor[j])
+ *     batch_idx[j, t]  = seg_start[j] + perm[cursor[j] + t]      for 0 <= t < batch_len[j]
+ * entries past batch_len[j] are untouched.  The permutation is a stream of this library's own,
+ * defined in integers (niidmix/sampling.py restates it in numpy; the two agree exactly): position
+ * i of the segment gets the 32-bit key
+ *     k_i = word (i & 3) of Philox4x32-10(counter (i >> 2, epoch[j], 0, 0), key (seed, rank[j]))
+ * (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85), and perm lists the
+ * positions in ascending order of the 64-bit composites (k_i << 32) | i, which are distinct.
+ *   seed      the run's seed, low 32 bits
+ *   rank, seg_start, seg_len, epoch, cursor   [n_jobs] int32 (device); ranks may come in any order
+ *             and segments may coincide
+ *   batch_idx [n_jobs, b_max] int32 (device), batch_len [n_jobs] int32 (device)
+ * The call is stateless: one workgroup per job sorts the whole segment every time (in registers
+ * of one wave up to 64 samples, else in LDS), so two calls on the same inputs give the same bits.
+ * niidmix_draw_batches_max_len() is the longest segment a workgroup sorts (8192: composites of 8 B
+ * in 64 KiB of LDS).  The per-job arrays are device data and are NOT read by the launcher: the
+ * kernel clamps a longer seg_len to the maximum (the permutation is then that of the clamped
+ * length; niidmix.train refuses such a node list) and writes batch_len 0 and no index for a cursor
+ * outside [0, seg_len) -- nothing is read or written out of range.
+ * Checked before anything touches the GPU, in this order:
+ *   NIIDMIX_EINVAL        a null pointer
+ *   NIIDMIX_EINVAL        n_jobs or b_max < 1
+ *   NIIDMIX_EUNSUPPORTED  b_max above niidmix_draw_batches_max_len(), n_jobs >= 2^31
+ *   NIIDMIX_EALIAS        batch_idx or batch_len overlaps an input or the other output
+ * A pure addition: the ABI version is unchanged. */
+int64_t niidmix_draw_batches_max_len(void);
+int niidmix_draw_batches_i32(uint32_t seed, const int32_t *rank, const int32_t *seg_start,
+                             const int32_t *seg_len, const int32_t *epoch, const int32_t *cursor,
+                             int64_t n_jobs, int64_t b_max, int32_t *batch_idx, int32_t *batch_len,
+                             void *stream);
 
 /* update_models(all_models, avg) after the 'sample' topology's uniform average (d_sgd.py:240-250,
  * :29-35): every row y_i := fl(fl(x_i * 0) + avg) (p.mul_(0.); p.add_(new)) — avg everywhere

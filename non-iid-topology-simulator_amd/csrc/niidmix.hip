@@ -39,6 +39,7 @@
 //                      k_lin_eval, k_lin_eval_sum                  niidmix_linear_eval_rows_f32
 //   model_gnlenet.inc  k_gnl_eval, k_gnl_grad_sample / _conv / _fc niidmix_gnlenet_eval_rows_f32,
 //                                                                  niidmix_gnlenet_nll_grad_rows_f32
+//   sampling.inc       k_draw_batches                              niidmix_draw_batches_i32
 //   halo pack          k_gather_rows (and the RCCL loader)         niidmix_mix_sharded_f32
 //   host side          (argument checks, env readers, pick, vec_width, BlockGeom, clique launchers)
 //   slab memory        (VMM allocator)                             niidmix_hbm_alloc, niidmix_hbm_free
@@ -4750,6 +4751,8 @@ __global__ __launch_bounds__(256) void k_lin_eval_sum(const int32_t *__restrict_
 
 #include "model_gnlenet.inc"
 
+#include "sampling.inc"
+
 // ----------------------------------------------------------------------------------------------
 // Halo pack of the sharded round: out[i, :] = x[rows[i], :] (the rows a peer shard reads), so that
 // one contiguous send per peer carries them.
@@ -6176,6 +6179,32 @@ int niidmix_gnlenet_nll_grad_rows_f32(const float *theta, int64_t ld_t, const fl
     hipLaunchKernelGGL(k_gnl_grad_fc, dim3((unsigned)(n_rows * n_blk)), dim3(256), 0, s, batch_len,
                        (int)b_max, rows, (int)n_tiles, (int)n_blk, g, L, (const float *)sc, grad, ld_g, loss);
     return check_launch("k_gnl_grad_fc");
+}
+
+int64_t niidmix_draw_batches_max_len(void) { return kDrawMaxLen; }
+
+int niidmix_draw_batches_i32(uint32_t seed, const int32_t *rank, const int32_t *seg_start,
+                             const int32_t *seg_len, const int32_t *epoch, const int32_t *cursor,
+                             int64_t n_jobs, int64_t b_max, int32_t *batch_idx, int32_t *batch_len,
+                             void *stream) {
+    if (!rank || !seg_start || !seg_len || !epoch || !cursor || !batch_idx || !batch_len)
+        return set_error(NIIDMIX_EINVAL, "null pointer");
+    if (n_jobs < 1 || b_max < 1) return set_error(NIIDMIX_EINVAL, "n_jobs and b_max must be >= 1");
+    if (b_max > kDrawMaxLen)
+        return set_error(NIIDMIX_EUNSUPPORTED, "b_max %lld: a workgroup sorts at most %d samples",
+                         (long long)b_max, kDrawMaxLen);
+    if (n_jobs > 0x7fffffff) return set_error(NIIDMIX_EUNSUPPORTED, "n_jobs %lld: too many blocks", (long long)n_jobs);
+    // int32 words compared as the 4-byte elements `overlaps` counts
+    auto f = [](const int32_t *q) { return reinterpret_cast<const float *>(q); };
+    for (const int32_t *in : {rank, seg_start, seg_len, epoch, cursor})
+        if (overlaps(f(in), n_jobs, f(batch_idx), n_jobs * b_max) || overlaps(f(in), n_jobs, f(batch_len), n_jobs))
+            return set_error(NIIDMIX_EALIAS, "batch_idx or batch_len overlaps an input");
+    if (overlaps(f(batch_idx), n_jobs * b_max, f(batch_len), n_jobs))
+        return set_error(NIIDMIX_EALIAS, "batch_idx and batch_len overlap");
+    hipLaunchKernelGGL(k_draw_batches, dim3((unsigned)n_jobs), dim3(kDrawThreads), 0,
+                       reinterpret_cast<hipStream_t>(stream), seed, rank, seg_start, seg_len, epoch, cursor,
+                       (int)b_max, batch_idx, batch_len);
+    return check_launch("k_draw_batches");
 }
 
 int niidmix_update_rows_f32(const float *x, int64_t ld_x, float *y, int64_t ld_y, int64_t n_rows,

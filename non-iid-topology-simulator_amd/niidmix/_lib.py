@@ -111,6 +111,9 @@ SIGNATURES = {
     "niidmix_gnlenet_nll_grad_rows_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64,
                                                          _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp,
                                                          _i64, _vp]),
+    "niidmix_draw_batches_max_len": (_i64, []),
+    "niidmix_draw_batches_i32": (ctypes.c_int, [ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, _i64, _i64,
+                                                _vp, _vp, _vp]),
     "niidmix_sharded_create": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.POINTER(_vp)]),
     "niidmix_sharded_destroy": (ctypes.c_int, [_vp]),
     "niidmix_sharded_is_loopback": (ctypes.c_int, [_vp]),

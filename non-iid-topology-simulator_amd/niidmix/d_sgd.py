@@ -22,7 +22,9 @@ Gradient averaging (--clique-gradient, --unbiased-gradient) also runs on the GPU
 With --device-training (params['algorithm']['device-training'], opt-in) a linear model's local
 training runs on the device too: gradient, step and mixing never leave HBM (niidmix.train);
 --device-training-gn-lenet does the same for GN-LeNet models, and --device-training-sample for
-rounds of the 'sample' topology (the other two flags refuse it).
+rounds of the 'sample' topology (the other two flags refuse it).  --device-sampling, with any of
+the three, draws the batches on the device too, from a sample stream of the plugin's own
+(niidmix.sampling) instead of one DataLoader per node.
 With --device-evaluation (params['algorithm']['device-evaluation'], opt-in) the logger's accuracy
 and loss events of linear and GN-LeNet models are computed on the device as well (niidmix.evaluate).
 """
@@ -773,6 +775,9 @@ def _device_training_step(state, params, rundir):
     if tr.sample != train.sample_run(params):
         raise ValueError(f"{train.FLAG_SAMPLE}: the run changed between a sample round and a graph "
                          "round under a live device trainer: not supported")
+    if tr.sampling != train.sampling_enabled(params):
+        raise ValueError(f"{train.FLAG_SAMPLING} was switched during the run, under a live device "
+                         "trainer: not supported")
     if tr.sample:
         # --device-training-sample (d_sgd.py:236-250): only the sample trains and steps, its
         # average replaces every model (niidmix.train.DeviceTrainer.sample_round)
@@ -901,11 +906,14 @@ def init(nodes, topology, params):
     if params["algorithm"].get("device-evaluation"):
         from . import evaluate
         evaluate.check_eligible(nodes, params)            # refusals: ValueError naming the flag
-    if params["algorithm"].get("device-training"):
+    if params["algorithm"].get("device-training") or params["algorithm"].get("device-sampling"):
         from . import train
         train.check_eligible(nodes, params, topology)     # refusals: ValueError naming the flag
         for n in nodes:
-            n["train-iterator"] = train.index_loader(n, params)
+            # --device-sampling: the batches are drawn on the device (niidmix.sampling's stream):
+            # no loader, and sampling consumes nothing of the global torch RNG
+            n["train-iterator"] = None if train.sampling_enabled(params) else \
+                train.index_loader(n, params)
     else:
         for n in nodes:
             n["train-iterator"] = _loader(n, params)
@@ -1129,6 +1137,14 @@ def main(argv=None):
                          "with --device-training-gn-lenet, ignores --clique-gradient and "
                          "--unbiased-gradient as the reference's sample rounds do; on another "
                          "topology it is plain --device-training")
+    ap.add_argument("--device-sampling", action="store_const", const=True, default=False,
+                    help="with one of the three --device-training flags: the training batches are "
+                         "drawn on the device from a sample stream of the plugin's own (Philox keys "
+                         "per node, epoch and run seed; niidmix.sampling), not by a DataLoader per "
+                         "node from torch's RNG: a round's host work for sampling no longer grows "
+                         "with the nodes; such a run draws other samples than a CPU-path run and is "
+                         "sample-for-sample comparable only with --device-sampling runs of the same "
+                         "seed")
     ap.add_argument("--device-evaluation", action="store_const", const=True, default=False,
                     help="linear models only: the logger's train, test, validation and full-train "
                          "accuracy and loss of every logged node (and of the global model) are "
@@ -1139,6 +1155,10 @@ def main(argv=None):
                          "default it returns while they stream back, whenever the driver reads no "
                          "model before the next round: run.py's logging is predicted)")
     args = ap.parse_args(argv)
+    if args.device_sampling and not (args.device_training or args.device_training_gn_lenet
+                                     or args.device_training_sample):
+        ap.error("--device-sampling needs one of --device-training, --device-training-gn-lenet or "
+                 "--device-training-sample")
     rundir = m.rundir(args)
     params = m.params(rundir)
     topology = load_topology(rundir)
@@ -1160,6 +1180,7 @@ def main(argv=None):
            or args.device_training_sample else {}),
         **({"device-training-gn-lenet": True} if args.device_training_gn_lenet else {}),
         **({"device-training-sample": True} if args.device_training_sample else {}),
+        **({"device-sampling": True} if args.device_sampling else {}),
         **({"device-evaluation": True} if args.device_evaluation else {}),
     })
     if args.rundir is None:

@@ -40,6 +40,9 @@ Ops (registered in the `niidmix` namespace, usable as torch.ops.niidmix.*):
                                                     (the same for GN-LeNet, --device-training-gn-lenet)
   gnlenet_eval_rows(theta, data, labels, rows, seg_start, seg_len, max_len, loss_sum, correct, pred,
                     logits, Cin, H, W, C)           k_gnl_eval + k_lin_eval_sum (the same for GN-LeNet)
+  draw_batches(seed, rank, seg_start, seg_len, epoch, cursor, batch_idx, batch_len)
+                                                    k_draw_batches (the training batches of a round,
+                                                    in the gradient ops' layout, --device-sampling)
 All ops launch on torch's current HIP stream of the input's device, never synchronise, and raise
 RuntimeError (TORCH_CHECK-style) on bad arguments.  They accept HIP tensors only: there is no CPU
 implementation and no fallback.
@@ -862,6 +865,45 @@ def gnlenet_nll_grad_rows(theta: torch.Tensor, data: torch.Tensor, labels: torch
         batch_len.data_ptr(), b_max, rows.data_ptr(), n, grad.data_ptr(), _ld(grad), loss.data_ptr(),
         Cin, H, W, C, scratch.data_ptr(), nbytes, _stream(theta))
     _lib.check(rc, "niidmix::gnlenet_nll_grad_rows")
+
+
+def draw_batches_max_len():
+    """The longest sample segment niidmix::draw_batches sorts (one workgroup's LDS), and so the
+    largest b_max it accepts (include/niidmix.h)."""
+    return int(_lib.lib.niidmix_draw_batches_max_len())
+
+
+@torch.library.custom_op("niidmix::draw_batches", mutates_args=("batch_idx", "batch_len"))
+def draw_batches(seed: int, rank: torch.Tensor, seg_start: torch.Tensor, seg_len: torch.Tensor,
+                 epoch: torch.Tensor, cursor: torch.Tensor, batch_idx: torch.Tensor,
+                 batch_len: torch.Tensor) -> None:
+    """Job j's batch of the --device-sampling stream (include/niidmix.h, niidmix_draw_batches_i32;
+    niidmix.sampling restates it): batch_len[j] = min(b_max, seg_len[j] - cursor[j]) and
+    batch_idx[j, :batch_len[j]] = seg_start[j] + the entries from cursor[j] on of epoch[j]'s
+    permutation for the node of rank rank[j]; the rest of batch_idx is untouched.  int32 HIP
+    tensors only; their CONTENTS are not checked here (the kernel clamps; niidmix.train checks the
+    lengths once)."""
+    _req(isinstance(batch_idx, torch.Tensor) and batch_idx.is_cuda,
+         f"batch_idx: expected a HIP (cuda) tensor, got {batch_idx.device} (no CPU fallback)")
+    dev = batch_idx.device
+    _req(batch_idx.dtype == torch.int32 and batch_idx.dim() == 2 and batch_idx.is_contiguous(),
+         "batch_idx: expected a contiguous int32 [n_jobs, b_max] tensor")
+    n, b_max = batch_idx.shape
+    _req(n >= 1 and b_max >= 1, "batch_idx: n_jobs and b_max must be >= 1")
+    _req(b_max <= draw_batches_max_len(),
+         f"batch_idx: b_max {b_max} above the kernel's maximum of {draw_batches_max_len()}")
+    ins = (("rank", rank), ("seg_start", seg_start), ("seg_len", seg_len), ("epoch", epoch),
+           ("cursor", cursor))
+    for name, t in ins + (("batch_len", batch_len),):
+        _vec(name, t, torch.int32, dev, n)
+    for name, t in ins:
+        _req(not _hits(t, batch_idx) and not _hits(t, batch_len), f"an output overlaps {name}")
+    _req(not _hits(batch_idx, batch_len), "batch_idx and batch_len overlap")
+    rc = _lib.lib.niidmix_draw_batches_i32(
+        int(seed) & 0xFFFFFFFF, rank.data_ptr(), seg_start.data_ptr(), seg_len.data_ptr(),
+        epoch.data_ptr(), cursor.data_ptr(), n, b_max, batch_idx.data_ptr(), batch_len.data_ptr(),
+        _stream(batch_idx))
+    _lib.check(rc, "niidmix::draw_batches")
 
 
 # ------------------------------------------------------------------------------------------------

@@ -63,6 +63,16 @@ with the GN-LeNet flag; the other two flags keep refusing 'sample').  DeviceTrai
 A node's first momentum step falls in whichever round first samples it, so the trainer keeps on
 the host which rows have stepped (first_flags) and sends the k flags with the indices.  Gradient
 averaging does not apply and no Mixer is built (the topology is {'edges': {}, 'weights': []}).
+
+Keeping the CPU path's RNG stream costs N DataLoader draws and the index packing in Python every
+round, far more than the device work of a linear model's round.  `--device-sampling` (with any of
+the three flags above) gives that stream up for one of the project's own, defined in integers
+(niidmix.sampling) and drawn where it is consumed: the host keeps (epoch, cursor) of every row
+(sampling.SamplerState: epoch_done and the batch lengths need no copy back), sends them in one
+small H2D copy, and niidmix::draw_batches writes the indices and lengths straight into the block
+the gradient op reads (_draw_device, in place of draw and _fill_batches).  No DataLoader is built,
+node['train-iterator'] stays None and the global torch RNG is not consumed by sampling; such a run
+is sample-for-sample comparable only with other --device-sampling runs of the same seed.
 """
 import os
 
@@ -77,6 +87,7 @@ from .topology import to_csr
 FLAG = "--device-training"
 FLAG_GN = "--device-training-gn-lenet"
 FLAG_SAMPLE = "--device-training-sample"
+FLAG_SAMPLING = "--device-sampling"
 SCRATCH_FRACTION = 0.4   # of the free HBM, for one GN-LeNet gradient call's scratch
 # When a sample round takes the one-launch step + average + broadcast
 # (niidmix::sample_step_mean_update) instead of the three ops it restates: slabs of at least
@@ -102,6 +113,11 @@ def sample_run(params):
     DeviceTrainer.sample_round.  The key alone, on another topology, changes nothing."""
     return bool(params.get("algorithm", {}).get("device-training-sample")) and \
         params.get("topology", {}).get("name") == "sample"
+
+
+def sampling_enabled(params):
+    """--device-sampling: the batches come from niidmix.sampling's stream, drawn on the device."""
+    return bool(params.get("algorithm", {}).get("device-sampling"))
 
 
 def flag_of(params):
@@ -185,8 +201,30 @@ def clique_segments(plan):
     return plan.seg_ptr[:n_seg + 1].copy(), plan.seg_row[:len(plan.stepped)].copy()
 
 
+def check_sampling(nodes, params):
+    """--device-sampling's own refusals, each a ValueError naming the flag: the stream needs the
+    run's seed, and one workgroup sorts a node's whole train-set (ops.draw_batches_max_len)."""
+    most = ops.draw_batches_max_len()
+    seed = params.get("meta", {}).get("seed")
+    if not isinstance(seed, int) or isinstance(seed, bool):
+        raise ValueError(f"{FLAG_SAMPLING} keys its sample stream by params['meta']['seed'], an "
+                         f"integer; got {seed!r}")
+    b = int(params["algorithm"]["batch-size"])
+    if not 1 <= b <= most:
+        raise ValueError(f"{FLAG_SAMPLING}: batch size {b} is not in 1..{most}, the longest batch the "
+                         "kernel draws")
+    for nd in nodes:
+        ts = nd.get("train-set")
+        if ts is not None and len(ts) > most:
+            raise ValueError(f"{FLAG_SAMPLING}: node {nd['rank']}'s train-set has {len(ts)} samples, "
+                             f"the kernel sorts at most {most} per node")
+        if not 0 <= int(nd["rank"]) < 2 ** 31 or not 0 <= int(nd.get("epoch", 0)) < 2 ** 31 - 1:
+            raise ValueError(f"{FLAG_SAMPLING}: node {nd['rank']}'s rank or epoch is outside int32")
+
+
 def check_eligible(nodes, params, topology=None):
-    """The refusals that need no GPU (d_sgd.init calls this): raises ValueError naming the flag.
+    """The refusals that need no GPU (d_sgd.init calls this): raises ValueError naming the flag
+    (--device-sampling's are check_sampling's, and that it needs one of the training flags).
     Returns (K, C) for linear models and, under --device-training-gn-lenet, (Cin, C, F) for
     GN-LeNet.  --clique-gradient / --unbiased-gradient are accepted when `topology` gives their
     averaging lists (grad_plan).  The 'sample' topology is accepted under --device-training-sample
@@ -194,6 +232,9 @@ def check_eligible(nodes, params, topology=None):
     does, and needs nothing of `topology`."""
     from . import d_sgd
     alg = params["algorithm"]
+    if sampling_enabled(params) and not enabled(params):
+        raise ValueError(f"{FLAG_SAMPLING} draws the batches of a device-training round: it needs one "
+                         f"of {FLAG}, {FLAG_GN} or {FLAG_SAMPLE}")
     gn_flag = gn_enabled(params)
     flag = flag_of(params)
     sample = sample_run(params)
@@ -205,6 +246,8 @@ def check_eligible(nodes, params, topology=None):
         raise ValueError(f"{flag} runs on one device; NIIDMIX_DEVICES lists several")
     if not nodes:
         raise ValueError(f"{flag}: no nodes")
+    if sampling_enabled(params):
+        check_sampling(nodes, params)
     if sample:
         size = params["topology"].get("sample-size")
         if not isinstance(size, int) or not 1 <= size <= len(nodes):
@@ -302,9 +345,14 @@ class DeviceTrainer:
         self.loss = torch.empty(self.n, dtype=torch.float32, device=dev)
         # one round's indices, one H2D copy: [n, b_max] sample indices, [n] batch lengths and, for
         # a sample round (sample_layout), the active rows, their `first` flags and the step lists
-        self.idx_host = torch.zeros(self.n * self.b_max + (4 if self.sample else 1) * self.n,
-                                    dtype=torch.int32).pin_memory()
+        # and, under --device-sampling (job_layout), the five per-job lists of niidmix::draw_batches
+        self.sampling = sampling_enabled(params)     # fixed for the trainer's life, as `sample` is
+        self.idx_host = torch.zeros(self.n * self.b_max + (4 if self.sample else 1) * self.n +
+                                    (5 * self.n if self.sampling else 0), dtype=torch.int32).pin_memory()
         self.idx_dev = torch.empty_like(self.idx_host, device=dev)
+        self.sampler = None
+        if self.sampling:
+            self._init_sampler(nodes, params)
         self.stepped_rows = set()     # sample rounds: rows that have taken an optimizer step
         self.last_first = []          # the `first` flags of the last sample round (tests)
         self._avg = None              # sample rounds, three-op sequence: the CSR row and the average
@@ -500,6 +548,51 @@ class DeviceTrainer:
             bi[j, :k] = idx.numpy() + self.offsets[i]
             bl[j] = k
 
+    def _init_sampler(self, nodes, params):
+        """--device-sampling: the host's (epoch, cursor) of every row (niidmix.sampling.SamplerState)
+        and, behind everything else in the index block, the job lists of niidmix::draw_batches --
+        five rows of n int32: rank, seg_start and seg_len (a graph round's job j is row j, so these
+        go up here, once), then epoch and cursor (every round)."""
+        import numpy as np
+        from .sampling import SamplerState
+        self.seed = int(params["meta"]["seed"]) & 0xFFFFFFFF
+        off = np.asarray(self.offsets, dtype=np.int64)
+        self.seg_start = off[:-1]
+        self.sampler = SamplerState([nd["rank"] for nd in nodes], off[1:] - off[:-1], self.b_max,
+                                    epochs=[nd.get("epoch", 0) for nd in nodes])
+        self.all_rows = np.arange(self.n)
+        self.job0 = self.idx_host.numel() - 5 * self.n
+        job = self.idx_host[self.job0:].view(5, self.n).numpy()
+        job[0], job[1], job[2] = self.sampler.rank, self.seg_start, self.sampler.length
+        self.idx_dev.copy_(self.idx_host)
+
+    def _draw_device(self, active, rows=None):
+        """One round's batches under --device-sampling, in place of draw() and _fill_batches(): the
+        rows' (epoch, cursor) from the host state, one H2D copy of them (and, for a sample round, of
+        its other lists, which lie in front of them) and niidmix::draw_batches, which writes job
+        j's indices and length where the gradient op reads them.  `rows`: the slab rows of a sample
+        round's active nodes, in the sample's order (only they advance; their rank, seg_start and
+        seg_len go up too); None: every row.  Returns {rank: epoch_done}; node['epoch'] counts as
+        it does in draw()."""
+        n, nb, st = self.n, self.n * self.b_max, self.sampler
+        k = n if rows is None else len(rows)
+        epoch, cursor, done = st.advance(self.all_rows if rows is None else rows)
+        if int(epoch.max()) >= 2 ** 31 - 1:
+            raise ValueError(f"{FLAG_SAMPLING}: an epoch count outside int32")
+        job = self.idx_host[self.job0:].view(5, n).numpy()
+        if rows is not None:
+            job[0, :k], job[1, :k], job[2, :k] = st.rank[rows], self.seg_start[rows], st.length[rows]
+        job[3, :k], job[4, :k] = epoch, cursor
+        for nd in active:
+            if done[nd["rank"]]:
+                nd["epoch"] += 1
+        first = self.job0 + 3 * n if rows is None else nb + n
+        self.idx_dev[first:].copy_(self.idx_host[first:], non_blocking=True)       # one H2D copy
+        jd = self.idx_dev[self.job0:].view(5, n)[:, :k]
+        ops.draw_batches(self.seed, jd[0], jd[1], jd[2], jd[3], jd[4],
+                         self.idx_dev[:nb].view(n, self.b_max)[:k], self.idx_dev[nb:nb + k])
+        return done
+
     def _sample_sequence(self, x, y, active, lists, n_first):
         """Step, average and broadcast of a sample round as the three ops in sequence (x is
         stepped in place): what niidmix::sample_step_mean_update restates in one launch."""
@@ -532,21 +625,26 @@ class DeviceTrainer:
         k = len(rows)
         if k < 1 or len(set(rows)) != k:
             raise ValueError(f"{self.flag}: a sample of {k} nodes with {len(set(rows))} distinct ones")
-        batches, epoch_done = draw(active, params)
+        if not self.sampling:
+            batches, epoch_done = draw(active, params)
         self._host()
         if not self.fresh or self.version != self.slab.version():
             self.upload()
-        self._fill_batches(active, rows, batches)
+        if not self.sampling:
+            self._fill_batches(active, rows, batches)
         first = first_flags(self.stepped_rows, rows)
         self.last_first = first
         nb, n = self.n * self.b_max, self.n
-        tail = self.idx_host[nb + n:].view(3, n)
+        tail = self.idx_host[nb + n:nb + 4 * n].view(3, n)
         tail[0, :k] = torch.tensor(rows, dtype=torch.int32)
         tail[1, :k] = torch.tensor(first, dtype=torch.int32)
         tail[2, :k] = torch.tensor([r for r, f in zip(rows, first) if f] +
                                    [r for r, f in zip(rows, first) if not f], dtype=torch.int32)
-        self.idx_dev.copy_(self.idx_host, non_blocking=True)           # one H2D copy
-        dev = self.idx_dev[nb + n:].view(3, n)
+        if self.sampling:
+            epoch_done = self._draw_device(active, rows)                # the one H2D copy is there
+        else:
+            self.idx_dev.copy_(self.idx_host, non_blocking=True)       # one H2D copy
+        dev = self.idx_dev[nb + n:nb + 4 * n].view(3, n)
         x, y = self.theta[self.cur], self.theta[1 - self.cur]
         self._gradient(x, self.idx_dev[:nb].view(n, self.b_max)[:k], self.idx_dev[nb:nb + k], dev[0, :k])
         self.sample_fused = self.ld >= SAMPLE_FUSED_MIN_COLS and k >= SAMPLE_FUSED_MIN_SHARE * n
@@ -569,15 +667,19 @@ class DeviceTrainer:
             raise ValueError(f"{self.flag}: a sample run's rounds are sample_round's")
         if topology is not self.topology or id(topology.get("weights")) != self.weights_id:
             self.set_topology(topology)
-        batches, epoch_done = draw(nodes, params)
+        if not self.sampling:
+            batches, epoch_done = draw(nodes, params)
         self._host()
         if not self.fresh or self.version != self.slab.version():
             self.upload()
         nb = self.n * self.b_max
-        self._fill_batches(nodes, range(self.n), batches)
-        self.idx_dev.copy_(self.idx_host, non_blocking=True)           # one H2D copy
+        if self.sampling:
+            epoch_done = self._draw_device(nodes)
+        else:
+            self._fill_batches(nodes, range(self.n), batches)
+            self.idx_dev.copy_(self.idx_host, non_blocking=True)       # one H2D copy
         x, y = self.theta[self.cur], self.theta[1 - self.cur]
-        self._gradient(x, self.idx_dev[:nb].view(self.n, self.b_max), self.idx_dev[nb:])
+        self._gradient(x, self.idx_dev[:nb].view(self.n, self.b_max), self.idx_dev[nb:nb + self.n])
         self._step(x)
         self.mixer(x, out=y, mode=mode)
         self.cur = 1 - self.cur
