@@ -31,7 +31,9 @@
  * niidmix_sample_step_mean_update_f32 added (the 'sample' topology's step, average and broadcast
  * in one launch, for --device-training-sample; a pure addition too); niidmix_draw_batches_i32 and
  * its niidmix_draw_batches_max_len added (training batches drawn on the device, for
- * --device-sampling; a pure addition too).
+ * --device-sampling; a pure addition too); niidmix_epoch_perm_i32, niidmix_take_batches_i32,
+ * niidmix_epoch_perm_max_len and niidmix_epoch_perm_scratch_bytes added (a whole epoch's
+ * permutation sorted once and sliced every round, for --device-sampling-cached; pure additions too).
  * ABI 5: niidmix_dense_split_elems / niidmix_dense_split_w /
  * niidmix_mix_dense_bf16x6_f32 added (the dense GEMM on the bf16 matrix cores, fp32-accurate by
  * three-term splitting); niidmix_mix_strip_f32 refuses a strip that does not fit the device's LDS.
@@ -762,6 +764,54 @@ int niidmix_gnlenet_nll_grad_rows_f32(const float *theta, int64_t ld_t, const fl
 int64_t niidmix_draw_batches_max_len(void);
 int niidmix_draw_batches_i32(uint32_t seed, const int32_t *rank, const int32_t *seg_start,
                              const int32_t *seg_len, const int32_t *epoch, const int32_t *cursor,
+                             int64_t n_jobs, int64_t b_max, int32_t *batch_idx, int32_t *batch_len,
+                             void *stream);
+
+/* The same stream, sorted once per epoch and kept (the drop-in's --device-sampling-cached, for
+ * train-sets longer than one workgroup sorts): niidmix_epoch_perm_i32 writes job j's whole
+ * permutation of epoch[j] -- seg_len[j] segment-local positions, the ascending order of the
+ * composites above -- to perm[perm_off[j] .. perm_off[j] + seg_len[j]), and
+ * niidmix_take_batches_i32 slices such a cache every round, in niidmix_draw_batches_i32's layout:
+ *     batch_len[j]     = min(b_max, seg_len[j] - cursor[j])
+ *     batch_idx[j, t]  = seg_start[j] + perm[perm_off[j] + cursor[j] + t]   for 0 <= t < batch_len[j]
+ * For segments of at most niidmix_draw_batches_max_len() samples the two calls give, bit for bit,
+ * what niidmix_draw_batches_i32 gives on the same jobs.
+ *   rank, seg_len, epoch, seg_start, cursor   [n_jobs] int32 (device)
+ *   perm_off  [n_jobs] int64 (device): the jobs' stretches of perm; they must not overlap each
+ *             other (not checked: overlapping stretches have two writers)
+ *   perm      [perm_len] int32 (device)
+ *   max_len   (host) the longest seg_len among the jobs: the launcher sizes its grid and the
+ *             scratch by it without reading device memory.  The kernels clamp a longer seg_len to
+ *             it (the permutation is then that of the clamped length).
+ *   scratch   (device, 16-B aligned) niidmix_epoch_perm_scratch_bytes(n_jobs, max_len) bytes: 0
+ *             (scratch may be NULL) when max_len <= niidmix_draw_batches_max_len(), else
+ *             n_jobs * pow2(max_len) * 8, pow2 the next power of two
+ * Segments up to niidmix_draw_batches_max_len() are sorted by one workgroup in LDS, as there.  A
+ * longer one is one bitonic network over pow2(seg_len) composites in the scratch (all-ones
+ * padding): a workgroup sorts each chunk of 8192 in LDS, then every level takes one launch per
+ * stage of stride >= 8192 in global memory and one launch that finishes it in LDS.  Every word
+ * has one writer and no stage depends on scheduling: two calls give the same bits.
+ * niidmix_epoch_perm_max_len() is the longest segment (2^20 = 1048576: 36 launches).
+ * The per-job arrays are device data and are NOT read by the launcher.  A job whose stretch
+ * [perm_off, perm_off + seg_len) does not lie inside [0, perm_len) is skipped by
+ * niidmix_epoch_perm_i32 and gets batch_len 0 from niidmix_take_batches_i32, as does a cursor
+ * outside [0, seg_len); slots past batch_len are untouched -- nothing is read or written out of
+ * range whatever the arrays hold.
+ * Checked before anything touches the GPU, in this order:
+ *   NIIDMIX_EINVAL        a null pointer (scratch only when max_len needs one)
+ *   NIIDMIX_EINVAL        n_jobs, max_len, b_max or perm_len < 1
+ *   NIIDMIX_EUNSUPPORTED  max_len or b_max above niidmix_epoch_perm_max_len(), n_jobs >= 2^31
+ *   NIIDMIX_EINVAL        scratch_bytes below the need, scratch not 16-B aligned
+ *   NIIDMIX_EALIAS        an output (perm, scratch; batch_idx, batch_len) overlaps an input or the
+ *                         other output
+ * Pure additions: the ABI version is unchanged. */
+int64_t niidmix_epoch_perm_max_len(void);
+int64_t niidmix_epoch_perm_scratch_bytes(int64_t n_jobs, int64_t max_len);
+int niidmix_epoch_perm_i32(uint32_t seed, const int32_t *rank, const int32_t *seg_len, const int32_t *epoch,
+                           const int64_t *perm_off, int64_t n_jobs, int64_t max_len, int32_t *perm,
+                           int64_t perm_len, void *scratch, int64_t scratch_bytes, void *stream);
+int niidmix_take_batches_i32(const int32_t *perm, int64_t perm_len, const int64_t *perm_off,
+                             const int32_t *seg_start, const int32_t *seg_len, const int32_t *cursor,
                              int64_t n_jobs, int64_t b_max, int32_t *batch_idx, int32_t *batch_len,
                              void *stream);
 

@@ -39,7 +39,8 @@
 //                      k_lin_eval, k_lin_eval_sum                  niidmix_linear_eval_rows_f32
 //   model_gnlenet.inc  k_gnl_eval, k_gnl_grad_sample / _conv / _fc niidmix_gnlenet_eval_rows_f32,
 //                                                                  niidmix_gnlenet_nll_grad_rows_f32
-//   sampling.inc       k_draw_batches                              niidmix_draw_batches_i32
+//   sampling.inc       k_draw_batches, k_epoch_perm_chunks /       niidmix_draw_batches_i32, _epoch_perm_i32,
+//                      _global / _finish, k_take_batches           _take_batches_i32
 //   halo pack          k_gather_rows (and the RCCL loader)         niidmix_mix_sharded_f32
 //   host side          (argument checks, env readers, pick, vec_width, BlockGeom, clique launchers)
 //   slab memory        (VMM allocator)                             niidmix_hbm_alloc, niidmix_hbm_free
@@ -6205,6 +6206,94 @@ int niidmix_draw_batches_i32(uint32_t seed, const int32_t *rank, const int32_t *
                        reinterpret_cast<hipStream_t>(stream), seed, rank, seg_start, seg_len, epoch, cursor,
                        (int)b_max, batch_idx, batch_len);
     return check_launch("k_draw_batches");
+}
+
+int64_t niidmix_epoch_perm_max_len(void) { return kEpochPermMaxLen; }
+
+// the padded length of the network that sorts a segment of max_len samples (0 < max_len <= 2^20)
+static int64_t epoch_perm_pad(int64_t max_len) {
+    int64_t n = kDrawMaxLen;
+    while (n < max_len) n <<= 1;
+    return n;
+}
+
+int64_t niidmix_epoch_perm_scratch_bytes(int64_t n_jobs, int64_t max_len) {
+    if (n_jobs < 1 || n_jobs > 0x7fffffff || max_len <= kDrawMaxLen || max_len > kEpochPermMaxLen) return 0;
+    return n_jobs * epoch_perm_pad(max_len) * 8;
+}
+
+int niidmix_epoch_perm_i32(uint32_t seed, const int32_t *rank, const int32_t *seg_len, const int32_t *epoch,
+                           const int64_t *perm_off, int64_t n_jobs, int64_t max_len, int32_t *perm,
+                           int64_t perm_len, void *scratch, int64_t scratch_bytes, void *stream) {
+    const bool is_long = max_len > kDrawMaxLen;
+    if (!rank || !seg_len || !epoch || !perm_off || !perm || (is_long && !scratch))
+        return set_error(NIIDMIX_EINVAL, "null pointer");
+    if (n_jobs < 1 || max_len < 1 || perm_len < 1)
+        return set_error(NIIDMIX_EINVAL, "n_jobs, max_len and perm_len must be >= 1");
+    if (max_len > kEpochPermMaxLen)
+        return set_error(NIIDMIX_EUNSUPPORTED, "max_len %lld: a segment of at most %d samples is sorted",
+                         (long long)max_len, kEpochPermMaxLen);
+    if (n_jobs > 0x7fffffff) return set_error(NIIDMIX_EUNSUPPORTED, "n_jobs %lld: too many blocks", (long long)n_jobs);
+    const int64_t need = niidmix_epoch_perm_scratch_bytes(n_jobs, max_len);
+    if (is_long && (scratch_bytes < need || (reinterpret_cast<uintptr_t>(scratch) & 15u)))
+        return set_error(NIIDMIX_EINVAL, "scratch of %lld bytes (16-B aligned), %lld needed",
+                         (long long)scratch_bytes, (long long)need);
+    // 4-byte words, as the elements `overlaps` counts (perm_off and the scratch: two per entry)
+    auto f = [](const void *q) { return reinterpret_cast<const float *>(q); };
+    const std::pair<const void *, int64_t> ins[] = {{rank, n_jobs}, {seg_len, n_jobs}, {epoch, n_jobs},
+                                                    {perm_off, 2 * n_jobs}};
+    for (const auto &in : ins)
+        if (overlaps(f(in.first), in.second, f(perm), perm_len) ||
+            (is_long && overlaps(f(in.first), in.second, f(scratch), need / 4)))
+            return set_error(NIIDMIX_EALIAS, "perm or scratch overlaps an input");
+    if (is_long && overlaps(f(perm), perm_len, f(scratch), need / 4))
+        return set_error(NIIDMIX_EALIAS, "perm and scratch overlap");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int64_t pad = epoch_perm_pad(max_len);
+    uint64_t *sc = reinterpret_cast<uint64_t *>(scratch);
+    const dim3 chunks((unsigned)n_jobs, (unsigned)(pad / kDrawMaxLen)), threads(kDrawThreads);
+    hipLaunchKernelGGL(k_epoch_perm_chunks, chunks, threads, 0, s, seed, rank, seg_len, epoch, perm_off,
+                       (int)max_len, perm, perm_len, sc, pad);
+    if (int rc = check_launch("k_epoch_perm_chunks")) return rc;
+    for (int64_t k = 2 * kDrawMaxLen; k <= pad; k <<= 1) {
+        for (int64_t j = k / 2; j >= kDrawMaxLen; j >>= 1) {
+            hipLaunchKernelGGL(k_epoch_perm_global, dim3((unsigned)n_jobs, (unsigned)(pad / (4 * kDrawThreads))),
+                               threads, 0, s, seg_len, perm_off, (int)max_len, perm_len, sc, pad, (int)k, (int)j);
+            if (int rc = check_launch("k_epoch_perm_global")) return rc;
+        }
+        hipLaunchKernelGGL(k_epoch_perm_finish, chunks, threads, 0, s, seg_len, perm_off, (int)max_len, perm,
+                           perm_len, sc, pad, (int)k);
+        if (int rc = check_launch("k_epoch_perm_finish")) return rc;
+    }
+    return NIIDMIX_OK;
+}
+
+int niidmix_take_batches_i32(const int32_t *perm, int64_t perm_len, const int64_t *perm_off,
+                             const int32_t *seg_start, const int32_t *seg_len, const int32_t *cursor,
+                             int64_t n_jobs, int64_t b_max, int32_t *batch_idx, int32_t *batch_len,
+                             void *stream) {
+    if (!perm || !perm_off || !seg_start || !seg_len || !cursor || !batch_idx || !batch_len)
+        return set_error(NIIDMIX_EINVAL, "null pointer");
+    if (n_jobs < 1 || b_max < 1 || perm_len < 1)
+        return set_error(NIIDMIX_EINVAL, "n_jobs, b_max and perm_len must be >= 1");
+    if (b_max > kEpochPermMaxLen)
+        return set_error(NIIDMIX_EUNSUPPORTED, "b_max %lld: a batch holds at most %d samples",
+                         (long long)b_max, kEpochPermMaxLen);
+    if (n_jobs > 0x7fffffff) return set_error(NIIDMIX_EUNSUPPORTED, "n_jobs %lld: too many blocks", (long long)n_jobs);
+    auto f = [](const void *q) { return reinterpret_cast<const float *>(q); };
+    const std::pair<const void *, int64_t> ins[] = {{perm, perm_len}, {perm_off, 2 * n_jobs}, {seg_start, n_jobs},
+                                                    {seg_len, n_jobs}, {cursor, n_jobs}};
+    for (const auto &in : ins)
+        if (overlaps(f(in.first), in.second, f(batch_idx), n_jobs * b_max) ||
+            overlaps(f(in.first), in.second, f(batch_len), n_jobs))
+            return set_error(NIIDMIX_EALIAS, "batch_idx or batch_len overlaps an input");
+    if (overlaps(f(batch_idx), n_jobs * b_max, f(batch_len), n_jobs))
+        return set_error(NIIDMIX_EALIAS, "batch_idx and batch_len overlap");
+    const int64_t tiles = (b_max + kDrawThreads - 1) / kDrawThreads;     // <= 4096
+    hipLaunchKernelGGL(k_take_batches, dim3((unsigned)n_jobs, (unsigned)tiles), dim3(kDrawThreads), 0,
+                       reinterpret_cast<hipStream_t>(stream), perm, perm_len, perm_off, seg_start, seg_len,
+                       cursor, (int)b_max, batch_idx, batch_len);
+    return check_launch("k_take_batches");
 }
 
 int niidmix_update_rows_f32(const float *x, int64_t ld_x, float *y, int64_t ld_y, int64_t n_rows,

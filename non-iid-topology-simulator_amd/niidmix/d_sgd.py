@@ -24,7 +24,8 @@ training runs on the device too: gradient, step and mixing never leave HBM (niid
 --device-training-gn-lenet does the same for GN-LeNet models, and --device-training-sample for
 rounds of the 'sample' topology (the other two flags refuse it).  --device-sampling, with any of
 the three, draws the batches on the device too, from a sample stream of the plugin's own
-(niidmix.sampling) instead of one DataLoader per node.
+(niidmix.sampling) instead of one DataLoader per node; --device-sampling-cached keeps every epoch's
+permutation in HBM, which lifts that flag's limit of 8192 samples per node.
 With --device-evaluation (params['algorithm']['device-evaluation'], opt-in) the logger's accuracy
 and loss events of linear and GN-LeNet models are computed on the device as well (niidmix.evaluate).
 """
@@ -778,6 +779,9 @@ def _device_training_step(state, params, rundir):
     if tr.sampling != train.sampling_enabled(params):
         raise ValueError(f"{train.FLAG_SAMPLING} was switched during the run, under a live device "
                          "trainer: not supported")
+    if tr.cached != train.cached_enabled(params):
+        raise ValueError(f"{train.FLAG_CACHED} was switched during the run, under a live device "
+                         "trainer: not supported")
     if tr.sample:
         # --device-training-sample (d_sgd.py:236-250): only the sample trains and steps, its
         # average replaces every model (niidmix.train.DeviceTrainer.sample_round)
@@ -1145,6 +1149,12 @@ def main(argv=None):
                          "with the nodes; such a run draws other samples than a CPU-path run and is "
                          "sample-for-sample comparable only with --device-sampling runs of the same "
                          "seed")
+    ap.add_argument("--device-sampling-cached", action="store_const", const=True, default=False,
+                    help="with --device-sampling: every node's permutation is sorted once per epoch "
+                         "into a cache in HBM and sliced every round, so train-sets of more than "
+                         "8192 samples (up to 2^20) are accepted; the same sample stream: a run "
+                         "draws, batch for batch, what plain --device-sampling draws with the same "
+                         "seed")
     ap.add_argument("--device-evaluation", action="store_const", const=True, default=False,
                     help="linear models only: the logger's train, test, validation and full-train "
                          "accuracy and loss of every logged node (and of the global model) are "
@@ -1159,6 +1169,8 @@ def main(argv=None):
                                      or args.device_training_sample):
         ap.error("--device-sampling needs one of --device-training, --device-training-gn-lenet or "
                  "--device-training-sample")
+    if args.device_sampling_cached and not args.device_sampling:
+        ap.error("--device-sampling-cached needs --device-sampling")
     rundir = m.rundir(args)
     params = m.params(rundir)
     topology = load_topology(rundir)
@@ -1181,6 +1193,7 @@ def main(argv=None):
         **({"device-training-gn-lenet": True} if args.device_training_gn_lenet else {}),
         **({"device-training-sample": True} if args.device_training_sample else {}),
         **({"device-sampling": True} if args.device_sampling else {}),
+        **({"device-sampling-cached": True} if args.device_sampling_cached else {}),
         **({"device-evaluation": True} if args.device_evaluation else {}),
     })
     if args.rundir is None:

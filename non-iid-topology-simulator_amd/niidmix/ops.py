@@ -43,6 +43,12 @@ Ops (registered in the `niidmix` namespace, usable as torch.ops.niidmix.*):
   draw_batches(seed, rank, seg_start, seg_len, epoch, cursor, batch_idx, batch_len)
                                                     k_draw_batches (the training batches of a round,
                                                     in the gradient ops' layout, --device-sampling)
+  epoch_perm(seed, rank, seg_len, epoch, perm_off, max_len, perm, scratch)
+                                                    k_epoch_perm_chunks + _global + _finish (whole
+                                                    epochs' permutations of the same stream, kept
+                                                    in HBM, --device-sampling-cached)
+  take_batches(perm, perm_off, seg_start, seg_len, cursor, batch_idx, batch_len)
+                                                    k_take_batches (a round's slice of them)
 All ops launch on torch's current HIP stream of the input's device, never synchronise, and raise
 RuntimeError (TORCH_CHECK-style) on bad arguments.  They accept HIP tensors only: there is no CPU
 implementation and no fallback.
@@ -904,6 +910,90 @@ def draw_batches(seed: int, rank: torch.Tensor, seg_start: torch.Tensor, seg_len
         epoch.data_ptr(), cursor.data_ptr(), n, b_max, batch_idx.data_ptr(), batch_len.data_ptr(),
         _stream(batch_idx))
     _lib.check(rc, "niidmix::draw_batches")
+
+
+def epoch_perm_max_len():
+    """The longest sample segment niidmix::epoch_perm sorts (include/niidmix.h)."""
+    return int(_lib.lib.niidmix_epoch_perm_max_len())
+
+
+def epoch_perm_scratch_bytes(n_jobs, max_len):
+    """Bytes of scratch niidmix::epoch_perm needs for n_jobs segments of at most max_len samples:
+    0 up to draw_batches_max_len(), else n_jobs * pow2(max_len) * 8."""
+    return int(_lib.lib.niidmix_epoch_perm_scratch_bytes(int(n_jobs), int(max_len)))
+
+
+@torch.library.custom_op("niidmix::epoch_perm", mutates_args=("perm", "scratch"))
+def epoch_perm(seed: int, rank: torch.Tensor, seg_len: torch.Tensor, epoch: torch.Tensor,
+               perm_off: torch.Tensor, max_len: int, perm: torch.Tensor, scratch: torch.Tensor) -> None:
+    """Job j's whole permutation of epoch[j] in the --device-sampling stream (include/niidmix.h,
+    niidmix_epoch_perm_i32; niidmix.sampling.epoch_permutation restates it) into
+    perm[perm_off[j] : perm_off[j] + seg_len[j]]; the rest of perm is untouched.  max_len: the
+    longest seg_len (host), which sizes the grid and the scratch -- a contiguous HIP tensor of at
+    least epoch_perm_scratch_bytes(n_jobs, max_len) bytes (any dtype; it may be empty when that is
+    0).  HIP tensors only; the per-job CONTENTS are not checked here (the kernels clamp a longer
+    seg_len to max_len and skip a stretch outside perm)."""
+    _req(isinstance(perm, torch.Tensor) and perm.is_cuda,
+         f"perm: expected a HIP (cuda) tensor, got {perm.device} (no CPU fallback)")
+    dev = perm.device
+    _vec("perm", perm, torch.int32, dev)
+    _req(perm.numel() >= 1, "perm: empty")
+    _req(isinstance(rank, torch.Tensor) and rank.dim() == 1 and rank.numel() >= 1,
+         "rank: expected a 1-D tensor of n_jobs >= 1 elements")
+    n, max_len = rank.numel(), int(max_len)
+    _req(1 <= max_len <= epoch_perm_max_len(),
+         f"max_len {max_len} is not in 1..{epoch_perm_max_len()}, the longest segment the kernel sorts")
+    ins = (("rank", rank, torch.int32), ("seg_len", seg_len, torch.int32), ("epoch", epoch, torch.int32),
+           ("perm_off", perm_off, torch.int64))
+    for name, t, dtype in ins:
+        _vec(name, t, dtype, dev, n)
+    need = epoch_perm_scratch_bytes(n, max_len)
+    _req(isinstance(scratch, torch.Tensor) and scratch.device == dev and scratch.is_contiguous(),
+         f"scratch: expected a contiguous tensor on {dev}")
+    nbytes = scratch.numel() * scratch.element_size()
+    _req(nbytes >= need, f"scratch: {nbytes} bytes, {need} needed")
+    for name, t, _ in ins:
+        _req(not _hits(t, perm) and not (need and _hits(t, scratch)), f"an output overlaps {name}")
+    _req(not (need and _hits(perm, scratch)), "perm and scratch overlap")
+    rc = _lib.lib.niidmix_epoch_perm_i32(
+        int(seed) & 0xFFFFFFFF, rank.data_ptr(), seg_len.data_ptr(), epoch.data_ptr(), perm_off.data_ptr(),
+        n, max_len, perm.data_ptr(), perm.numel(), scratch.data_ptr() if need else None, nbytes,
+        _stream(perm))
+    _lib.check(rc, "niidmix::epoch_perm")
+
+
+@torch.library.custom_op("niidmix::take_batches", mutates_args=("batch_idx", "batch_len"))
+def take_batches(perm: torch.Tensor, perm_off: torch.Tensor, seg_start: torch.Tensor,
+                 seg_len: torch.Tensor, cursor: torch.Tensor, batch_idx: torch.Tensor,
+                 batch_len: torch.Tensor) -> None:
+    """The round's slice of the permutations niidmix::epoch_perm cached (include/niidmix.h,
+    niidmix_take_batches_i32), in niidmix::draw_batches' layout: batch_len[j] = min(b_max,
+    seg_len[j] - cursor[j]) and batch_idx[j, :batch_len[j]] = seg_start[j] + perm[perm_off[j] +
+    cursor[j] + t]; the rest of batch_idx is untouched.  HIP tensors only; their CONTENTS are not
+    checked here (a cursor outside the segment, or a stretch outside perm, gives an empty batch)."""
+    _req(isinstance(batch_idx, torch.Tensor) and batch_idx.is_cuda,
+         f"batch_idx: expected a HIP (cuda) tensor, got {batch_idx.device} (no CPU fallback)")
+    dev = batch_idx.device
+    _req(batch_idx.dtype == torch.int32 and batch_idx.dim() == 2 and batch_idx.is_contiguous(),
+         "batch_idx: expected a contiguous int32 [n_jobs, b_max] tensor")
+    n, b_max = batch_idx.shape
+    _req(n >= 1 and b_max >= 1, "batch_idx: n_jobs and b_max must be >= 1")
+    _req(b_max <= epoch_perm_max_len(),
+         f"batch_idx: b_max {b_max} above the kernel's maximum of {epoch_perm_max_len()}")
+    _vec("perm", perm, torch.int32, dev)
+    _req(perm.numel() >= 1, "perm: empty")
+    ins = (("perm_off", perm_off, torch.int64), ("seg_start", seg_start, torch.int32),
+           ("seg_len", seg_len, torch.int32), ("cursor", cursor, torch.int32))
+    for name, t, dtype in ins:
+        _vec(name, t, dtype, dev, n)
+    _vec("batch_len", batch_len, torch.int32, dev, n)
+    for name, t, _ in ins + (("perm", perm, None),):
+        _req(not _hits(t, batch_idx) and not _hits(t, batch_len), f"an output overlaps {name}")
+    _req(not _hits(batch_idx, batch_len), "batch_idx and batch_len overlap")
+    rc = _lib.lib.niidmix_take_batches_i32(
+        perm.data_ptr(), perm.numel(), perm_off.data_ptr(), seg_start.data_ptr(), seg_len.data_ptr(),
+        cursor.data_ptr(), n, b_max, batch_idx.data_ptr(), batch_len.data_ptr(), _stream(batch_idx))
+    _lib.check(rc, "niidmix::take_batches")
 
 
 # ------------------------------------------------------------------------------------------------

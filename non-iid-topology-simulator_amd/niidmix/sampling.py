@@ -15,7 +15,10 @@ from a stream of the project's own, defined in integers only so that the device 
                  permutation reports epoch_done, increments the epoch and resets the cursor
 
 This module is the tests' oracle for the kernel, and SamplerState tells the host every round's
-epoch_done flags and batch lengths without a copy back from the device.
+epoch_done flags and batch lengths without a copy back from the device.  Under
+`--device-sampling-cached` the same permutations are sorted once per epoch into a device cache
+(niidmix::epoch_perm, sliced by niidmix::take_batches); SamplerState then also records which
+epoch's permutation each row's part of the cache holds.
 """
 import numpy as np
 
@@ -60,7 +63,8 @@ def batch(seed, rank, epoch, cursor, length, b):
 
 class SamplerState:
     """Epoch and cursor of every node of a list, on the host: numpy arrays `epoch`, `cursor`,
-    `length` (and `rank`), one entry per row of the list."""
+    `length` (and `rank`), one entry per row of the list; `cached` is the epoch whose permutation
+    the device cache of --device-sampling-cached holds for the row (-1: none)."""
 
     def __init__(self, ranks, lengths, b, epochs=None):
         self.rank = np.asarray(ranks, dtype=np.int64)
@@ -70,6 +74,19 @@ class SamplerState:
             raise ValueError("SamplerState: batch size and every length must be >= 1")
         self.epoch = np.zeros_like(self.length) if epochs is None else np.asarray(epochs, dtype=np.int64).copy()
         self.cursor = np.zeros_like(self.length)
+        # --device-sampling-cached: the epoch whose permutation the device cache holds, -1 for none
+        self.cached = np.full_like(self.length, -1)
+
+    def stale(self, rows):
+        """Those of the rows `rows` (distinct, any order; their order is kept) whose cached
+        permutation is not the one their NEXT batch comes from: they are sorted before it is drawn."""
+        rows = np.asarray(rows, dtype=np.int64)
+        return rows[self.cached[rows] != self.epoch[rows]]
+
+    def mark_cached(self, rows):
+        """The cache now holds the current epoch's permutation of the rows `rows`."""
+        rows = np.asarray(rows, dtype=np.int64)
+        self.cached[rows] = self.epoch[rows]
 
     def advance(self, rows):
         """One batch of each of the rows `rows` (distinct, any order): returns (epoch, cursor,

@@ -73,6 +73,17 @@ small H2D copy, and niidmix::draw_batches writes the indices and lengths straigh
 the gradient op reads (_draw_device, in place of draw and _fill_batches).  No DataLoader is built,
 node['train-iterator'] stays None and the global torch RNG is not consumed by sampling; such a run
 is sample-for-sample comparable only with other --device-sampling runs of the same seed.
+
+niidmix::draw_batches is stateless -- one workgroup sorts a node's whole epoch on every call -- and
+so bounded by what a workgroup sorts in LDS (8192 samples).  `--device-sampling-cached` (with
+--device-sampling) keeps the same stream but sorts each epoch once: the trainer owns an int32 cache
+of offsets[-1] entries, a node's permutation at its data offset; before a round's draw the rows
+whose cache is not their current epoch's (SamplerState.stale: every row in round 0, afterwards the
+rows that crossed an epoch) are sorted by niidmix::epoch_perm -- rows of up to 8192 samples in one
+call without scratch, longer rows in calls cut by cut_rows to the scratch budget -- and
+niidmix::take_batches slices the cache into the index block (_draw_device).  Their lists travel in
+the same one H2D copy.  Train-sets up to ops.epoch_perm_max_len() are accepted; for shorter ones
+the batches are those of plain --device-sampling, bit for bit.
 """
 import os
 
@@ -88,6 +99,7 @@ FLAG = "--device-training"
 FLAG_GN = "--device-training-gn-lenet"
 FLAG_SAMPLE = "--device-training-sample"
 FLAG_SAMPLING = "--device-sampling"
+FLAG_CACHED = "--device-sampling-cached"
 SCRATCH_FRACTION = 0.4   # of the free HBM, for one GN-LeNet gradient call's scratch
 # When a sample round takes the one-launch step + average + broadcast
 # (niidmix::sample_step_mean_update) instead of the three ops it restates: slabs of at least
@@ -118,6 +130,11 @@ def sample_run(params):
 def sampling_enabled(params):
     """--device-sampling: the batches come from niidmix.sampling's stream, drawn on the device."""
     return bool(params.get("algorithm", {}).get("device-sampling"))
+
+
+def cached_enabled(params):
+    """--device-sampling-cached: every epoch's permutation is sorted once and kept in HBM."""
+    return bool(params.get("algorithm", {}).get("device-sampling-cached"))
 
 
 def flag_of(params):
@@ -203,8 +220,11 @@ def clique_segments(plan):
 
 def check_sampling(nodes, params):
     """--device-sampling's own refusals, each a ValueError naming the flag: the stream needs the
-    run's seed, and one workgroup sorts a node's whole train-set (ops.draw_batches_max_len)."""
+    run's seed, and one workgroup sorts a node's whole train-set (ops.draw_batches_max_len) --
+    under --device-sampling-cached a train-set may have ops.epoch_perm_max_len() samples; the batch
+    size stays bounded by the index block's kernel."""
     most = ops.draw_batches_max_len()
+    longest = ops.epoch_perm_max_len() if cached_enabled(params) else most
     seed = params.get("meta", {}).get("seed")
     if not isinstance(seed, int) or isinstance(seed, bool):
         raise ValueError(f"{FLAG_SAMPLING} keys its sample stream by params['meta']['seed'], an "
@@ -215,16 +235,18 @@ def check_sampling(nodes, params):
                          "kernel draws")
     for nd in nodes:
         ts = nd.get("train-set")
-        if ts is not None and len(ts) > most:
-            raise ValueError(f"{FLAG_SAMPLING}: node {nd['rank']}'s train-set has {len(ts)} samples, "
-                             f"the kernel sorts at most {most} per node")
+        if ts is not None and len(ts) > longest:
+            raise ValueError(f"{FLAG_CACHED if cached_enabled(params) else FLAG_SAMPLING}: node "
+                             f"{nd['rank']}'s train-set has {len(ts)} samples, "
+                             f"the kernel sorts at most {longest} per node")
         if not 0 <= int(nd["rank"]) < 2 ** 31 or not 0 <= int(nd.get("epoch", 0)) < 2 ** 31 - 1:
             raise ValueError(f"{FLAG_SAMPLING}: node {nd['rank']}'s rank or epoch is outside int32")
 
 
 def check_eligible(nodes, params, topology=None):
     """The refusals that need no GPU (d_sgd.init calls this): raises ValueError naming the flag
-    (--device-sampling's are check_sampling's, and that it needs one of the training flags).
+    (--device-sampling's are check_sampling's, and that it needs one of the training flags;
+    --device-sampling-cached needs --device-sampling).
     Returns (K, C) for linear models and, under --device-training-gn-lenet, (Cin, C, F) for
     GN-LeNet.  --clique-gradient / --unbiased-gradient are accepted when `topology` gives their
     averaging lists (grad_plan).  The 'sample' topology is accepted under --device-training-sample
@@ -232,6 +254,9 @@ def check_eligible(nodes, params, topology=None):
     does, and needs nothing of `topology`."""
     from . import d_sgd
     alg = params["algorithm"]
+    if cached_enabled(params) and not sampling_enabled(params):
+        raise ValueError(f"{FLAG_CACHED} caches the permutations of {FLAG_SAMPLING}'s stream: it needs "
+                         f"{FLAG_SAMPLING}")
     if sampling_enabled(params) and not enabled(params):
         raise ValueError(f"{FLAG_SAMPLING} draws the batches of a device-training round: it needs one "
                          f"of {FLAG}, {FLAG_GN} or {FLAG_SAMPLE}")
@@ -306,6 +331,8 @@ class DeviceTrainer:
         self.family = family.family_of(nodes[0]["model"])[0]
         self.flag = flag_of(params)
         self.sample = sample_run(params)     # fixed for the trainer's life (d_sgd._trainer)
+        self.sampling = sampling_enabled(params)     # and so are these two
+        self.cached = cached_enabled(params)
         self.scratch_budget = None      # bytes of scratch per GN-LeNet gradient call (None:
         self.last_calls = 0              # SCRATCH_FRACTION of the free HBM); calls of the last round
         self.sizes = None                # the kernel's size arguments (family.sizes), set by _materialise
@@ -345,10 +372,16 @@ class DeviceTrainer:
         self.loss = torch.empty(self.n, dtype=torch.float32, device=dev)
         # one round's indices, one H2D copy: [n, b_max] sample indices, [n] batch lengths and, for
         # a sample round (sample_layout), the active rows, their `first` flags and the step lists
-        # and, under --device-sampling (job_layout), the five per-job lists of niidmix::draw_batches
-        self.sampling = sampling_enabled(params)     # fixed for the trainer's life, as `sample` is
-        self.idx_host = torch.zeros(self.n * self.b_max + (4 if self.sample else 1) * self.n +
-                                    (5 * self.n if self.sampling else 0), dtype=torch.int32).pin_memory()
+        # and, under --device-sampling (_init_sampler), the five per-job lists of
+        # niidmix::draw_batches, with the cached mode's lists around them
+        words = self.n * self.b_max + (4 if self.sample else 1) * self.n
+        if self.cached:
+            words += words & 1                       # the two int64 lists start on 8 bytes
+            self.off0, words = words, words + 4 * self.n
+        self.job0 = words
+        if self.sampling:
+            words += (8 if self.cached else 5) * self.n
+        self.idx_host = torch.zeros(words, dtype=torch.int32).pin_memory()
         self.idx_dev = torch.empty_like(self.idx_host, device=dev)
         self.sampler = None
         if self.sampling:
@@ -398,6 +431,9 @@ class DeviceTrainer:
         need = n_buf * self.n * self.ld * 4 + xs.numel() * 4
         # where calls are cut, one row's scratch at least: _cut sizes the calls every round
         need += self._gn_need(1 if self.family.cut else self.n)
+        if self.cached:      # the permutation cache, and the sort's scratch for the longest row alone
+            longest = max(b - a for a, b in zip(self.offsets, self.offsets[1:]))
+            need += self.offsets[-1] * 4 + ops.epoch_perm_scratch_bytes(1, longest)
         free, _ = torch.cuda.mem_get_info(self.device)
         if need > 0.8 * free:
             raise RuntimeError(f"{self.flag}: {need / 2**30:.1f} GiB of device buffers ({n_buf} slabs of "
@@ -407,16 +443,21 @@ class DeviceTrainer:
     def _gn_need(self, rows):
         return self.family.grad_scratch_bytes(rows, self.b_max, self.sizes)
 
+    def _budget(self):
+        """Bytes of scratch one call may take: scratch_budget when set, else SCRATCH_FRACTION of the
+        HBM that was free before the first such call."""
+        if self.scratch_budget is not None:
+            return self.scratch_budget
+        if self._free_budget is None:    # taken once: later rounds see the cached scratch block as used
+            self._free_budget = SCRATCH_FRACTION * torch.cuda.mem_get_info(self.device)[0]
+        return self._free_budget
+
     def _cut(self, n):
         """Rows per call of the gradient kernel over n jobs: all of them for a family whose calls
         are not cut, else as many as keep the call's scratch within the budget."""
         if not self.family.cut:
             return n
-        budget = self.scratch_budget
-        if budget is None:           # taken once: later rounds see the cached scratch block as used
-            if self._free_budget is None:
-                self._free_budget = SCRATCH_FRACTION * torch.cuda.mem_get_info(self.device)[0]
-            budget = self._free_budget
+        budget = self._budget()
         k = cut_rows(n, self._gn_need, budget)
         if k is None:
             raise RuntimeError(f"{self.flag}: {self._gn_need(1) / 2**30:.2f} GiB of scratch for one "
@@ -552,7 +593,10 @@ class DeviceTrainer:
         """--device-sampling: the host's (epoch, cursor) of every row (niidmix.sampling.SamplerState)
         and, behind everything else in the index block, the job lists of niidmix::draw_batches --
         five rows of n int32: rank, seg_start and seg_len (a graph round's job j is row j, so these
-        go up here, once), then epoch and cursor (every round)."""
+        go up here, once), then epoch and cursor (every round).  --device-sampling-cached adds, in
+        front of them, two int64 lists of n -- the jobs' perm_off (a graph round's is the data
+        offset of row j: up here, once) and the perm_off of the rows to sort -- and behind them
+        rank, seg_len and epoch of the rows to sort; and the cache itself."""
         import numpy as np
         from .sampling import SamplerState
         self.seed = int(params["meta"]["seed"]) & 0xFFFFFFFF
@@ -561,36 +605,117 @@ class DeviceTrainer:
         self.sampler = SamplerState([nd["rank"] for nd in nodes], off[1:] - off[:-1], self.b_max,
                                     epochs=[nd.get("epoch", 0) for nd in nodes])
         self.all_rows = np.arange(self.n)
-        self.job0 = self.idx_host.numel() - 5 * self.n
-        job = self.idx_host[self.job0:].view(5, self.n).numpy()
+        job = self._jobs(self.idx_host).numpy()
         job[0], job[1], job[2] = self.sampler.rank, self.seg_start, self.sampler.length
+        if self.cached:
+            self._offs(self.idx_host).numpy()[0] = self.seg_start
+            self.perm = torch.empty(self.offsets[-1], dtype=torch.int32, device=self.device)
+            self.no_scratch = torch.empty(0, dtype=torch.int64, device=self.device)
+            self.short_max = ops.draw_batches_max_len()
+            self.last_perm_jobs = self.last_perm_calls = 0      # of the last round (tests)
         self.idx_dev.copy_(self.idx_host)
+
+    def _jobs(self, block):
+        """The five per-job lists of niidmix::draw_batches in the index block `block` (host or
+        device): [5, n] int32."""
+        return block[self.job0:self.job0 + 5 * self.n].view(5, self.n)
+
+    def _offs(self, block):
+        """--device-sampling-cached: [2, n] int64 -- perm_off of the round's jobs, of the rows to sort."""
+        return block[self.off0:self.job0].view(torch.int64).view(2, self.n)
+
+    def _sort_lists(self, block):
+        """--device-sampling-cached: [3, n] int32 -- rank, seg_len and epoch of the rows to sort."""
+        return block[self.job0 + 5 * self.n:].view(3, self.n)
+
+    def _stale_lists(self, sel):
+        """--device-sampling-cached, before the draw advances the rows `sel`: those whose cached
+        permutation is not their current epoch's go into the sort lists of the pinned block, rows
+        of up to short_max samples first, and are marked cached.  Returns (rows to sort, how many
+        of them are short)."""
+        import numpy as np
+        st = self.sampler
+        stale = st.stale(sel)
+        if stale.size == 0:
+            return stale, 0
+        short = st.length[stale] <= self.short_max
+        stale = np.concatenate([stale[short], stale[~short]])
+        m = stale.size
+        lists = self._sort_lists(self.idx_host).numpy()
+        lists[0, :m], lists[1, :m], lists[2, :m] = st.rank[stale], st.length[stale], st.epoch[stale]
+        self._offs(self.idx_host).numpy()[1, :m] = self.seg_start[stale]
+        st.mark_cached(stale)
+        return stale, int(short.sum())
+
+    def _sort_stale(self, stale, n_short):
+        """niidmix::epoch_perm over the rows `stale` (_stale_lists; their lists are on the device):
+        the short ones in one call without scratch, the long ones in calls of as many rows as keep
+        the scratch within the budget (cut_rows)."""
+        m, length = len(stale), self.sampler.length
+        self.last_perm_jobs, self.last_perm_calls = m, 0
+        if m == 0:
+            return
+        lists, off = self._sort_lists(self.idx_dev), self._offs(self.idx_dev)[1]
+
+        def call(a, b, scratch):
+            ops.epoch_perm(self.seed, lists[0, a:b], lists[1, a:b], lists[2, a:b], off[a:b],
+                           int(length[stale[a:b]].max()), self.perm, scratch)
+            self.last_perm_calls += 1
+        if n_short:
+            call(0, n_short, self.no_scratch)
+        if m > n_short:
+            longest = int(length[stale[n_short:]].max())
+            budget = self._budget()
+            cut = cut_rows(m - n_short, lambda k: ops.epoch_perm_scratch_bytes(k, longest), budget)
+            if cut is None:
+                raise RuntimeError(f"{FLAG_CACHED}: {ops.epoch_perm_scratch_bytes(1, longest) / 2**30:.2f} "
+                                   f"GiB of scratch to sort one row of {longest} samples exceed the "
+                                   f"budget of {budget / 2**30:.2f} GiB")
+            for a in range(n_short, m, cut):
+                b = min(m, a + cut)
+                nbytes = ops.epoch_perm_scratch_bytes(b - a, int(length[stale[a:b]].max()))
+                call(a, b, torch.empty(nbytes // 8, dtype=torch.int64, device=self.device))
 
     def _draw_device(self, active, rows=None):
         """One round's batches under --device-sampling, in place of draw() and _fill_batches(): the
         rows' (epoch, cursor) from the host state, one H2D copy of them (and, for a sample round, of
         its other lists, which lie in front of them) and niidmix::draw_batches, which writes job
-        j's indices and length where the gradient op reads them.  `rows`: the slab rows of a sample
+        j's indices and length where the gradient op reads them (--device-sampling-cached: the rows
+        that begin an epoch are sorted into the cache first, niidmix::take_batches then slices it;
+        their lists go up in the same copy).  `rows`: the slab rows of a sample
         round's active nodes, in the sample's order (only they advance; their rank, seg_start and
         seg_len go up too); None: every row.  Returns {rank: epoch_done}; node['epoch'] counts as
         it does in draw()."""
         n, nb, st = self.n, self.n * self.b_max, self.sampler
         k = n if rows is None else len(rows)
+        if self.cached:
+            stale, n_short = self._stale_lists(self.all_rows if rows is None else rows)
         epoch, cursor, done = st.advance(self.all_rows if rows is None else rows)
         if int(epoch.max()) >= 2 ** 31 - 1:
             raise ValueError(f"{FLAG_SAMPLING}: an epoch count outside int32")
-        job = self.idx_host[self.job0:].view(5, n).numpy()
+        job = self._jobs(self.idx_host).numpy()
         if rows is not None:
             job[0, :k], job[1, :k], job[2, :k] = st.rank[rows], self.seg_start[rows], st.length[rows]
+            if self.cached:
+                self._offs(self.idx_host).numpy()[0, :k] = self.seg_start[rows]
         job[3, :k], job[4, :k] = epoch, cursor
         for nd in active:
             if done[nd["rank"]]:
                 nd["epoch"] += 1
-        first = self.job0 + 3 * n if rows is None else nb + n
-        self.idx_dev[first:].copy_(self.idx_host[first:], non_blocking=True)       # one H2D copy
-        jd = self.idx_dev[self.job0:].view(5, n)[:, :k]
-        ops.draw_batches(self.seed, jd[0], jd[1], jd[2], jd[3], jd[4],
-                         self.idx_dev[:nb].view(n, self.b_max)[:k], self.idx_dev[nb:nb + k])
+        # one H2D copy: a graph round's epochs and cursors (with the sort lists around them when a
+        # row begins an epoch), a sample round's whole tail
+        first = nb + n if rows is not None else self.job0 + 3 * n
+        last = self.job0 + 5 * n
+        if self.cached and len(stale):
+            first, last = first if rows is not None else self.off0 + 2 * n, self.idx_host.numel()
+        self.idx_dev[first:last].copy_(self.idx_host[first:last], non_blocking=True)
+        jd = self._jobs(self.idx_dev)[:, :k]
+        bi, bl = self.idx_dev[:nb].view(n, self.b_max)[:k], self.idx_dev[nb:nb + k]
+        if self.cached:
+            self._sort_stale(stale, n_short)
+            ops.take_batches(self.perm, self._offs(self.idx_dev)[0, :k], jd[1], jd[2], jd[4], bi, bl)
+        else:
+            ops.draw_batches(self.seed, jd[0], jd[1], jd[2], jd[3], jd[4], bi, bl)
         return done
 
     def _sample_sequence(self, x, y, active, lists, n_first):

@@ -21,9 +21,20 @@
            SamplerState.advance.
            --per-node sets every node's train-set length (default 2 x batch; 60 with batch 125
            makes every round an epoch, as MNIST over 1000 nodes does).
+           --cached compares the two sampling modes instead: flag off is plain --device-sampling,
+           flag on adds --device-sampling-cached.
+  cached   device-event times of single launches, alternating within every repetition, of
+           niidmix_epoch_perm_i32 (every job's epoch 0), niidmix_take_batches_i32 at cursor 0,
+           the stateless draw where the segments allow it (up to 8192 samples) and the linear
+           gradient call on the batches taken, at the two shapes above and
+               e60000  1 job of 60 000 samples, B 128
+               e10000  5 jobs of 10 000 samples, B 128
+           and epoch_perm's share of the gradient call once divided by the rounds of an epoch.
 
     python tools/device_sampling_probe.py kernel --shape small [--warmup 5] [--reps 20]
     python tools/device_sampling_probe.py rounds --run linear [--per-node 60] [--warmup 2] [--rounds 10]
+    python tools/device_sampling_probe.py rounds --run linear --cached
+    python tools/device_sampling_probe.py cached --shape e60000 [--warmup 5] [--reps 20]
 
 Every step prints one JSON line.
 """
@@ -39,6 +50,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [REPO, os.path.join(REPO, "non-iid-topology-simulator_amd"), os.path.join(REPO, "tools")]
 
 KERNEL_SHAPES = {"small": (1000, 60, 125), "large": (100, 600, 128)}
+CACHED_SHAPES = {**KERNEL_SHAPES, "e60000": (1, 60000, 128), "e10000": (5, 10000, 128)}
 K, C = 784, 10
 
 
@@ -107,6 +119,89 @@ def kernel(a):
     print(json.dumps(out))
 
 
+def cached(a):
+    import numpy as np
+    import torch
+    from niidmix import _lib, sampling, train
+    n, length, b = CACHED_SHAPES[a.shape]
+    dev = torch.device("cuda:0")
+    ld = train.padded_ld(C * K + C)
+    gen = torch.Generator(device=dev).manual_seed(1)
+    theta = (torch.rand(n, ld, device=dev, generator=gen) - 0.5) * (2 / K ** 0.5)
+    grad = torch.zeros(n, ld, device=dev)
+    data = torch.rand(n * length, K, device=dev, generator=gen)
+    labels = torch.randint(0, C, (n * length,), device=dev, generator=gen).to(torch.int32)
+    i32 = dict(dtype=torch.int32, device=dev)
+    rank = torch.arange(n, **i32)
+    start, seg = rank * length, torch.full((n,), length, **i32)
+    off = start.to(torch.int64)
+    zero = torch.zeros(n, **i32)
+    idx, blen = torch.zeros(n, b, **i32), torch.zeros(n, **i32)
+    idx2, blen2 = torch.zeros(n, b, **i32), torch.zeros(n, **i32)
+    perm = torch.zeros(n * length, **i32)
+    loss = torch.empty(n, device=dev)
+    lib = _lib.lib
+    elems = int(lib.niidmix_linear_nll_grad_rows_scratch_elems(n, b, C))
+    scratch = torch.empty(elems, device=dev)
+    sort_bytes = int(lib.niidmix_epoch_perm_scratch_bytes(n, length))
+    sort_scratch = torch.empty(max(sort_bytes // 8, 2), dtype=torch.int64, device=dev)
+    strm = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+    def perm_call():
+        return lib.niidmix_epoch_perm_i32(a.seed, rank.data_ptr(), seg.data_ptr(), zero.data_ptr(),
+                                          off.data_ptr(), n, length, perm.data_ptr(), perm.numel(),
+                                          sort_scratch.data_ptr(), sort_bytes, strm)
+
+    def take_call():
+        return lib.niidmix_take_batches_i32(perm.data_ptr(), perm.numel(), off.data_ptr(), start.data_ptr(),
+                                            seg.data_ptr(), zero.data_ptr(), n, b, idx.data_ptr(),
+                                            blen.data_ptr(), strm)
+
+    def draw_call():
+        return lib.niidmix_draw_batches_i32(a.seed, rank.data_ptr(), start.data_ptr(), seg.data_ptr(),
+                                            zero.data_ptr(), zero.data_ptr(), n, b, idx2.data_ptr(),
+                                            blen2.data_ptr(), strm)
+
+    def grad_call():
+        return lib.niidmix_linear_nll_grad_rows_f32(
+            theta.data_ptr(), ld, data.data_ptr(), labels.data_ptr(), idx.data_ptr(), blen.data_ptr(),
+            b, rank.data_ptr(), n, grad.data_ptr(), ld, loss.data_ptr(), K, C, scratch.data_ptr(),
+            elems, strm)
+
+    stateless = length <= int(lib.niidmix_draw_batches_max_len())
+    calls = [("epoch_perm", perm_call), ("take", take_call)] + ([("draw", draw_call)] if stateless else []) + \
+        [("grad", grad_call)]
+    times = {name: [] for name, _ in calls}
+    for rep in range(a.warmup + a.reps):
+        for name, fn in calls:
+            s0, e0 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s0.record()
+            _lib.check(fn(), name)
+            e0.record()
+            e0.synchronize()
+            if rep >= a.warmup:
+                times[name].append(s0.elapsed_time(e0) * 1e-3)
+    nb = min(b, length)
+    got, whole = idx.cpu().numpy(), perm.cpu().numpy()
+    for r in (0, n - 1):                                   # what was timed is the stream
+        want = sampling.epoch_permutation(a.seed, r, 0, length)
+        assert np.array_equal(whole[r * length:(r + 1) * length], want), r
+        assert np.array_equal(got[r, :nb], r * length + want[:nb]), r
+    assert bool((blen == nb).all()) and bool(torch.isfinite(loss).all())
+    assert not stateless or (torch.equal(idx2[:, :nb], idx[:, :nb]) and torch.equal(blen2, blen))
+    rounds_per_epoch = -(-length // b)
+    out = {"step": "cached", "shape": a.shape, "n": n, "len": length, "b": b, "k": K, "c": C,
+           "warmup": a.warmup, "reps": a.reps, "device": torch.cuda.get_device_name(dev),
+           "lib_sha16": _lib.lib_sha16(), "rounds_per_epoch": rounds_per_epoch}
+    for name, _ in calls:
+        out[name] = _stats(times[name])
+    out["epoch_perm_per_round_over_grad"] = out["epoch_perm"]["median_ms"] / rounds_per_epoch / \
+        out["grad"]["median_ms"]
+    if stateless:
+        out["take_over_draw"] = out["take"]["median_ms"] / out["draw"]["median_ms"]
+    print(json.dumps(out))
+
+
 def rounds(a):
     import torch
     import torch.nn.functional as F
@@ -154,7 +249,9 @@ def rounds(a):
                                 "initial-averaging": False, "clique-gradient": False,
                                 "unbiased-gradient": False, "deferred-writeback": True,
                                 "mixing-mode": "exact", "device-training": True,
-                                **{f: True for f in flags}, **({"device-sampling": True} if on else {})}}
+                                **{f: True for f in flags},
+                                **({"device-sampling": True} if on or a.cached else {}),
+                                **({"device-sampling-cached": True} if on and a.cached else {})}}
         nodes = []
         for r in range(n):
             mdl = Net()
@@ -174,15 +271,17 @@ def rounds(a):
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
             run["trainer"] = d_sgd._trainers[id(run["state"]["nodes"])]
-            assert run["trainer"].sampling == on
+            assert run["trainer"].sampling == (on or a.cached) and run["trainer"].cached == (on and a.cached)
             if rnd >= a.warmup:
                 run["times"].append(dt)
-    out = {"step": "rounds", "run": a.run, "n": n, "k": k, "c": C, "b": b, "per_node": per_node,
+    out = {"step": "rounds", "run": a.run, "cached": a.cached, "n": n, "k": k, "c": C, "b": b, "per_node": per_node,
            "sample": a.sample if a.run == "sample" else None, "momentum": a.momentum,
            "warmup": a.warmup, "rounds": a.rounds, "threads": torch.get_num_threads(),
            "device": torch.cuda.get_device_name(0)}
     out["flag_off"], out["flag_on"] = _stats(runs[False]["times"]), _stats(runs[True]["times"])
     out["on_over_off"] = out["flag_on"]["median_ms"] / out["flag_off"]["median_ms"]
+    out["on_median_within_off_spread"] = \
+        out["flag_off"]["min_ms"] <= out["flag_on"]["median_ms"] <= out["flag_off"]["max_ms"]
     # what is left on the host in a flag-on round, each alone between two synchronises: the
     # synchronous write-back of the slab, the loss copy, and the sampler's host part
     tr, parts = runs[True]["trainer"], {"write_back": [], "loss_d2h": [], "advance": []}
@@ -201,8 +300,10 @@ def rounds(a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("step", choices=["kernel", "rounds"])
-    ap.add_argument("--shape", choices=list(KERNEL_SHAPES), default="small")
+    ap.add_argument("step", choices=["kernel", "rounds", "cached"])
+    ap.add_argument("--shape", choices=list(CACHED_SHAPES), default="small")
+    ap.add_argument("--cached", action="store_true",
+                    help="rounds: flag off is plain --device-sampling, flag on adds --device-sampling-cached")
     ap.add_argument("--run", choices=["linear", "sample", "gn"], default="linear")
     ap.add_argument("--nodes", type=int, default=1000)
     ap.add_argument("--sample", type=int, default=100, help="rounds --run sample: the sample size")
@@ -219,7 +320,9 @@ def main():
         sys.exit("device_sampling_probe: no GPU (a time is only ever measured on one)")
     if a.warmup is None:
         a.warmup = 2 if a.step == "rounds" else 5
-    {"kernel": kernel, "rounds": rounds}[a.step](a)
+    if a.step == "kernel" and a.shape not in KERNEL_SHAPES:
+        sys.exit(f"device_sampling_probe: kernel --shape is one of {list(KERNEL_SHAPES)}")
+    {"kernel": kernel, "rounds": rounds, "cached": cached}[a.step](a)
 
 
 if __name__ == "__main__":
