@@ -33,7 +33,10 @@
  * its niidmix_draw_batches_max_len added (training batches drawn on the device, for
  * --device-sampling; a pure addition too); niidmix_epoch_perm_i32, niidmix_take_batches_i32,
  * niidmix_epoch_perm_max_len and niidmix_epoch_perm_scratch_bytes added (a whole epoch's
- * permutation sorted once and sliced every round, for --device-sampling-cached; pure additions too).
+ * permutation sorted once and sliced every round, for --device-sampling-cached; pure additions too);
+ * niidmix_linear_nll_grad_rows_sliced_f32, niidmix_linear_nll_grad_rows_sliced_scratch_elems and
+ * niidmix_linear_nll_grad_rows_sliced_slice added (the linear gradient at any batch size, for
+ * --device-training-large-batch; pure additions too).
  * ABI 5: niidmix_dense_split_elems / niidmix_dense_split_w /
  * niidmix_mix_dense_bf16x6_f32 added (the dense GEMM on the bf16 matrix cores, fp32-accurate by
  * three-term splitting); niidmix_mix_strip_f32 refuses a strip that does not fit the device's LDS.
@@ -543,6 +546,45 @@ int niidmix_linear_nll_grad_rows_f32(const float *theta, int64_t ld_t, const flo
                                      int64_t n_rows, float *grad, int64_t ld_g, float *loss,
                                      int64_t K, int64_t C, float *scratch, int64_t scratch_elems,
                                      void *stream);
+
+/* niidmix_linear_nll_grad_rows_f32 at any batch size (the drop-in's --device-training-large-batch:
+ * few nodes with long batches, down to the reference's centralised baseline of one node and
+ * batches of 12 800).  The arguments, their order, the loss and gradient computed, the argument
+ * checks, the error codes and the clamping of batch_len to [0, b_max] are those of
+ * niidmix_linear_nll_grad_rows_f32; only the limits and the scratch differ:
+ *   Limits (NIIDMIX_EUNSUPPORTED beyond): C <= 1024, K <= 2^20, 1 <= b_max <= 2^20; a scratch size
+ *   beyond int64 or a grid beyond int32.
+ *   scratch   at least niidmix_linear_nll_grad_rows_sliced_scratch_elems(n_rows, b_max, K, C)
+ *             floats (0 for a non-positive size): the partial logits / dz, one partial gradient
+ *             row of P floats (padded to 4) per (row, slice), one loss partial per (row, slice).
+ * A batch is cut into slices of S = niidmix_linear_nll_grad_rows_sliced_slice(C) samples, slice q =
+ * samples [qS, min((q + 1) S, len)): S is the largest power of two with S * C <= 8192 and
+ * S <= 1024 (0 for a C outside 1..1024), a function of C alone, so that a slice's dz takes
+ * S * C * 4 <= 32768 bytes of LDS and five workgroups share a CU.  Four launches: the partial
+ * logits as in niidmix_linear_nll_grad_rows_f32; per (row, slice) the max-subtracted softmax, dz
+ * divided by the WHOLE batch's len and the slice's loss partial; per (row, slice, column chunk,
+ * class block) the slice's dW / db into the partial gradients, a lane summing the slice's samples
+ * in order; per (row, column) the partials summed in slice order into grad, and loss =
+ * -(sum of the loss partials in slice order) / len.  Slices that start at or past len are skipped
+ * by every launch.  A row with len = 0 gets a zero gradient and the loss 0 / 0, as from
+ * niidmix_linear_nll_grad_rows_f32.
+ * No floating-point atomics: every output bit is a function of (n_rows, b_max, K, C), the leading
+ * dimensions, the pointer alignments and the inputs alone.  Of the four sizes the SUMMATION ORDER
+ * depends on n_rows and K (the K-chunks of the partial logits, as in
+ * niidmix_linear_nll_grad_rows_f32) and on C (the slice length S and the lanes per sample of the
+ * softmax); it does not depend on b_max, which only sizes the scratch: a batch gives the same bits
+ * under any b_max >= len.  Not bit-identical to niidmix_linear_nll_grad_rows_f32 where both take a
+ * shape (the slices are another order); both are within 1e-5 of the condition-aware bound
+ * (tests/test_gpu_train_large_batch.py). */
+int64_t niidmix_linear_nll_grad_rows_sliced_slice(int64_t C);
+int64_t niidmix_linear_nll_grad_rows_sliced_scratch_elems(int64_t n_rows, int64_t b_max, int64_t K,
+                                                          int64_t C);
+int niidmix_linear_nll_grad_rows_sliced_f32(const float *theta, int64_t ld_t, const float *data,
+                                            const int32_t *labels, const int32_t *batch_idx,
+                                            const int32_t *batch_len, int64_t b_max, const int32_t *rows,
+                                            int64_t n_rows, float *grad, int64_t ld_g, float *loss,
+                                            int64_t K, int64_t C, float *scratch, int64_t scratch_elems,
+                                            void *stream);
 
 /* Evaluation of a linear classifier on the listed rows: what the reference's logger computes per
  * node on the CPU (model.forward + F.nll_loss(reduction='sum') + argmax over a DataLoader), for

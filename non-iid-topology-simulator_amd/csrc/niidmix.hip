@@ -37,6 +37,8 @@
 //                                                                  _sample_step_mean_update_f32
 //   linear model       k_lin_logits, k_lin_softmax, k_lin_dw,      niidmix_linear_nll_grad_rows_f32,
 //                      k_lin_eval, k_lin_eval_sum                  niidmix_linear_eval_rows_f32
+//                      k_lin_softmax_sl, k_lin_dw_sl,              niidmix_linear_nll_grad_rows_sliced_f32
+//                      k_lin_reduce_sl                             (any batch size: slices of the batch)
 //   model_gnlenet.inc  k_gnl_eval, k_gnl_grad_sample / _conv / _fc niidmix_gnlenet_eval_rows_f32,
 //                                                                  niidmix_gnlenet_nll_grad_rows_f32
 //   sampling.inc       k_draw_batches, k_epoch_perm_chunks /       niidmix_draw_batches_i32, _epoch_perm_i32,
@@ -4506,6 +4508,197 @@ __global__ __launch_bounds__(256) void k_lin_dw(const float *__restrict__ data,
 }
 
 // ----------------------------------------------------------------------------------------------
+// The same gradient at any batch size (niidmix_linear_nll_grad_rows_sliced_f32): few rows with a
+// long batch.  The batch is cut into slices of S = lin_slice(C) samples, slice q = samples
+// [qS, min((q + 1) S, len)), so that a slice's dz (S * C floats, 32 KiB at most) sits in LDS with
+// several workgroups per CU and the grid grows with the batch.  Four launches, no atomics:
+//   k_lin_logits      as above (it takes any b_max)
+//   k_lin_softmax_sl  per (row, slice): k_lin_softmax over the slice's samples, dz divided by the
+//                     whole batch's len, one loss partial (sum_s z[s,y_s] - lse_s) per slice
+//   k_lin_dw_sl       per (row, slice, 256-lane column chunk, class-block slice): k_lin_dw over the
+//                     slice, 16 gathers in flight, into the partial gradients [n_rows, n_slices, ldp]
+//   k_lin_reduce_sl   per (row, 256 columns): the partials summed in slice order into grad; the
+//                     loss partials summed in slice order, loss = -sum / len
+// A block whose slice starts at or past len returns at once and the reduction reads the first
+// ceil(len / S) slices only: a short row costs what its own length costs.
+// Scratch: [n_rows, split, b_max, C] partial logits / dz (rounded up to 4 floats), then the partial
+// gradients [n_rows, n_slices, ldp] (ldp = P rounded up to 4), then the loss partials
+// [n_rows, n_slices]; n_slices = ceil(b_max / S).
+constexpr int64_t kLinMaxBSliced = 1 << 20;   // b_max
+constexpr int64_t kLinSliceBC = 8192;         // S * C at most: a slice's dz in LDS (32 KiB)
+constexpr int kLinSlG = 16;                   // gathers k_lin_dw_sl keeps in flight
+
+__global__ __launch_bounds__(256) void k_lin_softmax_sl(const float *__restrict__ theta, int64_t ld_t,
+                                                        const int32_t *__restrict__ labels,
+                                                        const int32_t *__restrict__ batch_idx,
+                                                        const int32_t *__restrict__ batch_len, int b_max,
+                                                        const int32_t *__restrict__ rows, int K, int C,
+                                                        int n_kc, int split, int S, int n_sl, float *part,
+                                                        float *__restrict__ loss_part) {
+    __shared__ float red[256];
+    const int64_t i = blockIdx.x / n_sl;
+    const int q = (int)(blockIdx.x % n_sl);
+    const int len = lin_len(batch_len, i, b_max);
+    const int s_lo = q * S;
+    if (s_lo >= len) return;                           // an empty slice: the reduction skips it
+    const int s_hi = s_lo + S < len ? s_lo + S : len;
+    const float *bias = theta + (int64_t)rows[i] * ld_t + (int64_t)C * K;
+    const int32_t *idx = batch_idx + i * b_max;
+    const int64_t stride = (int64_t)b_max * C;
+    float *z = part + i * split * stride;
+    int G = 64;
+    while (G > 1 && (G >> 1) >= C) G >>= 1;
+    const int gl = threadIdx.x & (G - 1), g = threadIdx.x / G, ng = 256 / G;
+    const float flen = (float)len;
+    float tsum = 0.f;
+    for (int sb = s_lo; sb < s_hi; sb += ng) {
+        const int s = sb + g;
+        const bool on = s < s_hi;
+        float *zs = z + (int64_t)(on ? s : s_lo) * C;
+        const int y = on ? labels[idx[s]] : -1;
+        float m = -__builtin_inff();
+        if (on)
+            for (int c = gl; c < C; c += G) {
+                float a = zs[c];
+                for (int kc = 1; kc < n_kc; ++kc) a += zs[kc * stride + c];
+                a += bias[c];
+                zs[c] = a;
+                m = fmaxf(m, a);
+            }
+        for (int o = G >> 1; o; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+        float se = 0.f, zy = 0.f;
+        if (on)
+            for (int c = gl; c < C; c += G) {
+                const float a = zs[c];
+                se += expf(a - m);
+                if (c == y) zy = a;
+            }
+        for (int o = G >> 1; o; o >>= 1) { se += __shfl_xor(se, o); zy += __shfl_xor(zy, o); }
+        const float lse = m + logf(se);
+        if (on) {
+            for (int c = gl; c < C; c += G) zs[c] = (expf(zs[c] - lse) - (c == y ? 1.f : 0.f)) / flen;
+            if (gl == 0) tsum += zy - lse;
+        }
+    }
+    red[threadIdx.x] = gl == 0 ? tsum : 0.f;
+    __syncthreads();
+    for (int o = 128; o; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) loss_part[i * n_sl + q] = red[0];
+}
+
+template <int V, bool C4>      // V = 4: float4 gathers and stores (K % 4 == 0, data and scratch aligned)
+__global__ __launch_bounds__(256) void k_lin_dw_sl(const float *__restrict__ data,
+                                                   const int32_t *__restrict__ batch_idx,
+                                                   const int32_t *__restrict__ batch_len, int b_max,
+                                                   int K, int C, int n_kch, int split, int S, int n_sl,
+                                                   const float *__restrict__ part,
+                                                   float *__restrict__ pgrad, int64_t ldp) {
+    extern __shared__ __attribute__((aligned(16))) float lin_dz_sl[];     // [n_s, C]
+    const int kch = (int)(blockIdx.x % n_kch);
+    const int64_t iq = blockIdx.x / n_kch, i = iq / n_sl;
+    const int q = (int)(iq % n_sl);
+    const int len = lin_len(batch_len, i, b_max);
+    const int s_lo = q * S;
+    if (s_lo >= len) return;                           // an empty slice: the reduction skips it
+    const int n_s = len - s_lo < S ? len - s_lo : S;
+    const int32_t *idx = batch_idx + i * b_max + s_lo;
+    const float *src = part + i * split * ((int64_t)b_max * C) + (int64_t)s_lo * C;
+    const int n = n_s * C;
+    if constexpr (C4) {
+        for (int t = threadIdx.x * 4; t < n; t += 1024)
+            *reinterpret_cast<float4 *>(lin_dz_sl + t) = ld4(src + t);
+    } else {
+        for (int t = threadIdx.x; t < n; t += 256) lin_dz_sl[t] = src[t];
+    }
+    __syncthreads();
+    float *g = pgrad + iq * ldp;
+    const int k = (kch * 256 + (int)threadIdx.x) * V;
+    const int ncb = (C + kLinDC - 1) / kLinDC;
+    if (k < K) {
+        for (int cb = blockIdx.y; cb < ncb; cb += gridDim.y) {
+            const int c0 = cb * kLinDC;
+            float acc[kLinDC][V];
+#pragma unroll
+            for (int j = 0; j < kLinDC; ++j)
+#pragma unroll
+                for (int e = 0; e < V; ++e) acc[j][e] = 0.f;
+            for (int s0 = 0; s0 < n_s; s0 += kLinSlG) {
+                float xv[kLinSlG][V];
+#pragma unroll
+                for (int u = 0; u < kLinSlG; ++u)
+                    ldv<V>(data + (int64_t)idx[s0 + u < n_s ? s0 + u : s0] * K + k, xv[u]);
+#pragma unroll
+                for (int u = 0; u < kLinSlG; ++u) {
+                    if (s0 + u < n_s) {
+                        const float *dzs = lin_dz_sl + (s0 + u) * C + c0;
+                        float d[kLinDC];
+                        if constexpr (C4) {
+#pragma unroll
+                            for (int f = 0; f < kLinDC / 4; ++f) {
+                                float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
+                                if (c0 + 4 * f < C) t = *reinterpret_cast<const float4 *>(dzs + 4 * f);
+                                d[4 * f] = t.x; d[4 * f + 1] = t.y; d[4 * f + 2] = t.z; d[4 * f + 3] = t.w;
+                            }
+                        } else {
+#pragma unroll
+                            for (int j = 0; j < kLinDC; ++j) d[j] = c0 + j < C ? dzs[j] : 0.f;
+                        }
+#pragma unroll
+                        for (int j = 0; j < kLinDC; ++j)
+#pragma unroll
+                            for (int e = 0; e < V; ++e)
+                                acc[j][e] = __builtin_fmaf(d[j], xv[u][e], acc[j][e]);
+                    }
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < kLinDC; ++j) {
+                if (c0 + j < C) {
+                    float *o = g + (int64_t)(c0 + j) * K + k;
+                    if constexpr (V == 4) *reinterpret_cast<float4 *>(o) = make_float4(acc[j][0], acc[j][1], acc[j][2], acc[j][3]);
+                    else o[0] = acc[j][0];
+                }
+            }
+        }
+    }
+    if (kch == 0 && blockIdx.y == 0)
+        for (int c = threadIdx.x; c < C; c += 256) {
+            float a = 0.f;
+            for (int s = 0; s < n_s; ++s) a += lin_dz_sl[s * C + c];
+            g[(int64_t)C * K + c] = a;
+        }
+}
+
+__global__ __launch_bounds__(256) void k_lin_reduce_sl(const float *__restrict__ pgrad, int64_t ldp,
+                                                       const float *__restrict__ loss_part,
+                                                       const int32_t *__restrict__ batch_len, int b_max,
+                                                       const int32_t *__restrict__ rows, int64_t P,
+                                                       int n_pc, int S, int n_sl,
+                                                       float *__restrict__ grad, int64_t ld_g,
+                                                       float *__restrict__ loss) {
+    const int64_t i = blockIdx.x / n_pc;
+    const int pc = (int)(blockIdx.x % n_pc);
+    const int len = lin_len(batch_len, i, b_max);
+    const int nq = (len + S - 1) / S;                  // the slices that hold samples
+    const int64_t col = (int64_t)pc * 256 + threadIdx.x;
+    if (col < P) {
+        const float *p = pgrad + i * n_sl * ldp + col;
+        float a = 0.f;
+#pragma unroll 4
+        for (int q = 0; q < nq; ++q) a += p[q * ldp];
+        grad[(int64_t)rows[i] * ld_g + col] = a;
+    }
+    if (pc == 0 && threadIdx.x == 0) {
+        float t = 0.f;
+        for (int q = 0; q < nq; ++q) t += loss_part[i * n_sl + q];
+        loss[i] = -t / (float)len;
+    }
+}
+
+// ----------------------------------------------------------------------------------------------
 // Evaluation of a linear classifier (niidmix_linear_eval_rows_f32): job i scores slab row rows[i]
 // (W [C, K] then b [C], as above) on the contiguous samples data[seg_start[i] .. + seg_len[i]):
 // summed NLL, number of correct argmax predictions and, optionally, the predictions.  Two launches:
@@ -5976,6 +6169,112 @@ int niidmix_linear_nll_grad_rows_f32(const float *theta, int64_t ld_t, const flo
                        dim3(256), lds, s, data, batch_idx, batch_len, ib, rows, iK, iC, (int)n_kch,
                        (int)split, (const float *)scratch, grad, ld_g);
     return check_launch("k_lin_dw");
+}
+
+// Samples per slice: the largest power of two with S * C <= 8192 floats (32 KiB of LDS: five
+// workgroups of k_lin_dw_sl per CU), at most 1024; a function of C alone.
+int64_t niidmix_linear_nll_grad_rows_sliced_slice(int64_t C) {
+    if (C <= 0 || C > kLinMaxC) return 0;
+    int64_t s = 1024;
+    while (s * C > kLinSliceBC) s >>= 1;
+    return s;
+}
+
+// The scratch layout of the sliced entry: floats of partial logits / dz (rounded up to 4) and of the
+// partial gradients; the loss partials follow.  False when a size exceeds int64.
+static bool lin_sliced_layout(int64_t n_rows, int64_t b_max, int64_t K, int64_t C, int64_t *part,
+                              int64_t *pgrad, int64_t *total) {
+    const int64_t S = niidmix_linear_nll_grad_rows_sliced_slice(C);
+    const int64_t n_sl = (b_max + S - 1) / S;
+    int64_t ldp, a, b, c;
+    if (__builtin_mul_overflow(C, K + 1, &ldp) || __builtin_add_overflow(ldp, (int64_t)3, &ldp)) return false;
+    ldp = ldp / 4 * 4;
+    if (__builtin_mul_overflow(n_rows, lin_split(n_rows), &a) || __builtin_mul_overflow(a, b_max, &a) ||
+        __builtin_mul_overflow(a, C, &a) || __builtin_add_overflow(a, (int64_t)3, &a))
+        return false;
+    a = a / 4 * 4;
+    if (__builtin_mul_overflow(n_rows, n_sl, &c) || __builtin_mul_overflow(c, ldp, &b)) return false;
+    *part = a;
+    *pgrad = b;
+    return !__builtin_add_overflow(a, b, total) && !__builtin_add_overflow(*total, c, total);
+}
+
+int64_t niidmix_linear_nll_grad_rows_sliced_scratch_elems(int64_t n_rows, int64_t b_max, int64_t K,
+                                                          int64_t C) {
+    if (n_rows <= 0 || b_max <= 0 || K <= 0 || C <= 0 || C > kLinMaxC) return 0;
+    int64_t part, pgrad, total;
+    return lin_sliced_layout(n_rows, b_max, K, C, &part, &pgrad, &total) ? total : INT64_MAX;
+}
+
+int niidmix_linear_nll_grad_rows_sliced_f32(const float *theta, int64_t ld_t, const float *data,
+                                            const int32_t *labels, const int32_t *batch_idx,
+                                            const int32_t *batch_len, int64_t b_max, const int32_t *rows,
+                                            int64_t n_rows, float *grad, int64_t ld_g, float *loss,
+                                            int64_t K, int64_t C, float *scratch, int64_t scratch_elems,
+                                            void *stream) {
+    if (n_rows < 0 || b_max < 0 || K < 0 || C < 0 || scratch_elems < 0)
+        return set_error(NIIDMIX_EINVAL, "negative size");
+    if (n_rows == 0) return NIIDMIX_OK;
+    if (!theta || !data || !labels || !batch_idx || !batch_len || !rows || !grad || !loss || !scratch)
+        return set_error(NIIDMIX_EINVAL, "null pointer");
+    if (b_max == 0 || K == 0 || C == 0) return set_error(NIIDMIX_EINVAL, "b_max, K and C must be >= 1");
+    if (C > kLinMaxC || b_max > kLinMaxBSliced)
+        return set_error(NIIDMIX_EUNSUPPORTED, "C %lld, b_max %lld: the kernel holds C <= %lld and "
+                         "b_max <= %lld", (long long)C, (long long)b_max, (long long)kLinMaxC,
+                         (long long)kLinMaxBSliced);
+    if (K > (1 << 20)) return set_error(NIIDMIX_EUNSUPPORTED, "K %lld > 2^20", (long long)K);
+    const int64_t p = C * K + C;
+    if (int rc = check_ld(ld_t, ld_g, p, "C * K + C")) return rc;
+    int64_t n_part, n_pgrad, need;
+    if (!lin_sliced_layout(n_rows, b_max, K, C, &n_part, &n_pgrad, &need))
+        return set_error(NIIDMIX_EUNSUPPORTED, "n_rows %lld, b_max %lld: the scratch size exceeds int64",
+                         (long long)n_rows, (long long)b_max);
+    if (scratch_elems < need)
+        return set_error(NIIDMIX_EINVAL, "scratch of %lld elements, %lld needed", (long long)scratch_elems,
+                         (long long)need);
+    // `rows` lives on the device: n_rows distinct rows reach at least row n_rows - 1
+    if (int rc = check_overlap(theta, ld_t, grad, ld_g, n_rows, p, "theta and grad overlap")) return rc;
+    if (overlaps(scratch, need, theta, slab_extent(n_rows, ld_t, p)) ||
+        overlaps(scratch, need, grad, slab_extent(n_rows, ld_g, p)))
+        return set_error(NIIDMIX_EALIAS, "scratch overlaps theta or grad");
+    const int64_t S = niidmix_linear_nll_grad_rows_sliced_slice(C);
+    const int64_t n_sl = (b_max + S - 1) / S, ldp = (p + 3) / 4 * 4;
+    const int64_t split = lin_split(n_rows);
+    const int64_t kchunk = ((K + split - 1) / split + 255) / 256 * 256;
+    const int64_t n_kc = (K + kchunk - 1) / kchunk;
+    const int v1 = vec_width({K, ld_t}, {theta, data}) == 4 ? 4 : 1;
+    const int v3 = vec_width({K}, {data}) == 4 && aligned16(scratch) ? 4 : 1;
+    const bool c4 = C % 4 == 0 && aligned16(scratch);
+    const int64_t n_kch = (K + 256 * v3 - 1) / (256 * v3), n_pc = (p + 255) / 256;
+    // n_rows * n_sl fits int64: it is a factor of the scratch size
+    if (n_rows * n_kc > 0x7fffffff || n_rows * n_sl > 0x7fffffff / n_kch || n_rows > 0x7fffffff / n_pc)
+        return set_error(NIIDMIX_EUNSUPPORTED, "n_rows %lld, b_max %lld: too many blocks", (long long)n_rows,
+                         (long long)b_max);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int ib = (int)b_max, iK = (int)K, iC = (int)C, iS = (int)S, isl = (int)n_sl;
+    float *pgrad = scratch + n_part, *loss_part = pgrad + n_pgrad;
+
+    auto k1 = pick<4, 1>(v1, [](auto V) { return k_lin_logits<V()>; });
+    const int64_t tiles = ((b_max + 3) / 4) * ((C + 3) / 4);
+    hipLaunchKernelGGL(k1, dim3((unsigned)(n_rows * n_kc), lin_slices(n_rows * n_kc, (tiles + 3) / 4)),
+                       dim3(256), 0, s, theta, ld_t, data, batch_idx, batch_len, ib, rows, iK, iC,
+                       (int)kchunk, (int)n_kc, (int)split, scratch);
+    if (int rc = check_launch("k_lin_logits")) return rc;
+    hipLaunchKernelGGL(k_lin_softmax_sl, dim3((unsigned)(n_rows * n_sl)), dim3(256), 0, s, theta, ld_t,
+                       labels, batch_idx, batch_len, ib, rows, iK, iC, (int)n_kc, (int)split, iS, isl,
+                       scratch, loss_part);
+    if (int rc = check_launch("k_lin_softmax_sl")) return rc;
+    auto k3 = pick<4, 1>(v3, [&](auto V) { return pick<true, false>(c4, [&](auto C4) {
+        return k_lin_dw_sl<V(), C4()>; }); });
+    const int64_t blocks = n_rows * n_sl * n_kch;
+    hipLaunchKernelGGL(k3, dim3((unsigned)blocks, lin_slices(blocks, (C + kLinDC - 1) / kLinDC)), dim3(256),
+                       (size_t)((S < b_max ? S : b_max) * C) * sizeof(float), s, data, batch_idx, batch_len,
+                       ib, iK, iC, (int)n_kch, (int)split, iS, isl, (const float *)scratch, pgrad, ldp);
+    if (int rc = check_launch("k_lin_dw_sl")) return rc;
+    hipLaunchKernelGGL(k_lin_reduce_sl, dim3((unsigned)(n_rows * n_pc)), dim3(256), 0, s,
+                       (const float *)pgrad, ldp, (const float *)loss_part, batch_len, ib, rows, p,
+                       (int)n_pc, iS, isl, grad, ld_g, loss);
+    return check_launch("k_lin_reduce_sl");
 }
 
 static int64_t ev_tiles(int64_t max_len) { return (max_len + kEvTS - 1) / kEvTS; }

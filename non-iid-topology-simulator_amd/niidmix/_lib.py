@@ -100,6 +100,11 @@ SIGNATURES = {
     "niidmix_linear_nll_grad_rows_scratch_elems": (_i64, [_i64, _i64, _i64]),
     "niidmix_linear_nll_grad_rows_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64,
                                                         _vp, _i64, _vp, _i64, _i64, _vp, _i64, _vp]),
+    "niidmix_linear_nll_grad_rows_sliced_slice": (_i64, [_i64]),
+    "niidmix_linear_nll_grad_rows_sliced_scratch_elems": (_i64, [_i64, _i64, _i64, _i64]),
+    "niidmix_linear_nll_grad_rows_sliced_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp,
+                                                               _i64, _vp, _i64, _vp, _i64, _i64, _vp,
+                                                               _i64, _vp]),
     "niidmix_linear_eval_rows_scratch_bytes": (_i64, [_i64, _i64, _i64]),
     "niidmix_linear_eval_rows_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64,
                                                     _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp]),

@@ -782,6 +782,9 @@ def _device_training_step(state, params, rundir):
     if tr.cached != train.cached_enabled(params):
         raise ValueError(f"{train.FLAG_CACHED} was switched during the run, under a live device "
                          "trainer: not supported")
+    if tr.large != train.large_enabled(params):
+        raise ValueError(f"{train.FLAG_LARGE} was switched during the run, under a live device "
+                         "trainer: not supported")
     if tr.sample:
         # --device-training-sample (d_sgd.py:236-250): only the sample trains and steps, its
         # average replaces every model (niidmix.train.DeviceTrainer.sample_round)
@@ -910,7 +913,8 @@ def init(nodes, topology, params):
     if params["algorithm"].get("device-evaluation"):
         from . import evaluate
         evaluate.check_eligible(nodes, params)            # refusals: ValueError naming the flag
-    if params["algorithm"].get("device-training") or params["algorithm"].get("device-sampling"):
+    if params["algorithm"].get("device-training") or params["algorithm"].get("device-sampling") or \
+            params["algorithm"].get("device-training-large-batch"):
         from . import train
         train.check_eligible(nodes, params, topology)     # refusals: ValueError naming the flag
         for n in nodes:
@@ -1141,6 +1145,14 @@ def main(argv=None):
                          "with --device-training-gn-lenet, ignores --clique-gradient and "
                          "--unbiased-gradient as the reference's sample rounds do; on another "
                          "topology it is plain --device-training")
+    ap.add_argument("--device-training-large-batch", action="store_const", const=True, default=False,
+                    help="with --device-training or --device-training-sample, linear models only "
+                         "(GN-LeNet has no such limit and refuses the flag): batch sizes beyond "
+                         "batch-size * C = 32768, up to 2^20, train on kernels that cut the batch "
+                         "into slices -- few nodes with long batches, down to the reference's "
+                         "centralised baseline of one node and batches of 12800; with "
+                         "--device-sampling-cached the batches drawn on the device may be that long "
+                         "too; a batch the existing kernel takes keeps it, bit for bit")
     ap.add_argument("--device-sampling", action="store_const", const=True, default=False,
                     help="with one of the three --device-training flags: the training batches are "
                          "drawn on the device from a sample stream of the plugin's own (Philox keys "
@@ -1169,6 +1181,10 @@ def main(argv=None):
                                      or args.device_training_sample):
         ap.error("--device-sampling needs one of --device-training, --device-training-gn-lenet or "
                  "--device-training-sample")
+    if args.device_training_large_batch and (args.device_training_gn_lenet or not (
+            args.device_training or args.device_training_sample)):
+        ap.error("--device-training-large-batch needs --device-training or --device-training-sample, "
+                 "with linear models (not --device-training-gn-lenet)")
     if args.device_sampling_cached and not args.device_sampling:
         ap.error("--device-sampling-cached needs --device-sampling")
     rundir = m.rundir(args)
@@ -1192,6 +1208,7 @@ def main(argv=None):
            or args.device_training_sample else {}),
         **({"device-training-gn-lenet": True} if args.device_training_gn_lenet else {}),
         **({"device-training-sample": True} if args.device_training_sample else {}),
+        **({"device-training-large-batch": True} if args.device_training_large_batch else {}),
         **({"device-sampling": True} if args.device_sampling else {}),
         **({"device-sampling-cached": True} if args.device_sampling_cached else {}),
         **({"device-evaluation": True} if args.device_evaluation else {}),

@@ -19,7 +19,7 @@ import torch.nn.functional as F
 from . import ops
 from ._lib import lib
 from .model import flatten
-from .ops import GN_MAX_CIN, GN_MAX_HW, GN_MIN_HW, MAX_BC, MAX_C
+from .ops import GN_MAX_CIN, GN_MAX_HW, GN_MIN_HW, MAX_B_SLICED, MAX_BC, MAX_C
 
 PROBE_SAMPLES = 8
 
@@ -163,10 +163,16 @@ class _Linear:
     def P(self, shape):
         return shape[1] * shape[0] + shape[1]
 
-    def limits(self, shape, flag, batch=None):
+    def limits(self, shape, flag, batch=None, large=False):
         """ValueError naming `flag` when the kernels do not hold C classes (or, for training,
-        batches of `batch` samples)."""
+        batches of `batch` samples).  `large` (--device-training-large-batch): batches beyond
+        MAX_BC go to the sliced kernels, which hold MAX_B_SLICED samples."""
         c = shape[1]
+        if large and batch is not None and c <= MAX_C:
+            if batch > MAX_B_SLICED:
+                raise ValueError(f"{flag}: batch-size = {batch} exceeds the sliced kernel's limit "
+                                 f"(batch-size <= {MAX_B_SLICED})")
+            return
         if batch is not None and (c > MAX_C or batch * c > MAX_BC):
             raise ValueError(f"{flag}: C = {c}, batch-size * C = {batch * c} exceed the kernel's limits "
                              f"(C <= {MAX_C}, batch-size * C <= {MAX_BC})")
@@ -181,14 +187,24 @@ class _Linear:
                              f"model takes K = {shape[0]}")
         return shape
 
-    def grad_rows(self, theta, data, labels, bi, bl, rows, grad, loss, sizes):
-        ops.linear_nll_grad_rows(theta, data, labels, bi, bl, rows, grad, loss, *sizes)
+    @staticmethod
+    def sliced(b_max, sizes, large):
+        """Under --device-training-large-batch (`large`) a call goes to the sliced op exactly when
+        the existing kernel does not take its shape."""
+        return bool(large) and b_max * sizes[1] > MAX_BC
+
+    def grad_rows(self, theta, data, labels, bi, bl, rows, grad, loss, sizes, large=False):
+        op = ops.linear_nll_grad_rows_sliced if self.sliced(bi.shape[1], sizes, large) else \
+            ops.linear_nll_grad_rows
+        op(theta, data, labels, bi, bl, rows, grad, loss, *sizes)
 
     def eval_rows(self, theta, data, labels, rows, start, length, max_len, loss_sum, correct, sizes):
         ops.linear_eval_rows(theta, data, labels, rows, start, length, max_len, loss_sum, correct,
                              None, *sizes)
 
-    def grad_scratch_bytes(self, rows, b_max, sizes):
+    def grad_scratch_bytes(self, rows, b_max, sizes, large=False):
+        if self.sliced(b_max, sizes, large):
+            return 4 * int(lib.niidmix_linear_nll_grad_rows_sliced_scratch_elems(rows, b_max, *sizes))
         return 4 * int(lib.niidmix_linear_nll_grad_rows_scratch_elems(rows, b_max, sizes[1]))  # fp32 elements
 
     def eval_scratch_bytes(self, jobs, max_len, sizes):
@@ -226,7 +242,7 @@ class _GNLeNet:
     def P(self, shape):
         return gn_lenet_offsets(*shape)[-1]
 
-    def limits(self, shape, flag, batch=None):
+    def limits(self, shape, flag, batch=None, large=False):
         """ValueError naming `flag` when the kernels do not hold C classes or Cin channels."""
         cin, c, _ = shape
         if c > MAX_C:
@@ -253,14 +269,14 @@ class _GNLeNet:
                              f"features, the model's classifier takes F = {f}")
         return cin, h, w, c
 
-    def grad_rows(self, theta, data, labels, bi, bl, rows, grad, loss, sizes):
+    def grad_rows(self, theta, data, labels, bi, bl, rows, grad, loss, sizes, large=False):
         ops.gnlenet_nll_grad_rows(theta, data, labels, bi, bl, rows, grad, loss, *sizes)
 
     def eval_rows(self, theta, data, labels, rows, start, length, max_len, loss_sum, correct, sizes):
         ops.gnlenet_eval_rows(theta, data, labels, rows, start, length, max_len, loss_sum, correct,
                               None, None, *sizes)
 
-    def grad_scratch_bytes(self, rows, b_max, sizes):
+    def grad_scratch_bytes(self, rows, b_max, sizes, large=False):
         return int(lib.niidmix_gnlenet_nll_grad_rows_scratch_bytes(rows, b_max, *sizes))
 
     def eval_scratch_bytes(self, jobs, max_len, sizes):

@@ -31,6 +31,9 @@ Ops (registered in the `niidmix` namespace, usable as torch.ops.niidmix.*):
   linear_nll_grad_rows(theta, data, labels, batch_idx, batch_len, rows, grad, loss, K, C)
                                                     k_lin_logits + k_lin_softmax + k_lin_dw (local
                                                     training of a linear model, --device-training)
+  linear_nll_grad_rows_sliced(the same arguments)   k_lin_logits + k_lin_softmax_sl + k_lin_dw_sl +
+                                                    k_lin_reduce_sl (the same at any batch size,
+                                                    --device-training-large-batch)
   linear_eval_rows(theta, data, labels, rows, seg_start, seg_len, max_len, loss_sum, correct, pred,
                    K, C)                            k_lin_eval + k_lin_eval_sum (summed loss, correct
                                                     count and predictions of a linear model per
@@ -664,6 +667,7 @@ def _hits(a, b):
 # niidmix.family's refusals read them too.
 MAX_C = 1024
 MAX_BC = 32768
+MAX_B_SLICED = 2 ** 20      # batch of niidmix::linear_nll_grad_rows_sliced, which has no MAX_BC
 GN_MAX_CIN, GN_MIN_HW, GN_MAX_HW = 4, 15, 64
 GN_CHANNELS = (32, 32, 64)          # output channels of GN-LeNet's three convolutions
 
@@ -783,6 +787,39 @@ def linear_nll_grad_rows(theta: torch.Tensor, data: torch.Tensor, labels: torch.
         batch_len.data_ptr(), b_max, rows.data_ptr(), n, grad.data_ptr(), _ld(grad), loss.data_ptr(),
         K, C, scratch.data_ptr(), elems, _stream(theta))
     _lib.check(rc, "niidmix::linear_nll_grad_rows")
+
+
+def linear_sliced_slice(C):
+    """Samples per slice of niidmix::linear_nll_grad_rows_sliced for C classes (include/niidmix.h):
+    a function of C alone; 0 for a C the kernels do not hold."""
+    return int(_lib.lib.niidmix_linear_nll_grad_rows_sliced_slice(int(C)))
+
+
+@torch.library.custom_op("niidmix::linear_nll_grad_rows_sliced", mutates_args=("grad", "loss"))
+def linear_nll_grad_rows_sliced(theta: torch.Tensor, data: torch.Tensor, labels: torch.Tensor,
+                                batch_idx: torch.Tensor, batch_len: torch.Tensor, rows: torch.Tensor,
+                                grad: torch.Tensor, loss: torch.Tensor, K: int, C: int) -> None:
+    """linear_nll_grad_rows at any batch size up to MAX_B_SLICED (include/niidmix.h,
+    niidmix_linear_nll_grad_rows_sliced_f32): the same arguments, loss and gradient; the batch is
+    summed in slices of linear_sliced_slice(C) samples, then the slices in order.  The scratch
+    buffer comes from torch's caching allocator.  The index tensors' CONTENTS are not checked
+    here (niidmix.train.DeviceTrainer checks them once)."""
+    K, C = int(K), int(C)
+    _req(K >= 1 and C >= 1, "K and C must be >= 1")
+    n = _grad_rows_args(theta, data, labels, batch_idx, batch_len, rows, grad, loss,
+                        f"C * K + C = {C * K + C}", C * K + C, "K", K, apart=False)
+    if n == 0:
+        return
+    dev, b_max = theta.device, batch_idx.shape[1]
+    _req(C <= MAX_C and b_max <= MAX_B_SLICED,
+         f"unsupported shape: the kernel holds C <= {MAX_C} and b_max <= {MAX_B_SLICED}")
+    elems = int(_lib.lib.niidmix_linear_nll_grad_rows_sliced_scratch_elems(n, b_max, K, C))
+    scratch = torch.empty(elems, dtype=torch.float32, device=dev)
+    rc = _lib.lib.niidmix_linear_nll_grad_rows_sliced_f32(
+        theta.data_ptr(), _ld(theta), data.data_ptr(), labels.data_ptr(), batch_idx.data_ptr(),
+        batch_len.data_ptr(), b_max, rows.data_ptr(), n, grad.data_ptr(), _ld(grad), loss.data_ptr(),
+        K, C, scratch.data_ptr(), elems, _stream(theta))
+    _lib.check(rc, "niidmix::linear_nll_grad_rows_sliced")
 
 
 @torch.library.custom_op("niidmix::linear_eval_rows", mutates_args=("loss_sum", "correct", "pred"))

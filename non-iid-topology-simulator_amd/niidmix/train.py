@@ -84,6 +84,15 @@ call without scratch, longer rows in calls cut by cut_rows to the scratch budget
 niidmix::take_batches slices the cache into the index block (_draw_device).  Their lists travel in
 the same one H2D copy.  Train-sets up to ops.epoch_perm_max_len() are accepted; for shorter ones
 the batches are those of plain --device-sampling, bit for bit.
+
+The linear kernel keeps one row's dz in LDS, so batch-size * C is bounded by ops.MAX_BC.
+`--device-training-large-batch` (with --device-training or --device-training-sample, linear models
+only) lifts that to ops.MAX_B_SLICED samples: a gradient call whose b_max * C exceeds MAX_BC goes
+to niidmix::linear_nll_grad_rows_sliced, which cuts the batch into slices (family.LINEAR.sliced);
+every other call keeps the existing op, so a flagged run at an ordinary batch size is the unflagged
+run bit for bit.  Under --device-sampling-cached the batch may then be as long as
+niidmix::take_batches slices (ops.epoch_perm_max_len()); plain --device-sampling keeps its 8192.
+One node (the centralised baseline) is a graph round like any other: the Mixer takes n = 1.
 """
 import os
 
@@ -100,6 +109,7 @@ FLAG_GN = "--device-training-gn-lenet"
 FLAG_SAMPLE = "--device-training-sample"
 FLAG_SAMPLING = "--device-sampling"
 FLAG_CACHED = "--device-sampling-cached"
+FLAG_LARGE = "--device-training-large-batch"
 SCRATCH_FRACTION = 0.4   # of the free HBM, for one GN-LeNet gradient call's scratch
 # When a sample round takes the one-launch step + average + broadcast
 # (niidmix::sample_step_mean_update) instead of the three ops it restates: slabs of at least
@@ -135,6 +145,11 @@ def sampling_enabled(params):
 def cached_enabled(params):
     """--device-sampling-cached: every epoch's permutation is sorted once and kept in HBM."""
     return bool(params.get("algorithm", {}).get("device-sampling-cached"))
+
+
+def large_enabled(params):
+    """--device-training-large-batch: linear batches beyond ops.MAX_BC train on the sliced kernels."""
+    return bool(params.get("algorithm", {}).get("device-training-large-batch"))
 
 
 def flag_of(params):
@@ -225,6 +240,9 @@ def check_sampling(nodes, params):
     size stays bounded by the index block's kernel."""
     most = ops.draw_batches_max_len()
     longest = ops.epoch_perm_max_len() if cached_enabled(params) else most
+    large = large_enabled(params)
+    if large and cached_enabled(params):         # niidmix::take_batches slices batches that long
+        most = longest
     seed = params.get("meta", {}).get("seed")
     if not isinstance(seed, int) or isinstance(seed, bool):
         raise ValueError(f"{FLAG_SAMPLING} keys its sample stream by params['meta']['seed'], an "
@@ -232,7 +250,9 @@ def check_sampling(nodes, params):
     b = int(params["algorithm"]["batch-size"])
     if not 1 <= b <= most:
         raise ValueError(f"{FLAG_SAMPLING}: batch size {b} is not in 1..{most}, the longest batch the "
-                         "kernel draws")
+                         "kernel draws" + (f" ({FLAG_CACHED} slices batches of up to "
+                                           f"{ops.epoch_perm_max_len()} samples under {FLAG_LARGE})"
+                                           if large and not cached_enabled(params) else ""))
     for nd in nodes:
         ts = nd.get("train-set")
         if ts is not None and len(ts) > longest:
@@ -263,6 +283,13 @@ def check_eligible(nodes, params, topology=None):
     gn_flag = gn_enabled(params)
     flag = flag_of(params)
     sample = sample_run(params)
+    large = large_enabled(params)
+    if large and not enabled(params):
+        raise ValueError(f"{FLAG_LARGE} lifts the batch limit of a linear model's device-training "
+                         f"round: it needs {FLAG} or {FLAG_SAMPLE}")
+    if large and gn_flag:
+        raise ValueError(f"{FLAG_LARGE} is for linear models: GN-LeNet's kernels ({FLAG_GN}) have no "
+                         "such batch limit")
     if params["topology"]["name"] == "sample" and not sample:
         raise ValueError(f"{flag} does not support the 'sample' topology: it trains on the device "
                          f"under {FLAG_SAMPLE}")
@@ -300,7 +327,7 @@ def check_eligible(nodes, params, topology=None):
         if gn and fam.shape(nd["model"]) != shape:
             raise ValueError(f"{flag} needs models whose parameters are exactly GN-LeNet's 14 "
                              f"tensors, the same on every node (node {nd['rank']} differs)")
-    fam.limits(shape, flag, int(alg["batch-size"]))
+    fam.limits(shape, FLAG_LARGE if large else flag, int(alg["batch-size"]), large)
     for nd in nodes:
         ts = nd.get("train-set")         # an empty set is DeviceTrainer's refusal, and so are a
         if gn and ts is not None and len(ts):                   # linear model's samples
@@ -333,6 +360,7 @@ class DeviceTrainer:
         self.sample = sample_run(params)     # fixed for the trainer's life (d_sgd._trainer)
         self.sampling = sampling_enabled(params)     # and so are these two
         self.cached = cached_enabled(params)
+        self.large = large_enabled(params)           # batches beyond ops.MAX_BC: the sliced op
         self.scratch_budget = None      # bytes of scratch per GN-LeNet gradient call (None:
         self.last_calls = 0              # SCRATCH_FRACTION of the free HBM); calls of the last round
         self.sizes = None                # the kernel's size arguments (family.sizes), set by _materialise
@@ -441,7 +469,7 @@ class DeviceTrainer:
                                f"{free / 2**30:.1f} GiB of free HBM")
 
     def _gn_need(self, rows):
-        return self.family.grad_scratch_bytes(rows, self.b_max, self.sizes)
+        return self.family.grad_scratch_bytes(rows, self.b_max, self.sizes, self.large)
 
     def _budget(self):
         """Bytes of scratch one call may take: scratch_budget when set, else SCRATCH_FRACTION of the
@@ -476,7 +504,7 @@ class DeviceTrainer:
         for a in range(0, n, cut):
             b = min(n, a + cut)
             self.family.grad_rows(x, self.data, self.labels, bi[a:b], bl[a:b], rows[a:b],
-                                  self.grad, self.loss[a:b], self.sizes)
+                                  self.grad, self.loss[a:b], self.sizes, self.large)
             self.last_calls += 1
 
     def _step(self, x):

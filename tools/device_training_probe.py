@@ -44,6 +44,18 @@ Gradient averaging (--clique-gradient under --device-training):
     python tools/device_training_probe.py fused-step --shape e2e [--warmup 5] [--reps 20]
     python tools/device_training_probe.py gn-rounds --shape gn-cifar --clique-gradient --momentum 0.9
 
+Long batches (niidmix_linear_nll_grad_rows_sliced_f32, --device-training-large-batch):
+  large-batch  the sliced call at (rows, B) = (1, 12 800), (10, 6000), (100, 3277) with K 784, C 10,
+               against the bytes it must move as a share of 8 TB/s, its four kernels apart at the
+               first shape (torch's profiler); the sliced and the existing entry alternating at
+               (1, 3276) and (1000, 3276), the largest batch both take; and the centralised round:
+               d_sgd.next_step at one node, 60 000 x 784 synthetic samples, batch 12 800, under the
+               flag with --device-sampling --device-sampling-cached against the same round with
+               every device flag off, alternating round by round.  Device events for the calls, the
+               host clock around next_step + synchronize for the rounds.
+
+    python tools/device_training_probe.py large-batch [--warmup 5] [--reps 20]
+
 `all` runs the four steps one after the other, each in a fresh process under its own time limit,
 and stops at the first that fails.  Every step prints one JSON line.
 """
@@ -51,6 +63,7 @@ import argparse
 import ctypes
 import json
 import os
+import re
 import statistics
 import subprocess
 import sys
@@ -382,6 +395,170 @@ def rounds(a):
     print(json.dumps(out))
 
 
+LARGE_SHAPES = ((1, 12800, 784, 10), (10, 6000, 784, 10), (100, 3277, 784, 10))
+BOTH_SHAPES = ((1, 3276, 784, 10), (1000, 3276, 784, 10))
+
+
+def _stats(t, nbytes=None):
+    med = statistics.median(t)
+    out = {"median_ms": med * 1e3, "min_ms": min(t) * 1e3, "max_ms": max(t) * 1e3}
+    if nbytes is not None:
+        out.update(bytes=nbytes, share_of_8TBps=nbytes / med / 8e12)
+    return out
+
+
+def _linear_calls(n, b, k, c, dev, pool=60000):
+    """The two gradient entries on n rows with full batches of b samples drawn from a pool:
+    ({name: call}, bytes the sliced call must move, loss)."""
+    import torch
+    from niidmix import _lib, train
+    lib = _lib.lib
+    p = c * k + c
+    ld = train.padded_ld(p)
+    gen = torch.Generator(device=dev).manual_seed(1)
+    theta = (torch.rand(n, ld, device=dev, generator=gen) - 0.5) * (2 / k ** 0.5)
+    grad = torch.zeros(n, ld, device=dev)
+    data = torch.rand(pool, k, device=dev, generator=gen)
+    labels = torch.randint(0, c, (pool,), device=dev, generator=gen).to(torch.int32)
+    idx = torch.randint(0, pool, (n, b), device=dev, generator=gen).to(torch.int32).contiguous()
+    blen = torch.full((n,), b, dtype=torch.int32, device=dev)
+    rows = torch.arange(n, dtype=torch.int32, device=dev)
+    loss = torch.empty(n, device=dev)
+    strm = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    calls = {}
+    for name, fn, elems in (
+            ("sliced", lib.niidmix_linear_nll_grad_rows_sliced_f32,
+             int(lib.niidmix_linear_nll_grad_rows_sliced_scratch_elems(n, b, k, c))),
+            ("existing", lib.niidmix_linear_nll_grad_rows_f32,
+             int(lib.niidmix_linear_nll_grad_rows_scratch_elems(n, b, c)) if b * c <= 32768 else None)):
+        if elems is None:
+            continue
+        scratch = torch.empty(elems, device=dev)
+        calls[name] = lambda fn=fn, scratch=scratch, elems=elems: fn(
+            theta.data_ptr(), ld, data.data_ptr(), labels.data_ptr(), idx.data_ptr(), blen.data_ptr(), b,
+            rows.data_ptr(), n, grad.data_ptr(), ld, loss.data_ptr(), k, c, scratch.data_ptr(), elems, strm)
+    n_sl = -(-b // int(lib.niidmix_linear_nll_grad_rows_sliced_slice(c)))
+    n_kc = min(8, -(-1024 // n), -(-k // 256))
+    # the gather of x twice, the partial logits written and read and dz written and read, the partial
+    # gradients written and read, theta read and grad written
+    nbytes = 4 * (2 * n * b * k + 2 * (n_kc + 1) * n * b * c + 2 * n * n_sl * p + 2 * n * p)
+    return calls, nbytes, loss
+
+
+def _alternate(calls, a):
+    """Device-event times of single calls, alternating within every repetition."""
+    import torch
+    from niidmix import _lib
+    times = {name: [] for name in calls}
+    for rep in range(a.warmup + a.reps):
+        for name, fn in calls.items():
+            s0, e0 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s0.record()
+            _lib.check(fn(), name)
+            e0.record()
+            e0.synchronize()
+            if rep >= a.warmup:
+                times[name].append(s0.elapsed_time(e0) * 1e-3)
+    return times
+
+
+def _passes(call, a):
+    """Device time of each kernel of one call, by torch's profiler: {kernel: stats} or a reason."""
+    import torch
+    from torch.profiler import ProfilerActivity, profile
+    try:
+        per = {}
+        for _ in range(a.reps):
+            with profile(activities=[ProfilerActivity.CUDA]) as prof:
+                call()
+                torch.cuda.synchronize()
+            for ev in prof.events():
+                m = re.search(r"k_lin_\w+", ev.name)
+                if m and ev.device_time_total > 0:
+                    per.setdefault(m.group(0), []).append(ev.device_time_total * 1e-6)
+        return {k: _stats(v) for k, v in per.items()} or "the profiler recorded no k_lin_ kernel"
+    except Exception as e:                     # a measurement aid: the totals above stand without it
+        return f"{type(e).__name__}: {e}"
+
+
+def large_batch(a):
+    """--device-training-large-batch: the sliced call at few rows and long batches (the four passes
+    apart at the first shape), the sliced against the existing entry at the largest batch both
+    take, and the centralised round (one node, 60 000 x 784 synthetic samples, batch 12 800) under
+    the flag with --device-sampling-cached against the same round with every device flag off."""
+    import torch
+    import torch.nn.functional as F
+    from niidmix import _lib, d_sgd
+    dev = torch.device("cuda:0")
+    out = {"step": "large-batch", "warmup": a.warmup, "reps": a.reps, "threads": torch.get_num_threads(),
+           "device": torch.cuda.get_device_name(dev), "lib_sha16": _lib.lib_sha16(), "sliced": [], "both": []}
+    for i, (n, b, k, c) in enumerate(LARGE_SHAPES):
+        calls, nbytes, loss = _linear_calls(n, b, k, c, dev)
+        t = _alternate({"sliced": calls["sliced"]}, a)
+        assert bool(torch.isfinite(loss).all())
+        rec = {"shape": [n, b, k, c], **_stats(t["sliced"], nbytes)}
+        if i == 0:
+            rec["passes"] = _passes(calls["sliced"], a)
+        out["sliced"].append(rec)
+    for n, b, k, c in BOTH_SHAPES:
+        calls, nbytes, loss = _linear_calls(n, b, k, c, dev)
+        t = _alternate(calls, a)
+        assert bool(torch.isfinite(loss).all())
+        rec = {"shape": [n, b, k, c], **{name: _stats(v) for name, v in t.items()}}
+        rec["sliced_over_existing"] = rec["sliced"]["median_ms"] / rec["existing"]["median_ms"]
+        out["both"].append(rec)
+
+    k, c, b, size = 784, 10, 12800, 60000
+
+    class Net(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.fc = torch.nn.Linear(k, c)
+
+        def forward(self, x, params):
+            return F.log_softmax(self.fc(x.view(-1, k)), dim=1)
+
+    g = torch.Generator().manual_seed(5)
+    x = torch.rand(size, k, generator=g)
+    y = torch.randint(0, c, (size,), generator=g)
+    ts = [(x[j], int(y[j])) for j in range(size)]
+    topo = {"edges": {0: []}, "weights": torch.tensor([[1.0]])}
+    flags = {"device-training": True, "device-training-large-batch": True, "device-sampling": True,
+             "device-sampling-cached": True}
+    runs = {}
+    for name, extra in (("flags_off", {}), ("flagged", flags)):
+        torch.manual_seed(7)
+        params = {"meta": {"log": "WARNING", "seed": 7}, "model": {"input-size": k},
+                  "topology": {"name": "fully-connected", "remove-clique-edges": 0},
+                  "logger": {"accuracy-logging-interval": 0, "accuracy-logging-interval-steps": 0,
+                             "log-consensus-distance": False},
+                  "algorithm": {"learning-rate": 0.01, "learning-momentum": 0.0, "batch-size": b,
+                                "initial-averaging": False, "clique-gradient": False,
+                                "unbiased-gradient": False, "deferred-writeback": True,
+                                "mixing-mode": a.mode, **extra}}
+        mdl = Net()
+        nodes = [{"rank": 0, "epoch": 0, "train-set": ts, "model": mdl,
+                  "optimizer": d_sgd.optimizer(mdl, params)}]
+        state, _, _ = d_sgd.init(nodes, topo, params)
+        runs[name] = [state, params, []]
+    for rnd in range(a.warmup + a.reps):
+        for name in runs:
+            state, params, times = runs[name]
+            t0 = time.perf_counter()
+            state, _, _, _ = d_sgd.next_step(state, params, None)
+            d_sgd.synchronize()
+            torch.cuda.synchronize(dev)
+            dt = time.perf_counter() - t0
+            runs[name][0] = state
+            if rnd >= a.warmup:
+                times.append(dt)
+    out["centralised_round"] = {"samples": size, "k": k, "c": c, "batch": b,
+                                **{name: _stats(r[2]) for name, r in runs.items()}}
+    out["centralised_round"]["flagged_over_off"] = \
+        out["centralised_round"]["flagged"]["median_ms"] / out["centralised_round"]["flags_off"]["median_ms"]
+    print(json.dumps(out))
+
+
 def run_all(a):
     for step in ("kernel", "rounds"):
         for shape in SHAPES:
@@ -394,7 +571,8 @@ def run_all(a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("step", choices=["kernel", "rounds", "gn-kernel", "gn-rounds", "fused-step", "all"])
+    ap.add_argument("step", choices=["kernel", "rounds", "gn-kernel", "gn-rounds", "fused-step", "large-batch",
+                                     "all"])
     ap.add_argument("--shape", choices=list(SHAPES) + list(GN_SHAPES), default=None)
     ap.add_argument("--loop-nodes-device", type=int, default=8,
                     help="gn-kernel: nodes the device autograd loop runs per repetition (scaled to N)")
@@ -417,6 +595,8 @@ def main():
     gn = a.step.startswith("gn-")
     if a.warmup is None:
         a.warmup = 2 if a.step.endswith("rounds") else 5
+    if a.step == "large-batch":
+        return large_batch(a)
     if a.step == "fused-step":
         a.shape = a.shape or "e2e"
         if a.shape not in ("e2e", "gn-cifar"):
