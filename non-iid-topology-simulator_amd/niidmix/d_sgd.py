@@ -773,18 +773,14 @@ def _device_training_step(state, params, rundir):
     nodes = state["nodes"]
     synchronize()
     tr = _trainer(nodes, state["topology"], params)
-    if tr.sample != train.sample_run(params):
-        raise ValueError(f"{train.FLAG_SAMPLE}: the run changed between a sample round and a graph "
-                         "round under a live device trainer: not supported")
-    if tr.sampling != train.sampling_enabled(params):
-        raise ValueError(f"{train.FLAG_SAMPLING} was switched during the run, under a live device "
-                         "trainer: not supported")
-    if tr.cached != train.cached_enabled(params):
-        raise ValueError(f"{train.FLAG_CACHED} was switched during the run, under a live device "
-                         "trainer: not supported")
-    if tr.large != train.large_enabled(params):
-        raise ValueError(f"{train.FLAG_LARGE} was switched during the run, under a live device "
-                         "trainer: not supported")
+    switched = " was switched during the run, under a live device trainer: not supported"
+    for attr, now, msg in (("sample", train.sample_run, f"{train.FLAG_SAMPLE}: the run changed between a "
+                            "sample round and a graph round under a live device trainer: not supported"),
+                           ("sampling", train.sampling_enabled, train.FLAG_SAMPLING + switched),
+                           ("cached", train.cached_enabled, train.FLAG_CACHED + switched),
+                           ("large", train.large_enabled, train.FLAG_LARGE + switched)):
+        if getattr(tr, attr) != now(params):     # each is fixed for the trainer's life
+            raise ValueError(msg)
     if tr.sample:
         # --device-training-sample (d_sgd.py:236-250): only the sample trains and steps, its
         # average replaces every model (niidmix.train.DeviceTrainer.sample_round)

@@ -70,8 +70,8 @@ the three flags above) gives that stream up for one of the project's own, define
 (niidmix.sampling) and drawn where it is consumed: the host keeps (epoch, cursor) of every row
 (sampling.SamplerState: epoch_done and the batch lengths need no copy back), sends them in one
 small H2D copy, and niidmix::draw_batches writes the indices and lengths straight into the block
-the gradient op reads (_draw_device, in place of draw and _fill_batches).  No DataLoader is built,
-node['train-iterator'] stays None and the global torch RNG is not consumed by sampling; such a run
+the gradient op reads (batches.DeviceSource, in place of draw and the packing).  No DataLoader is
+built, node['train-iterator'] stays None and the global torch RNG is not consumed by sampling; such a run
 is sample-for-sample comparable only with other --device-sampling runs of the same seed.
 
 niidmix::draw_batches is stateless -- one workgroup sorts a node's whole epoch on every call -- and
@@ -81,8 +81,8 @@ of offsets[-1] entries, a node's permutation at its data offset; before a round'
 whose cache is not their current epoch's (SamplerState.stale: every row in round 0, afterwards the
 rows that crossed an epoch) are sorted by niidmix::epoch_perm -- rows of up to 8192 samples in one
 call without scratch, longer rows in calls cut by cut_rows to the scratch budget -- and
-niidmix::take_batches slices the cache into the index block (_draw_device).  Their lists travel in
-the same one H2D copy.  Train-sets up to ops.epoch_perm_max_len() are accepted; for shorter ones
+niidmix::take_batches slices the cache into the index block (batches.CachedSource).  Their lists
+travel in the same one H2D copy.  Train-sets up to ops.epoch_perm_max_len() are accepted; for shorter ones
 the batches are those of plain --device-sampling, bit for bit.
 
 The linear kernel keeps one row's dz in LDS, so batch-size * C is bounded by ops.MAX_BC.
@@ -93,12 +93,17 @@ every other call keeps the existing op, so a flagged run at an ordinary batch si
 run bit for bit.  Under --device-sampling-cached the batch may then be as long as
 niidmix::take_batches slices (ops.epoch_perm_max_len()); plain --device-sampling keeps its 8192.
 One node (the centralised baseline) is a graph round like any other: the Mixer takes n = 1.
+
+Whatever the mode, a round's indices go up in one H2D copy of one pinned int32 block.  Its lists
+and the words a round copies are niidmix.batches.IndexLayout's; what fills it is one of three batch
+sources, chosen once per trainer (LoaderSource: draw() and the packing; DeviceSource; CachedSource),
+so the two round methods do not know the sampling mode.
 """
 import os
 
 import torch
 
-from . import family, ops
+from . import batches, family, ops
 # defined in niidmix.family; the training suites (tests/test_gpu_train*.py) call them as train.<name>
 from .family import (fp64_reference, fp64_reference_gn_lenet, gn_lenet_offsets,  # noqa: F401
                      reference_gn_lenet, split_gn_lenet)
@@ -351,6 +356,8 @@ class DeviceTrainer:
     """Data, parameters, gradients (and momentum) of one node list in HBM, and the round above."""
 
     kind = property(lambda self: self.family.kind)       # "linear" / "gn-lenet", read-only
+    last_perm_jobs = property(lambda self: self.source.last_perm_jobs)       # batches.CachedSource's, of
+    last_perm_calls = property(lambda self: self.source.last_perm_calls)     # the last round (tests)
 
     def __init__(self, nodes, topology, params, device):
         from . import d_sgd
@@ -398,22 +405,12 @@ class DeviceTrainer:
         self.mom_steps = 0
         self.rows = torch.arange(self.n, dtype=torch.int32, device=dev)
         self.loss = torch.empty(self.n, dtype=torch.float32, device=dev)
-        # one round's indices, one H2D copy: [n, b_max] sample indices, [n] batch lengths and, for
-        # a sample round (sample_layout), the active rows, their `first` flags and the step lists
-        # and, under --device-sampling (_init_sampler), the five per-job lists of
-        # niidmix::draw_batches, with the cached mode's lists around them
-        words = self.n * self.b_max + (4 if self.sample else 1) * self.n
-        if self.cached:
-            words += words & 1                       # the two int64 lists start on 8 bytes
-            self.off0, words = words, words + 4 * self.n
-        self.job0 = words
-        if self.sampling:
-            words += (8 if self.cached else 5) * self.n
-        self.idx_host = torch.zeros(words, dtype=torch.int32).pin_memory()
+        # one round's indices, one H2D copy: batches.IndexLayout's lists, filled by the mode's source
+        self.layout = batches.IndexLayout(self.n, self.b_max, self.sample, self.sampling, self.cached)
+        self.idx_host = torch.zeros(self.layout.words, dtype=torch.int32).pin_memory()
         self.idx_dev = torch.empty_like(self.idx_host, device=dev)
-        self.sampler = None
-        if self.sampling:
-            self._init_sampler(nodes, params)
+        self.dev = {name: self.layout.view(self.idx_dev, name) for name in self.layout.spans}
+        self.source = batches.source_class(self.sample, self.sampling, self.cached)(self, nodes)
         self.stepped_rows = set()     # sample rounds: rows that have taken an optimizer step
         self.last_first = []          # the `first` flags of the last sample round (tests)
         self._avg = None              # sample rounds, three-op sequence: the CSR row and the average
@@ -493,12 +490,13 @@ class DeviceTrainer:
                                f"{budget / 2**30:.2f} GiB")
         return k
 
-    def _gradient(self, x, bi, bl, rows=None):
-        """Gradient and loss of the rows `rows` of x (default: every row) on this round's batches,
-        one job per row in the list's order: job j's gradient goes to row rows[j] of self.grad, its
-        loss to self.loss[j]."""
+    def _gradient(self, x, rows=None):
+        """Gradient and loss of the rows `rows` of x (default: every row) on this round's batches
+        (the index block's, where the batch source put them), one job per row in the list's order:
+        job j's gradient goes to row rows[j] of self.grad, its loss to self.loss[j]."""
         rows = self.rows if rows is None else rows
         n = rows.numel()
+        bi, bl = self.dev["indices"], self.dev["lengths"]
         cut = self._cut(n)
         self.last_calls = 0
         for a in range(0, n, cut):
@@ -603,148 +601,22 @@ class DeviceTrainer:
     def write_back(self):
         self._host().copy_(self.theta[self.cur])     # D2H, synchronous: the models are current
 
-    def _fill_batches(self, nodes, rows, batches):
-        """The batches of the nodes at slab rows `rows` into the pinned index block, job j = the
-        j-th of them: sample indices offset by the node's own data offset, and the lengths."""
-        nb = self.n * self.b_max
-        bi = self.idx_host[:nb].view(self.n, self.b_max).numpy()
-        bl = self.idx_host[nb:nb + self.n].numpy()
-        for j, (i, idx) in enumerate(zip(rows, batches)):
-            k = idx.numel()
-            if k < 1 or k > self.b_max or int(idx.max()) >= self.offsets[i + 1] - self.offsets[i]:
-                raise ValueError(f"{self.flag}: node {nodes[j]['rank']} drew a batch its train-set or "
-                                 "the batch size does not allow")
-            bi[j, :k] = idx.numpy() + self.offsets[i]
-            bl[j] = k
+    def _current_params(self):
+        """Makes the device parameters the models' current values (an upload when they are not).
+        Returns the slab that holds them and the one the round writes."""
+        self._host()
+        if not self.fresh or self.version != self.slab.version():
+            self.upload()
+        return self.theta[self.cur], self.theta[1 - self.cur]
 
-    def _init_sampler(self, nodes, params):
-        """--device-sampling: the host's (epoch, cursor) of every row (niidmix.sampling.SamplerState)
-        and, behind everything else in the index block, the job lists of niidmix::draw_batches --
-        five rows of n int32: rank, seg_start and seg_len (a graph round's job j is row j, so these
-        go up here, once), then epoch and cursor (every round).  --device-sampling-cached adds, in
-        front of them, two int64 lists of n -- the jobs' perm_off (a graph round's is the data
-        offset of row j: up here, once) and the perm_off of the rows to sort -- and behind them
-        rank, seg_len and epoch of the rows to sort; and the cache itself."""
-        import numpy as np
-        from .sampling import SamplerState
-        self.seed = int(params["meta"]["seed"]) & 0xFFFFFFFF
-        off = np.asarray(self.offsets, dtype=np.int64)
-        self.seg_start = off[:-1]
-        self.sampler = SamplerState([nd["rank"] for nd in nodes], off[1:] - off[:-1], self.b_max,
-                                    epochs=[nd.get("epoch", 0) for nd in nodes])
-        self.all_rows = np.arange(self.n)
-        job = self._jobs(self.idx_host).numpy()
-        job[0], job[1], job[2] = self.sampler.rank, self.seg_start, self.sampler.length
-        if self.cached:
-            self._offs(self.idx_host).numpy()[0] = self.seg_start
-            self.perm = torch.empty(self.offsets[-1], dtype=torch.int32, device=self.device)
-            self.no_scratch = torch.empty(0, dtype=torch.int64, device=self.device)
-            self.short_max = ops.draw_batches_max_len()
-            self.last_perm_jobs = self.last_perm_calls = 0      # of the last round (tests)
-        self.idx_dev.copy_(self.idx_host)
-
-    def _jobs(self, block):
-        """The five per-job lists of niidmix::draw_batches in the index block `block` (host or
-        device): [5, n] int32."""
-        return block[self.job0:self.job0 + 5 * self.n].view(5, self.n)
-
-    def _offs(self, block):
-        """--device-sampling-cached: [2, n] int64 -- perm_off of the round's jobs, of the rows to sort."""
-        return block[self.off0:self.job0].view(torch.int64).view(2, self.n)
-
-    def _sort_lists(self, block):
-        """--device-sampling-cached: [3, n] int32 -- rank, seg_len and epoch of the rows to sort."""
-        return block[self.job0 + 5 * self.n:].view(3, self.n)
-
-    def _stale_lists(self, sel):
-        """--device-sampling-cached, before the draw advances the rows `sel`: those whose cached
-        permutation is not their current epoch's go into the sort lists of the pinned block, rows
-        of up to short_max samples first, and are marked cached.  Returns (rows to sort, how many
-        of them are short)."""
-        import numpy as np
-        st = self.sampler
-        stale = st.stale(sel)
-        if stale.size == 0:
-            return stale, 0
-        short = st.length[stale] <= self.short_max
-        stale = np.concatenate([stale[short], stale[~short]])
-        m = stale.size
-        lists = self._sort_lists(self.idx_host).numpy()
-        lists[0, :m], lists[1, :m], lists[2, :m] = st.rank[stale], st.length[stale], st.epoch[stale]
-        self._offs(self.idx_host).numpy()[1, :m] = self.seg_start[stale]
-        st.mark_cached(stale)
-        return stale, int(short.sum())
-
-    def _sort_stale(self, stale, n_short):
-        """niidmix::epoch_perm over the rows `stale` (_stale_lists; their lists are on the device):
-        the short ones in one call without scratch, the long ones in calls of as many rows as keep
-        the scratch within the budget (cut_rows)."""
-        m, length = len(stale), self.sampler.length
-        self.last_perm_jobs, self.last_perm_calls = m, 0
-        if m == 0:
-            return
-        lists, off = self._sort_lists(self.idx_dev), self._offs(self.idx_dev)[1]
-
-        def call(a, b, scratch):
-            ops.epoch_perm(self.seed, lists[0, a:b], lists[1, a:b], lists[2, a:b], off[a:b],
-                           int(length[stale[a:b]].max()), self.perm, scratch)
-            self.last_perm_calls += 1
-        if n_short:
-            call(0, n_short, self.no_scratch)
-        if m > n_short:
-            longest = int(length[stale[n_short:]].max())
-            budget = self._budget()
-            cut = cut_rows(m - n_short, lambda k: ops.epoch_perm_scratch_bytes(k, longest), budget)
-            if cut is None:
-                raise RuntimeError(f"{FLAG_CACHED}: {ops.epoch_perm_scratch_bytes(1, longest) / 2**30:.2f} "
-                                   f"GiB of scratch to sort one row of {longest} samples exceed the "
-                                   f"budget of {budget / 2**30:.2f} GiB")
-            for a in range(n_short, m, cut):
-                b = min(m, a + cut)
-                nbytes = ops.epoch_perm_scratch_bytes(b - a, int(length[stale[a:b]].max()))
-                call(a, b, torch.empty(nbytes // 8, dtype=torch.int64, device=self.device))
-
-    def _draw_device(self, active, rows=None):
-        """One round's batches under --device-sampling, in place of draw() and _fill_batches(): the
-        rows' (epoch, cursor) from the host state, one H2D copy of them (and, for a sample round, of
-        its other lists, which lie in front of them) and niidmix::draw_batches, which writes job
-        j's indices and length where the gradient op reads them (--device-sampling-cached: the rows
-        that begin an epoch are sorted into the cache first, niidmix::take_batches then slices it;
-        their lists go up in the same copy).  `rows`: the slab rows of a sample
-        round's active nodes, in the sample's order (only they advance; their rank, seg_start and
-        seg_len go up too); None: every row.  Returns {rank: epoch_done}; node['epoch'] counts as
-        it does in draw()."""
-        n, nb, st = self.n, self.n * self.b_max, self.sampler
-        k = n if rows is None else len(rows)
-        if self.cached:
-            stale, n_short = self._stale_lists(self.all_rows if rows is None else rows)
-        epoch, cursor, done = st.advance(self.all_rows if rows is None else rows)
-        if int(epoch.max()) >= 2 ** 31 - 1:
-            raise ValueError(f"{FLAG_SAMPLING}: an epoch count outside int32")
-        job = self._jobs(self.idx_host).numpy()
-        if rows is not None:
-            job[0, :k], job[1, :k], job[2, :k] = st.rank[rows], self.seg_start[rows], st.length[rows]
-            if self.cached:
-                self._offs(self.idx_host).numpy()[0, :k] = self.seg_start[rows]
-        job[3, :k], job[4, :k] = epoch, cursor
-        for nd in active:
-            if done[nd["rank"]]:
-                nd["epoch"] += 1
-        # one H2D copy: a graph round's epochs and cursors (with the sort lists around them when a
-        # row begins an epoch), a sample round's whole tail
-        first = nb + n if rows is not None else self.job0 + 3 * n
-        last = self.job0 + 5 * n
-        if self.cached and len(stale):
-            first, last = first if rows is not None else self.off0 + 2 * n, self.idx_host.numel()
-        self.idx_dev[first:last].copy_(self.idx_host[first:last], non_blocking=True)
-        jd = self._jobs(self.idx_dev)[:, :k]
-        bi, bl = self.idx_dev[:nb].view(n, self.b_max)[:k], self.idx_dev[nb:nb + k]
-        if self.cached:
-            self._sort_stale(stale, n_short)
-            ops.take_batches(self.perm, self._offs(self.idx_dev)[0, :k], jd[1], jd[2], jd[4], bi, bl)
-        else:
-            ops.draw_batches(self.seed, jd[0], jd[1], jd[2], jd[3], jd[4], bi, bl)
-        return done
+    def _finish(self, nodes, k):
+        """The end of a round, whose result is in the other slab: the losses of its k jobs D2H, the
+        parameters back into the models (synchronous).  Returns {rank: loss} of `nodes`, the jobs'
+        nodes in order."""
+        self.cur = 1 - self.cur
+        loss = self.loss[:k].cpu().tolist()
+        self.write_back()
+        return {nd["rank"]: float(v) for nd, v in zip(nodes, loss)}
 
     def _sample_sequence(self, x, y, active, lists, n_first):
         """Step, average and broadcast of a sample round as the three ops in sequence (x is
@@ -778,29 +650,14 @@ class DeviceTrainer:
         k = len(rows)
         if k < 1 or len(set(rows)) != k:
             raise ValueError(f"{self.flag}: a sample of {k} nodes with {len(set(rows))} distinct ones")
-        if not self.sampling:
-            batches, epoch_done = draw(active, params)
-        self._host()
-        if not self.fresh or self.version != self.slab.version():
-            self.upload()
-        if not self.sampling:
-            self._fill_batches(active, rows, batches)
-        first = first_flags(self.stepped_rows, rows)
-        self.last_first = first
-        nb, n = self.n * self.b_max, self.n
-        tail = self.idx_host[nb + n:nb + 4 * n].view(3, n)
-        tail[0, :k] = torch.tensor(rows, dtype=torch.int32)
-        tail[1, :k] = torch.tensor(first, dtype=torch.int32)
-        tail[2, :k] = torch.tensor([r for r, f in zip(rows, first) if f] +
-                                   [r for r, f in zip(rows, first) if not f], dtype=torch.int32)
-        if self.sampling:
-            epoch_done = self._draw_device(active, rows)                # the one H2D copy is there
-        else:
-            self.idx_dev.copy_(self.idx_host, non_blocking=True)       # one H2D copy
-        dev = self.idx_dev[nb + n:nb + 4 * n].view(3, n)
-        x, y = self.theta[self.cur], self.theta[1 - self.cur]
-        self._gradient(x, self.idx_dev[:nb].view(n, self.b_max)[:k], self.idx_dev[nb:nb + k], dev[0, :k])
-        self.sample_fused = self.ld >= SAMPLE_FUSED_MIN_COLS and k >= SAMPLE_FUSED_MIN_SHARE * n
+        first = self.last_first = first_flags(self.stepped_rows, rows)
+        order = [r for r, f in zip(rows, first) if f] + [r for r, f in zip(rows, first) if not f]
+        self.layout.view(self.idx_host, "sample_tail")[:, :k] = torch.tensor([rows, first, order])
+        epoch_done = self.source.fill(active, rows, params)     # the one H2D copy, the tail in it
+        x, y = self._current_params()
+        dev = self.dev["sample_tail"]
+        self._gradient(x, dev[0, :k])
+        self.sample_fused = self.ld >= SAMPLE_FUSED_MIN_COLS and k >= SAMPLE_FUSED_MIN_SHARE * self.n
         if self.sample_fused:
             mom = self.momentum != 0.0
             ops.sample_step_mean_update(x, y, self.grad, self.mbuf, dev[0, :k], dev[1, :k] if mom else None,
@@ -809,10 +666,7 @@ class DeviceTrainer:
             self._sample_sequence(x, y, dev[0, :k], dev[2, :k], sum(first))
         if self.momentum != 0.0:
             self.mom_steps += 1
-        self.cur = 1 - self.cur
-        loss = self.loss[:k].cpu().tolist()
-        self.write_back()
-        return {nd["rank"]: float(v) for nd, v in zip(active, loss)}, epoch_done
+        return self._finish(active, k), epoch_done
 
     def round(self, nodes, topology, params, mode):
         """One round of every node; returns ({rank: loss}, {rank: epoch_done})."""
@@ -820,22 +674,9 @@ class DeviceTrainer:
             raise ValueError(f"{self.flag}: a sample run's rounds are sample_round's")
         if topology is not self.topology or id(topology.get("weights")) != self.weights_id:
             self.set_topology(topology)
-        if not self.sampling:
-            batches, epoch_done = draw(nodes, params)
-        self._host()
-        if not self.fresh or self.version != self.slab.version():
-            self.upload()
-        nb = self.n * self.b_max
-        if self.sampling:
-            epoch_done = self._draw_device(nodes)
-        else:
-            self._fill_batches(nodes, range(self.n), batches)
-            self.idx_dev.copy_(self.idx_host, non_blocking=True)       # one H2D copy
-        x, y = self.theta[self.cur], self.theta[1 - self.cur]
-        self._gradient(x, self.idx_dev[:nb].view(self.n, self.b_max), self.idx_dev[nb:nb + self.n])
+        epoch_done = self.source.fill(nodes, None, params)      # the one H2D copy
+        x, y = self._current_params()
+        self._gradient(x)
         self._step(x)
         self.mixer(x, out=y, mode=mode)
-        self.cur = 1 - self.cur
-        loss = self.loss.cpu().tolist()
-        self.write_back()
-        return {nd["rank"]: float(v) for nd, v in zip(nodes, loss)}, epoch_done
+        return self._finish(nodes, self.n), epoch_done

@@ -248,9 +248,8 @@ def _run(case, cached, momentum, monkeypatch, budget=None):
         tr = d_sgd._trainers[id(nodes)]
         assert tr.sampling == tr.cached == cached
         # the index block the gradient op read: the restatement's batches, node offsets added
-        nb = n * batch
-        bi = tr.idx_dev[:nb].view(n, batch).cpu().numpy()
-        bl = tr.idx_dev[nb:nb + n].cpu().numpy()
+        bi = tr.layout.view(tr.idx_dev, "indices").cpu().numpy()
+        bl = tr.layout.view(tr.idx_dev, "lengths").cpu().numpy()
         for j, (r, e, c) in enumerate(zip(rows, epoch.tolist(), cursor.tolist())):
             want = start[r] + _perm(r, e, sizes[r])[c:c + batch]
             assert bl[j] == len(want) and np.array_equal(bi[j, :len(want)], want), (k, j)

@@ -243,7 +243,7 @@ def test_two_rounds_equal_their_parts(momentum, sampling, gpu):
         for i, idx in enumerate(batches):
             bi[i, :idx.numel()] = (idx + int(start[i])).to(torch.int32)
         bl = torch.tensor([b.numel() for b in batches], dtype=torch.int32)
-        got_bi = tr.idx_dev[:n * batch].view(n, batch).cpu()
+        got_bi = tr.layout.view(tr.idx_dev, "indices").cpu()
         for i in range(n):                       # the index block the gradient op read
             assert torch.equal(got_bi[i, :int(bl[i])], bi[i, :int(bl[i])]), (rnd, i)
         loss = torch.empty(n, device=gpu)

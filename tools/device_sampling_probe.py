@@ -285,10 +285,10 @@ def rounds(a):
     # what is left on the host in a flag-on round, each alone between two synchronises: the
     # synchronous write-back of the slab, the loss copy, and the sampler's host part
     tr, parts = runs[True]["trainer"], {"write_back": [], "loss_d2h": [], "advance": []}
-    rows = list(range(min(a.sample, n))) if a.run == "sample" else tr.all_rows
+    rows = list(range(min(a.sample, n))) if a.run == "sample" else tr.source.all_rows
     for _ in range(a.rounds):
         for name, fn in (("write_back", tr.write_back), ("loss_d2h", lambda: tr.loss.cpu().tolist()),
-                         ("advance", lambda: tr.sampler.advance(rows))):
+                         ("advance", lambda: tr.source.sampler.advance(rows))):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             fn()
