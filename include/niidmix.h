@@ -36,7 +36,9 @@
  * permutation sorted once and sliced every round, for --device-sampling-cached; pure additions too);
  * niidmix_linear_nll_grad_rows_sliced_f32, niidmix_linear_nll_grad_rows_sliced_scratch_elems and
  * niidmix_linear_nll_grad_rows_sliced_slice added (the linear gradient at any batch size, for
- * --device-training-large-batch; pure additions too).
+ * --device-training-large-batch; pure additions too); niidmix_torch_randperm_i32 and its
+ * niidmix_torch_randperm_max_len added (torch.randperm's CPU stream on the device, for
+ * --device-sampling-torch-stream; pure additions too).
  * ABI 5: niidmix_dense_split_elems / niidmix_dense_split_w /
  * niidmix_mix_dense_bf16x6_f32 added (the dense GEMM on the bf16 matrix cores, fp32-accurate by
  * three-term splitting); niidmix_mix_strip_f32 refuses a strip that does not fit the device's LDS.
@@ -856,6 +858,39 @@ int niidmix_take_batches_i32(const int32_t *perm, int64_t perm_len, const int64_
                              const int32_t *seg_start, const int32_t *seg_len, const int32_t *cursor,
                              int64_t n_jobs, int64_t b_max, int32_t *batch_idx, int32_t *batch_len,
                              void *stream);
+
+/* torch's own permutations for the same cache (the drop-in's --device-sampling-torch-stream: the
+ * batches of the CPU path's DataLoaders, shuffled on the device): job j writes to
+ * perm[perm_off[j] .. perm_off[j] + seg_len[j]) the permutation that
+ *     torch.randperm(seg_len[j], generator=g)      after g.manual_seed(s), on the CPU
+ * gives for every s whose low 32 bits are seed_lo[j] (the int32 read as uint32), in
+ * niidmix_epoch_perm_i32's index convention (segment-local positions), so niidmix_take_batches_i32
+ * slices it unchanged.  That is MT19937 seeded by init_genrand(seed_lo[j]) feeding
+ *     for i in 0 .. seg_len-2:  z = next_u32 % (seg_len - i);  swap(a[i], a[i + z])
+ * on a = 0 .. seg_len-1 (niidmix/sampling.py, torch_permutation, restates it in numpy).
+ *   seed_lo, seg_len   [n_jobs] int32 (device)
+ *   perm_off  [n_jobs] int64 (device): the jobs' stretches of perm; they must not overlap each
+ *             other (not checked: overlapping stretches have two writers)
+ *   perm      [perm_len] int32 (device)
+ *   max_len   (host) the longest seg_len among the jobs: it sizes the workgroups' LDS
+ *             (2 * max_len + 3744 bytes, rounded up to 16)
+ * One workgroup per job keeps the positions as uint16 in LDS, so
+ * niidmix_torch_randperm_max_len() is 65536; the swaps are walked by one lane (the chain is
+ * serial), everything else by the workgroup.  No scratch.  Every word has one writer: two calls
+ * give the same bits.
+ * The per-job arrays are device data and are NOT read by the launcher.  A job whose seg_len is
+ * outside 1..max_len, or whose stretch does not lie inside [0, perm_len), is skipped and writes
+ * nothing -- nothing is read or written out of range whatever the arrays hold.
+ * Checked before anything touches the GPU, in this order:
+ *   NIIDMIX_EINVAL        a null pointer
+ *   NIIDMIX_EINVAL        n_jobs, max_len or perm_len < 1
+ *   NIIDMIX_EUNSUPPORTED  max_len above niidmix_torch_randperm_max_len(), n_jobs >= 2^31
+ *   NIIDMIX_EALIAS        perm overlaps an input
+ * Pure additions: the ABI version is unchanged. */
+int64_t niidmix_torch_randperm_max_len(void);
+int niidmix_torch_randperm_i32(const int32_t *seed_lo, const int32_t *seg_len, const int64_t *perm_off,
+                               int64_t n_jobs, int64_t max_len, int32_t *perm, int64_t perm_len,
+                               void *stream);
 
 /* update_models(all_models, avg) after the 'sample' topology's uniform average (d_sgd.py:240-250,
  * :29-35): every row y_i := fl(fl(x_i * 0) + avg) (p.mul_(0.); p.add_(new)) — avg everywhere

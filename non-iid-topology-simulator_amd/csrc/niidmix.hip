@@ -43,6 +43,7 @@
 //                                                                  niidmix_gnlenet_nll_grad_rows_f32
 //   sampling.inc       k_draw_batches, k_epoch_perm_chunks /       niidmix_draw_batches_i32, _epoch_perm_i32,
 //                      _global / _finish, k_take_batches           _take_batches_i32
+//                      k_torch_randperm                            niidmix_torch_randperm_i32
 //   halo pack          k_gather_rows (and the RCCL loader)         niidmix_mix_sharded_f32
 //   host side          (argument checks, env readers, pick, vec_width, BlockGeom, clique launchers)
 //   slab memory        (VMM allocator)                             niidmix_hbm_alloc, niidmix_hbm_free
@@ -6593,6 +6594,32 @@ int niidmix_take_batches_i32(const int32_t *perm, int64_t perm_len, const int64_
                        reinterpret_cast<hipStream_t>(stream), perm, perm_len, perm_off, seg_start, seg_len,
                        cursor, (int)b_max, batch_idx, batch_len);
     return check_launch("k_take_batches");
+}
+
+int64_t niidmix_torch_randperm_max_len(void) { return kTorchPermMaxLen; }
+
+int niidmix_torch_randperm_i32(const int32_t *seed_lo, const int32_t *seg_len, const int64_t *perm_off,
+                               int64_t n_jobs, int64_t max_len, int32_t *perm, int64_t perm_len,
+                               void *stream) {
+    if (!seed_lo || !seg_len || !perm_off || !perm) return set_error(NIIDMIX_EINVAL, "null pointer");
+    if (n_jobs < 1 || max_len < 1 || perm_len < 1)
+        return set_error(NIIDMIX_EINVAL, "n_jobs, max_len and perm_len must be >= 1");
+    if (max_len > kTorchPermMaxLen)
+        return set_error(NIIDMIX_EUNSUPPORTED, "max_len %lld: a segment of at most %d samples is shuffled",
+                         (long long)max_len, kTorchPermMaxLen);
+    if (n_jobs > 0x7fffffff) return set_error(NIIDMIX_EUNSUPPORTED, "n_jobs %lld: too many blocks", (long long)n_jobs);
+    auto f = [](const void *q) { return reinterpret_cast<const float *>(q); };      // 4-byte words
+    const std::pair<const void *, int64_t> ins[] = {{seed_lo, n_jobs}, {seg_len, n_jobs}, {perm_off, 2 * n_jobs}};
+    for (const auto &in : ins)
+        if (overlaps(f(in.first), in.second, f(perm), perm_len))
+            return set_error(NIIDMIX_EALIAS, "perm overlaps an input");
+    const size_t lds = torch_perm_lds_bytes((int)max_len);
+    if (lds > 64 * 1024)
+        if (int rc = lds_opt_in(k_torch_randperm, lds, "k_torch_randperm")) return rc;
+    hipLaunchKernelGGL(k_torch_randperm, dim3((unsigned)n_jobs), dim3(kDrawThreads), lds,
+                       reinterpret_cast<hipStream_t>(stream), seed_lo, seg_len, perm_off, (int)max_len, perm,
+                       perm_len);
+    return check_launch("k_torch_randperm");
 }
 
 int niidmix_update_rows_f32(const float *x, int64_t ld_x, float *y, int64_t ld_y, int64_t n_rows,

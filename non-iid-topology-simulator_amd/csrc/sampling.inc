@@ -1,7 +1,8 @@
 // Training batches drawn on the device (niidmix_draw_batches_i32; --device-sampling) and the cached
 // mode's whole-epoch permutations (niidmix_epoch_perm_i32, niidmix_take_batches_i32;
-// --device-sampling-cached).  Included by niidmix.hip; the host restatement of the same stream is
-// niidmix/sampling.py.
+// --device-sampling-cached), and torch's own permutations for the same cache
+// (niidmix_torch_randperm_i32; --device-sampling-torch-stream, at the end of the file).  Included by
+// niidmix.hip; the host restatement of both streams is niidmix/sampling.py.
 // ----------------------------------------------------------------------------------------------
 // The stream, in integers only.  Position i of a segment of `len` samples, for the node of rank r
 // in epoch e under the run seed s, gets the 32-bit key
@@ -293,4 +294,105 @@ __global__ __launch_bounds__(kDrawThreads) void k_take_batches(
     n = n > b_max ? b_max : n;
     if (t == 0) batch_len[job] = n;
     if (t < n) batch_idx[job * b_max + t] = seg_start[job] + perm[off + cur + t];
+}
+
+// ----------------------------------------------------------------------------------------------
+// torch's stream (--device-sampling-torch-stream): the permutation torch.randperm(len, generator=g)
+// gives on the CPU after g.manual_seed(s), for the cache k_take_batches slices.  ATen seeds MT19937
+// with the low 32 bits of s (init_genrand) and runs
+//     for i in 0 .. len-2:  z = next_u32 % (len - i);  swap(a[i], a[i + z])
+// on a = 0 .. len-1.  k_torch_randperm: one workgroup per job, everything in dynamic LDS -- the
+// positions as uint16 (len <= 65536), the 624 state words, one block of 624 reduced z.  Seeding is a
+// serial chain (one lane).  Per block of 624 draws: the twist in three stretches of (at most) 227
+// words, each reading what the one before wrote (all loads, a barrier, all stores); tempering and
+// the reduction modulo len - i by all lanes; then one lane walks the block's swaps, eight z per
+// 16-B load.  The result goes out as int32 with all lanes.  Only the walk is serial in len.
+constexpr int kTorchPermMaxLen = 65536;     // positions as uint16: 128 KiB of LDS
+constexpr int kMtN = 624, kMtM = 397;
+static_assert(kDrawThreads >= kMtN - kMtM && kMtN - 2 * (kMtN - kMtM) <= kDrawThreads && kMtN % 8 == 0,
+              "a twist stretch is one word per thread; the walk loads eight z at a time");
+
+// bytes of dynamic LDS for jobs of up to max_len samples: positions | state | z, each 16-B aligned
+__host__ __device__ constexpr size_t torch_perm_pos_bytes(int max_len) {
+    return ((size_t)max_len * 2 + 15) / 16 * 16;
+}
+__host__ __device__ constexpr size_t torch_perm_lds_bytes(int max_len) {
+    return torch_perm_pos_bytes(max_len) + kMtN * 4 + kMtN * 2;
+}
+
+// One regeneration of the state (genrand's next_state), in place, by the whole workgroup; ends
+// with a barrier.
+__device__ __forceinline__ void mt_twist(uint32_t *mt, int tid) {
+    constexpr int kStretch = kMtN - kMtM;                    // 227
+#pragma unroll
+    for (int s = 0; s < 3; ++s) {
+        const int k = s * kStretch + tid, end = s < 2 ? (s + 1) * kStretch : kMtN;
+        uint32_t v = 0;
+        if (k < end) {
+            // word k + 397 (mod 624) is old in the first stretch and new afterwards; word k + 1 is
+            // old except for k = 623, whose successor is the new word 0
+            const uint32_t u = mt[k], w = mt[k + 1 == kMtN ? 0 : k + 1];
+            const uint32_t y = (u & 0x80000000u) | (w & 0x7fffffffu);
+            v = mt[k < kStretch ? k + kMtM : k - kStretch] ^ (y >> 1) ^ (w & 1u ? 0x9908b0dfu : 0u);
+        }
+        __syncthreads();                                     // word k + 1 is read before it is written
+        if (k < end) mt[k] = v;
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(kDrawThreads) void k_torch_randperm(
+        const int32_t *__restrict__ seed_lo, const int32_t *__restrict__ seg_len,
+        const int64_t *__restrict__ perm_off, int max_len, int32_t *__restrict__ perm, int64_t perm_len) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char torch_perm_lds[];
+    const int64_t job = blockIdx.x;
+    const int tid = threadIdx.x;
+    const int n = seg_len[job];
+    const int64_t off = perm_off[job];
+    if (n < 1 || n > max_len || off < 0 || off > perm_len - n) return;      // uniform: the job is skipped
+    uint16_t *a = reinterpret_cast<uint16_t *>(torch_perm_lds);
+    uint32_t *mt = reinterpret_cast<uint32_t *>(torch_perm_lds + torch_perm_pos_bytes(max_len));
+    uint16_t *z = reinterpret_cast<uint16_t *>(mt + kMtN);
+
+    for (int t = tid; t < n; t += kDrawThreads) a[t] = (uint16_t)t;
+    if (tid == 0) {                                          // init_genrand
+        uint32_t s = (uint32_t)seed_lo[job];
+        mt[0] = s;
+        for (uint32_t j = 1; j < (uint32_t)kMtN; ++j) {
+            s = 1812433253u * (s ^ (s >> 30)) + j;
+            mt[j] = s;
+        }
+    }
+    __syncthreads();
+    for (int base = 0; base < n - 1; base += kMtN) {         // draws base .. base + cnt - 1
+        mt_twist(mt, tid);
+        const int cnt = n - 1 - base < kMtN ? n - 1 - base : kMtN;
+        for (int k = tid; k < cnt; k += kDrawThreads) {
+            uint32_t y = mt[k];
+            y ^= y >> 11;
+            y ^= (y << 7) & 0x9d2c5680u;
+            y ^= (y << 15) & 0xefc60000u;
+            y ^= y >> 18;
+            z[k] = (uint16_t)(y % (uint32_t)(n - (base + k)));          // < n - i <= 65536, n - i >= 2
+        }
+        __syncthreads();
+        if (tid == 0) {
+            for (int k0 = 0; k0 < cnt; k0 += 8) {
+                const uint4 q = *reinterpret_cast<const uint4 *>(z + k0);
+                const uint32_t w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    if (k0 + u < cnt) {
+                        const int i = base + k0 + u, t = i + (int)((w[u >> 1] >> (16 * (u & 1))) & 0xffffu);
+                        const uint16_t x = a[i], y = a[t];                 // t <= n - 1
+                        a[i] = y;
+                        a[t] = x;
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    }
+    int32_t *out = perm + off;
+    for (int t = tid; t < n; t += kDrawThreads) out[t] = (int32_t)a[t];
 }

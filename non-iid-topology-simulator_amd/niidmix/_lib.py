@@ -124,6 +124,8 @@ SIGNATURES = {
     "niidmix_epoch_perm_i32": (ctypes.c_int, [ctypes.c_uint32, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64,
                                               _vp, _i64, _vp]),
     "niidmix_take_batches_i32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
+    "niidmix_torch_randperm_max_len": (_i64, []),
+    "niidmix_torch_randperm_i32": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp]),
     "niidmix_sharded_create": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.POINTER(_vp)]),
     "niidmix_sharded_destroy": (ctypes.c_int, [_vp]),
     "niidmix_sharded_is_loopback": (ctypes.c_int, [_vp]),

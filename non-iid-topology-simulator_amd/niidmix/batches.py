@@ -89,10 +89,12 @@ class DeviceSource:
     (epoch, cursor) of every row (SamplerState), sends them in the one copy, and
     niidmix::draw_batches writes the indices and lengths into the block."""
 
+    keyed = True      # the stream is keyed by params['meta']['seed']
+
     def __init__(self, tr, nodes):
         from .sampling import SamplerState
         self.tr = tr
-        self.seed = int(tr.params["meta"]["seed"]) & 0xFFFFFFFF
+        self.seed = int(tr.params["meta"]["seed"]) & 0xFFFFFFFF if self.keyed else None
         off = np.asarray(tr.offsets, dtype=np.int64)
         self.seg_start = off[:-1]
         self.sampler = SamplerState([nd["rank"] for nd in nodes], off[1:] - off[:-1], tr.b_max,
@@ -159,22 +161,34 @@ class CachedSource(DeviceSource):
         the pinned block, rows of up to short_max samples first, and are marked cached."""
         st = self.sampler
         stale = st.stale(rows)
+        keys = self._keys(rows, stale)
         if stale.size == 0:
             return stale, 0
         short = st.length[stale] <= self.short_max
-        stale = np.concatenate([stale[short], stale[~short]])
+        order = np.argsort(~short, kind="stable")
+        stale, keys = stale[order], keys[order]
         m, lists = stale.size, self.host["sort_lists"]
-        lists[0, :m], lists[1, :m], lists[2, :m] = st.rank[stale], st.length[stale], st.epoch[stale]
+        lists[0, :m], lists[1, :m], lists[2, :m] = st.rank[stale], st.length[stale], keys
         self.host["perm_off"][1, :m] = self.seg_start[stale]
         st.mark_cached(stale)
         return stale, int(short.sum())
 
+    def _keys(self, rows, stale):
+        """What the third sort list holds for the rows `stale` of the round's rows: their epochs."""
+        return self.sampler.epoch[stale]
+
     def _draw(self, k, jd, stale, n_short):
-        """niidmix::epoch_perm over the rows `stale` (their lists are on the device): the short
-        ones in one call without scratch, the long ones in calls of as many rows as keep the
-        scratch within the trainer's budget (train.cut_rows); then niidmix::take_batches."""
+        """The permutations of the rows `stale` (their lists are on the device) into the cache, then
+        niidmix::take_batches."""
+        self.last_perm_jobs, self.last_perm_calls = len(stale), 0
+        self._sort(stale, n_short)
+        ops.take_batches(self.perm, self.tr.dev["perm_off"][0, :k], jd[1], jd[2], jd[4],
+                         self.tr.dev["indices"][:k], self.tr.dev["lengths"][:k])
+
+    def _sort(self, stale, n_short):
+        """niidmix::epoch_perm: the short rows in one call without scratch, the long ones in calls
+        of as many rows as keep the scratch within the trainer's budget (train.cut_rows)."""
         m, length = len(stale), self.sampler.length
-        self.last_perm_jobs, self.last_perm_calls = m, 0
         lists, off = self.tr.dev["sort_lists"], self.tr.dev["perm_off"][1]
 
         def call(a, b, scratch):
@@ -195,10 +209,42 @@ class CachedSource(DeviceSource):
                 b = min(m, a + cut)
                 nbytes = ops.epoch_perm_scratch_bytes(b - a, int(length[stale[a:b]].max()))
                 call(a, b, torch.empty(nbytes // 8, dtype=torch.int64, device=self.tr.device))
-        ops.take_batches(self.perm, self.tr.dev["perm_off"][0, :k], jd[1], jd[2], jd[4],
-                         self.tr.dev["indices"][:k], self.tr.dev["lengths"][:k])
 
 
-def source_class(sample, sampling, cached):
+class TorchStreamSource(CachedSource):
+    """--device-sampling-torch-stream: the cache holds the CPU path's own permutations.  The host
+    draws what the nodes' DataLoaders would draw from the global torch generator
+    (sampling.LoaderDraws: a few int64 values a round, no loop over nodes); a row that begins an
+    epoch sends the low 32 bits of its permutation's seed (as an int32 bit pattern) where
+    CachedSource sends its epoch, and niidmix::torch_randperm shuffles it as torch.randperm does.
+    Indices, epoch counts and the global generator's state are those of LoaderSource."""
+
+    keyed = False
+
+    def _keys(self, rows, stale):
+        """The round's draws from the global generator, for `rows` in order: the seeds of the
+        rows that begin an epoch (`stale`, in the same order)."""
+        from .sampling import LoaderDraws
+        st = self.sampler
+        rows = np.asarray(rows, dtype=np.int64)
+        seeds = LoaderDraws.round(st.cached[rows] != st.epoch[rows],
+                                  st.cursor[rows] + st.b >= st.length[rows])
+        return seeds.astype(np.uint32).view(np.int32)
+
+    def _sort(self, stale, n_short):
+        """niidmix::torch_randperm: the short rows in one call, the long ones in another, so that a
+        call's LDS follows its longest row; no scratch."""
+        m, length = len(stale), self.sampler.length
+        lists, off = self.tr.dev["sort_lists"], self.tr.dev["perm_off"][1]
+        for a, b in ((0, n_short), (n_short, m)):
+            if b > a:
+                ops.torch_randperm(lists[2, a:b], lists[1, a:b], off[a:b], int(length[stale[a:b]].max()),
+                                   self.perm)
+                self.last_perm_calls += 1
+
+
+def source_class(sample, sampling, cached, torch_stream=False):
     """The batch source of a run's mode; graph rounds and sample rounds share them."""
+    if sampling and torch_stream:
+        return TorchStreamSource
     return CachedSource if sampling and cached else DeviceSource if sampling else LoaderSource

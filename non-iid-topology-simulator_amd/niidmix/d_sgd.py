@@ -25,7 +25,9 @@ training runs on the device too: gradient, step and mixing never leave HBM (niid
 rounds of the 'sample' topology (the other two flags refuse it).  --device-sampling, with any of
 the three, draws the batches on the device too, from a sample stream of the plugin's own
 (niidmix.sampling) instead of one DataLoader per node; --device-sampling-cached keeps every epoch's
-permutation in HBM, which lifts that flag's limit of 8192 samples per node.
+permutation in HBM, which lifts that flag's limit of 8192 samples per node, and
+--device-sampling-torch-stream fills that cache with the CPU path's own permutations (torch's
+stream restated on the device: the samples of a run without --device-sampling).
 With --device-evaluation (params['algorithm']['device-evaluation'], opt-in) the logger's accuracy
 and loss events of linear and GN-LeNet models are computed on the device as well (niidmix.evaluate).
 """
@@ -777,6 +779,7 @@ def _device_training_step(state, params, rundir):
     for attr, now, msg in (("sample", train.sample_run, f"{train.FLAG_SAMPLE}: the run changed between a "
                             "sample round and a graph round under a live device trainer: not supported"),
                            ("sampling", train.sampling_enabled, train.FLAG_SAMPLING + switched),
+                           ("torch_stream", train.torch_stream_enabled, train.FLAG_TORCH + switched),
                            ("cached", train.cached_enabled, train.FLAG_CACHED + switched),
                            ("large", train.large_enabled, train.FLAG_LARGE + switched)):
         if getattr(tr, attr) != now(params):     # each is fixed for the trainer's life
@@ -910,9 +913,15 @@ def init(nodes, topology, params):
         from . import evaluate
         evaluate.check_eligible(nodes, params)            # refusals: ValueError naming the flag
     if params["algorithm"].get("device-training") or params["algorithm"].get("device-sampling") or \
-            params["algorithm"].get("device-training-large-batch"):
+            params["algorithm"].get("device-training-large-batch") or \
+            params["algorithm"].get("device-sampling-torch-stream"):
         from . import train
         train.check_eligible(nodes, params, topology)     # refusals: ValueError naming the flag
+        if train.torch_stream_enabled(params):
+            # --device-sampling-torch-stream: no loader either, but the global torch RNG moves as
+            # if one had been created per node here
+            from .sampling import LoaderDraws
+            LoaderDraws.at_init(len(nodes))
         for n in nodes:
             # --device-sampling: the batches are drawn on the device (niidmix.sampling's stream):
             # no loader, and sampling consumes nothing of the global torch RNG
@@ -1163,6 +1172,13 @@ def main(argv=None):
                          "8192 samples (up to 2^20) are accepted; the same sample stream: a run "
                          "draws, batch for batch, what plain --device-sampling draws with the same "
                          "seed")
+    ap.add_argument("--device-sampling-torch-stream", action="store_const", const=True, default=False,
+                    help="with --device-sampling (sets the --device-sampling-cached key too): the "
+                         "cached permutations are the CPU path's own -- the host draws from the "
+                         "global torch generator what one DataLoader per node would draw, and the "
+                         "device restates torch.randperm (MT19937, Fisher-Yates) on those seeds; "
+                         "same samples, batches, epoch counts and RNG state as the run without "
+                         "--device-sampling; train-sets of up to 65536 samples per node")
     ap.add_argument("--device-evaluation", action="store_const", const=True, default=False,
                     help="linear models only: the logger's train, test, validation and full-train "
                          "accuracy and loss of every logged node (and of the global model) are "
@@ -1183,6 +1199,8 @@ def main(argv=None):
                  "with linear models (not --device-training-gn-lenet)")
     if args.device_sampling_cached and not args.device_sampling:
         ap.error("--device-sampling-cached needs --device-sampling")
+    if args.device_sampling_torch_stream and not args.device_sampling:
+        ap.error("--device-sampling-torch-stream needs --device-sampling")
     rundir = m.rundir(args)
     params = m.params(rundir)
     topology = load_topology(rundir)
@@ -1206,7 +1224,9 @@ def main(argv=None):
         **({"device-training-sample": True} if args.device_training_sample else {}),
         **({"device-training-large-batch": True} if args.device_training_large_batch else {}),
         **({"device-sampling": True} if args.device_sampling else {}),
-        **({"device-sampling-cached": True} if args.device_sampling_cached else {}),
+        **({"device-sampling-cached": True} if args.device_sampling_cached
+           or args.device_sampling_torch_stream else {}),
+        **({"device-sampling-torch-stream": True} if args.device_sampling_torch_stream else {}),
         **({"device-evaluation": True} if args.device_evaluation else {}),
     })
     if args.rundir is None:

@@ -52,6 +52,10 @@ Ops (registered in the `niidmix` namespace, usable as torch.ops.niidmix.*):
                                                     in HBM, --device-sampling-cached)
   take_batches(perm, perm_off, seg_start, seg_len, cursor, batch_idx, batch_len)
                                                     k_take_batches (a round's slice of them)
+  torch_randperm(seed_lo, seg_len, perm_off, max_len, perm)
+                                                    k_torch_randperm (torch.randperm's CPU stream
+                                                    into the same cache,
+                                                    --device-sampling-torch-stream)
 All ops launch on torch's current HIP stream of the input's device, never synchronise, and raise
 RuntimeError (TORCH_CHECK-style) on bad arguments.  They accept HIP tensors only: there is no CPU
 implementation and no fallback.
@@ -1031,6 +1035,41 @@ def take_batches(perm: torch.Tensor, perm_off: torch.Tensor, seg_start: torch.Te
         perm.data_ptr(), perm.numel(), perm_off.data_ptr(), seg_start.data_ptr(), seg_len.data_ptr(),
         cursor.data_ptr(), n, b_max, batch_idx.data_ptr(), batch_len.data_ptr(), _stream(batch_idx))
     _lib.check(rc, "niidmix::take_batches")
+
+
+def torch_randperm_max_len():
+    """The longest sample segment niidmix::torch_randperm shuffles (include/niidmix.h)."""
+    return int(_lib.lib.niidmix_torch_randperm_max_len())
+
+
+@torch.library.custom_op("niidmix::torch_randperm", mutates_args=("perm",))
+def torch_randperm(seed_lo: torch.Tensor, seg_len: torch.Tensor, perm_off: torch.Tensor, max_len: int,
+                   perm: torch.Tensor) -> None:
+    """Job j's torch.randperm(seg_len[j], generator=manual_seed(s)) of the CPU, for any s whose low
+    32 bits are seed_lo[j] (int32 bit pattern), into perm[perm_off[j] : perm_off[j] + seg_len[j]]
+    (include/niidmix.h, niidmix_torch_randperm_i32; niidmix.sampling.torch_permutation restates
+    it); the rest of perm is untouched.  max_len: the longest seg_len (host), which sizes the
+    workgroups' LDS.  HIP tensors only; the per-job CONTENTS are not checked here (the kernel skips
+    a seg_len outside 1..max_len and a stretch outside perm)."""
+    _req(isinstance(perm, torch.Tensor) and perm.is_cuda,
+         f"perm: expected a HIP (cuda) tensor, got {perm.device} (no CPU fallback)")
+    dev = perm.device
+    _vec("perm", perm, torch.int32, dev)
+    _req(perm.numel() >= 1, "perm: empty")
+    _req(isinstance(seed_lo, torch.Tensor) and seed_lo.dim() == 1 and seed_lo.numel() >= 1,
+         "seed_lo: expected a 1-D tensor of n_jobs >= 1 elements")
+    n, max_len = seed_lo.numel(), int(max_len)
+    _req(1 <= max_len <= torch_randperm_max_len(),
+         f"max_len {max_len} is not in 1..{torch_randperm_max_len()}, the longest segment the kernel shuffles")
+    ins = (("seed_lo", seed_lo, torch.int32), ("seg_len", seg_len, torch.int32),
+           ("perm_off", perm_off, torch.int64))
+    for name, t, dtype in ins:
+        _vec(name, t, dtype, dev, n)
+        _req(not _hits(t, perm), f"perm overlaps {name}")
+    rc = _lib.lib.niidmix_torch_randperm_i32(
+        seed_lo.data_ptr(), seg_len.data_ptr(), perm_off.data_ptr(), n, max_len, perm.data_ptr(),
+        perm.numel(), _stream(perm))
+    _lib.check(rc, "niidmix::torch_randperm")
 
 
 # ------------------------------------------------------------------------------------------------

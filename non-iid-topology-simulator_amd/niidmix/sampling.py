@@ -19,8 +19,14 @@ epoch_done flags and batch lengths without a copy back from the device.  Under
 `--device-sampling-cached` the same permutations are sorted once per epoch into a device cache
 (niidmix::epoch_perm, sliced by niidmix::take_batches); SamplerState then also records which
 epoch's permutation each row's part of the cache holds.
+
+`--device-sampling-torch-stream` fills the same cache with the CPU path's own permutations instead:
+what one DataLoader(range(n), batch_size, shuffle=True) per node draws from the global torch RNG.
+torch_permutation restates torch.randperm on the CPU (MT19937 and a Fisher-Yates loop; the oracle
+of niidmix::torch_randperm), LoaderDraws the loaders' draws from the global generator.
 """
 import numpy as np
+import torch
 
 M0, M1 = 0xD2511F53, 0xCD9E8D57           # Philox4x32 multipliers
 W0, W1 = 0x9E3779B9, 0xBB67AE85           # Weyl increments of the key
@@ -99,3 +105,77 @@ class SamplerState:
         self.epoch[rows] = epoch + done
         self.cursor[rows] = np.where(done, 0, cursor + self.b)
         return epoch, cursor, dict(zip(self.rank[rows].tolist(), done.tolist()))
+
+
+# ------------------------------------------------------------------------------------------------
+# torch's stream (--device-sampling-torch-stream)
+MT_N, MT_M = 624, 397
+
+
+def mt19937_words(seed, count):
+    """The first `count` 32-bit outputs of MT19937 after init_genrand(seed & 0xffffffff) -- what
+    ATen's CPU generator yields after manual_seed(seed): uint32 array."""
+    mt = np.empty(MT_N, dtype=np.uint64)
+    s = int(seed) & MASK
+    mt[0] = s
+    for j in range(1, MT_N):
+        s = (1812433253 * (s ^ (s >> 30)) + j) & MASK
+        mt[j] = s
+    out = np.empty(-(-int(count) // MT_N) * MT_N, dtype=np.uint64)
+    up, low, one = np.uint64(0x80000000), np.uint64(0x7FFFFFFF), np.uint64(1)
+    for base in range(0, out.size, MT_N):
+        # the twist in three stretches: word k + 397 (mod 624) is old for k < 227 and new after;
+        # word k + 1 is old except for k = 623, whose successor is the new word 0
+        for a, b in ((0, MT_N - MT_M), (MT_N - MT_M, 2 * (MT_N - MT_M)), (2 * (MT_N - MT_M), MT_N)):
+            k = np.arange(a, b)
+            nxt = mt[(k + 1) % MT_N]
+            y = (mt[k] & up) | (nxt & low)
+            mt[k] = mt[(k + MT_M) % MT_N] ^ (y >> one) ^ ((nxt & one) * np.uint64(0x9908B0DF))
+        y = mt.copy()
+        y ^= y >> np.uint64(11)
+        y ^= (y << np.uint64(7)) & np.uint64(0x9D2C5680)
+        y ^= (y << np.uint64(15)) & np.uint64(0xEFC60000)
+        y ^= y >> np.uint64(18)
+        out[base:base + MT_N] = y
+    return out[:int(count)].astype(np.uint32)
+
+
+def torch_permutation(seed, n):
+    """torch.randperm(n, generator=g) on the CPU after g.manual_seed(seed), for n below 2^32 / 20
+    (ATen's randperm_cpu): a = 0 .. n-1, then for i in 0 .. n-2: z = next_u32 % (n - i) and
+    a[i], a[i + z] swap.  Only the seed's low 32 bits count.  int64 array."""
+    n = int(n)
+    a = list(range(n))
+    z = mt19937_words(seed, max(n - 1, 0)).astype(np.int64) % (n - np.arange(max(n - 1, 0)))
+    for i, zi in enumerate(z.tolist()):
+        a[i], a[i + zi] = a[i + zi], a[i]
+    return np.asarray(a, dtype=np.int64)
+
+
+class LoaderDraws:
+    """What the CPU path's loaders (train.index_loader, d_sgd._loader) draw from the global torch
+    generator, without the loaders.  A DataLoader iterator draws one int64 random_() when it is
+    created (its base seed, unused without workers) and its sampler one more at the first next():
+    the seed of the epoch's randperm.  train.draw creates a node's next loader in the round its
+    epoch ends, so a round draws, for each of its rows in order, "the seed if the row begins an
+    epoch, then a base seed if its epoch ends".  One random_() over a tensor of that many values
+    yields the values of as many scalar draws and leaves the generator in the same state."""
+
+    @staticmethod
+    def at_init(n):
+        """The base seeds of the n loaders init() would create."""
+        torch.empty(int(n), dtype=torch.int64).random_()
+
+    @staticmethod
+    def round(stale_mask, done_mask):
+        """One round's draws for its rows in order (boolean arrays: the row begins an epoch, its
+        epoch ends this round).  Returns the low 32 bits of the seeds of the rows that begin an
+        epoch, in row order: int64 array of values below 2^32."""
+        stale, done = np.asarray(stale_mask, dtype=bool), np.asarray(done_mask, dtype=bool)
+        per_row = stale.astype(np.int64) + done
+        m = int(per_row.sum())
+        if m == 0:
+            return np.empty(0, dtype=np.int64)
+        values = torch.empty(m, dtype=torch.int64).random_().numpy()
+        first = np.cumsum(per_row) - per_row             # a row's first draw is its seed
+        return values[first[stale]] & MASK

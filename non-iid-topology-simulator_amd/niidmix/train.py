@@ -85,6 +85,16 @@ niidmix::take_batches slices the cache into the index block (batches.CachedSourc
 travel in the same one H2D copy.  Train-sets up to ops.epoch_perm_max_len() are accepted; for shorter ones
 the batches are those of plain --device-sampling, bit for bit.
 
+`--device-sampling-torch-stream` (with --device-sampling; it implies the cache) gives the CPU path's
+samples back at that speed: the cache is filled with the permutations the nodes' DataLoaders would
+draw.  The host draws the loaders' values from the global torch generator (sampling.LoaderDraws: N
+at init(), then per round a seed for every row that begins an epoch and a base seed for every row
+whose epoch ends, in one vectorised random_()), and niidmix::torch_randperm restates
+torch.randperm's CPU algorithm -- MT19937 and a Fisher-Yates walk, one workgroup per row -- on the
+seeds' low 32 bits (batches.TorchStreamSource).  Batches, epoch counts and the global generator's
+state are those of the run without --device-sampling; train-sets of up to
+ops.torch_randperm_max_len() samples (65536) are accepted, and no run seed is needed.
+
 The linear kernel keeps one row's dz in LDS, so batch-size * C is bounded by ops.MAX_BC.
 `--device-training-large-batch` (with --device-training or --device-training-sample, linear models
 only) lifts that to ops.MAX_B_SLICED samples: a gradient call whose b_max * C exceeds MAX_BC goes
@@ -95,8 +105,9 @@ niidmix::take_batches slices (ops.epoch_perm_max_len()); plain --device-sampling
 One node (the centralised baseline) is a graph round like any other: the Mixer takes n = 1.
 
 Whatever the mode, a round's indices go up in one H2D copy of one pinned int32 block.  Its lists
-and the words a round copies are niidmix.batches.IndexLayout's; what fills it is one of three batch
-sources, chosen once per trainer (LoaderSource: draw() and the packing; DeviceSource; CachedSource),
+and the words a round copies are niidmix.batches.IndexLayout's; what fills it is one of four batch
+sources, chosen once per trainer (LoaderSource: draw() and the packing; DeviceSource; CachedSource;
+TorchStreamSource),
 so the two round methods do not know the sampling mode.
 """
 import os
@@ -115,6 +126,7 @@ FLAG_SAMPLE = "--device-training-sample"
 FLAG_SAMPLING = "--device-sampling"
 FLAG_CACHED = "--device-sampling-cached"
 FLAG_LARGE = "--device-training-large-batch"
+FLAG_TORCH = "--device-sampling-torch-stream"
 SCRATCH_FRACTION = 0.4   # of the free HBM, for one GN-LeNet gradient call's scratch
 # When a sample round takes the one-launch step + average + broadcast
 # (niidmix::sample_step_mean_update) instead of the three ops it restates: slabs of at least
@@ -148,8 +160,14 @@ def sampling_enabled(params):
 
 
 def cached_enabled(params):
-    """--device-sampling-cached: every epoch's permutation is sorted once and kept in HBM."""
-    return bool(params.get("algorithm", {}).get("device-sampling-cached"))
+    """--device-sampling-cached: every epoch's permutation is sorted once and kept in HBM.
+    --device-sampling-torch-stream fills the same cache, so it counts as well."""
+    return bool(params.get("algorithm", {}).get("device-sampling-cached")) or torch_stream_enabled(params)
+
+
+def torch_stream_enabled(params):
+    """--device-sampling-torch-stream: the cached permutations are the CPU path's own, torch's."""
+    return bool(params.get("algorithm", {}).get("device-sampling-torch-stream"))
 
 
 def large_enabled(params):
@@ -242,7 +260,11 @@ def check_sampling(nodes, params):
     """--device-sampling's own refusals, each a ValueError naming the flag: the stream needs the
     run's seed, and one workgroup sorts a node's whole train-set (ops.draw_batches_max_len) --
     under --device-sampling-cached a train-set may have ops.epoch_perm_max_len() samples; the batch
-    size stays bounded by the index block's kernel."""
+    size stays bounded by the index block's kernel.  --device-sampling-torch-stream draws from the
+    global torch generator and needs no seed; its kernel shuffles ops.torch_randperm_max_len()
+    samples per node, which bounds the batch too under --device-training-large-batch."""
+    if torch_stream_enabled(params):
+        return check_torch_stream(nodes, params)
     most = ops.draw_batches_max_len()
     longest = ops.epoch_perm_max_len() if cached_enabled(params) else most
     large = large_enabled(params)
@@ -268,6 +290,24 @@ def check_sampling(nodes, params):
             raise ValueError(f"{FLAG_SAMPLING}: node {nd['rank']}'s rank or epoch is outside int32")
 
 
+def check_torch_stream(nodes, params):
+    """check_sampling under --device-sampling-torch-stream; the refusals name that flag."""
+    longest = ops.torch_randperm_max_len()
+    most = longest if large_enabled(params) else ops.draw_batches_max_len()
+    b = int(params["algorithm"]["batch-size"])
+    if not 1 <= b <= most:
+        raise ValueError(f"{FLAG_TORCH}: batch size {b} is not in 1..{most}, the longest batch the "
+                         "kernel draws" + ("" if large_enabled(params) else
+                                           f" ({longest} under {FLAG_LARGE})"))
+    for nd in nodes:
+        ts = nd.get("train-set")
+        if ts is not None and len(ts) > longest:
+            raise ValueError(f"{FLAG_TORCH}: node {nd['rank']}'s train-set has {len(ts)} samples, the "
+                             f"kernel shuffles at most {longest} per node")
+        if not 0 <= int(nd.get("epoch", 0)) < 2 ** 31 - 1:
+            raise ValueError(f"{FLAG_TORCH}: node {nd['rank']}'s epoch is outside int32")
+
+
 def check_eligible(nodes, params, topology=None):
     """The refusals that need no GPU (d_sgd.init calls this): raises ValueError naming the flag
     (--device-sampling's are check_sampling's, and that it needs one of the training flags;
@@ -279,6 +319,9 @@ def check_eligible(nodes, params, topology=None):
     does, and needs nothing of `topology`."""
     from . import d_sgd
     alg = params["algorithm"]
+    if torch_stream_enabled(params) and not sampling_enabled(params):
+        raise ValueError(f"{FLAG_TORCH} shuffles {FLAG_SAMPLING}'s batches as torch does: it needs "
+                         f"{FLAG_SAMPLING}")
     if cached_enabled(params) and not sampling_enabled(params):
         raise ValueError(f"{FLAG_CACHED} caches the permutations of {FLAG_SAMPLING}'s stream: it needs "
                          f"{FLAG_SAMPLING}")
@@ -365,8 +408,9 @@ class DeviceTrainer:
         self.family = family.family_of(nodes[0]["model"])[0]
         self.flag = flag_of(params)
         self.sample = sample_run(params)     # fixed for the trainer's life (d_sgd._trainer)
-        self.sampling = sampling_enabled(params)     # and so are these two
+        self.sampling = sampling_enabled(params)     # and so are these three
         self.cached = cached_enabled(params)
+        self.torch_stream = torch_stream_enabled(params)
         self.large = large_enabled(params)           # batches beyond ops.MAX_BC: the sliced op
         self.scratch_budget = None      # bytes of scratch per GN-LeNet gradient call (None:
         self.last_calls = 0              # SCRATCH_FRACTION of the free HBM); calls of the last round
@@ -410,7 +454,8 @@ class DeviceTrainer:
         self.idx_host = torch.zeros(self.layout.words, dtype=torch.int32).pin_memory()
         self.idx_dev = torch.empty_like(self.idx_host, device=dev)
         self.dev = {name: self.layout.view(self.idx_dev, name) for name in self.layout.spans}
-        self.source = batches.source_class(self.sample, self.sampling, self.cached)(self, nodes)
+        self.source = batches.source_class(self.sample, self.sampling, self.cached,
+                                                self.torch_stream)(self, nodes)
         self.stepped_rows = set()     # sample rounds: rows that have taken an optimizer step
         self.last_first = []          # the `first` flags of the last sample round (tests)
         self._avg = None              # sample rounds, three-op sequence: the CSR row and the average
@@ -458,7 +503,8 @@ class DeviceTrainer:
         need += self._gn_need(1 if self.family.cut else self.n)
         if self.cached:      # the permutation cache, and the sort's scratch for the longest row alone
             longest = max(b - a for a, b in zip(self.offsets, self.offsets[1:]))
-            need += self.offsets[-1] * 4 + ops.epoch_perm_scratch_bytes(1, longest)
+            need += self.offsets[-1] * 4
+            need += 0 if self.torch_stream else ops.epoch_perm_scratch_bytes(1, longest)
         free, _ = torch.cuda.mem_get_info(self.device)
         if need > 0.8 * free:
             raise RuntimeError(f"{self.flag}: {need / 2**30:.1f} GiB of device buffers ({n_buf} slabs of "

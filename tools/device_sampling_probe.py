@@ -30,11 +30,20 @@
                e60000  1 job of 60 000 samples, B 128
                e10000  5 jobs of 10 000 samples, B 128
            and epoch_perm's share of the gradient call once divided by the rounds of an epoch.
+  torch    the same for niidmix_torch_randperm_i32 (--device-sampling-torch-stream): single
+           launches of it, of niidmix_epoch_perm_i32 on the same jobs and of
+           niidmix_take_batches_i32, alternating, checked against torch.randperm on the CPU, at
+               r250    1000 jobs of 250 samples, B 125
+               e60000  1 job of 60 000 samples, B 128
+           rounds --torch-stream compares whole rounds: flag off is --device-sampling
+           --device-sampling-cached, flag on adds --device-sampling-torch-stream.
 
     python tools/device_sampling_probe.py kernel --shape small [--warmup 5] [--reps 20]
     python tools/device_sampling_probe.py rounds --run linear [--per-node 60] [--warmup 2] [--rounds 10]
     python tools/device_sampling_probe.py rounds --run linear --cached
     python tools/device_sampling_probe.py cached --shape e60000 [--warmup 5] [--reps 20]
+    python tools/device_sampling_probe.py torch --shape r250 [--warmup 5] [--reps 20]
+    python tools/device_sampling_probe.py rounds --run linear --torch-stream --per-node 250
 
 Every step prints one JSON line.
 """
@@ -51,6 +60,7 @@ sys.path[:0] = [REPO, os.path.join(REPO, "non-iid-topology-simulator_amd"), os.p
 
 KERNEL_SHAPES = {"small": (1000, 60, 125), "large": (100, 600, 128)}
 CACHED_SHAPES = {**KERNEL_SHAPES, "e60000": (1, 60000, 128), "e10000": (5, 10000, 128)}
+TORCH_SHAPES = {"r250": (1000, 250, 125), "e60000": CACHED_SHAPES["e60000"]}
 K, C = 784, 10
 
 
@@ -202,6 +212,67 @@ def cached(a):
     print(json.dumps(out))
 
 
+def torch_stream(a):
+    import numpy as np
+    import torch
+    from niidmix import _lib
+    n, length, b = TORCH_SHAPES[a.shape]
+    dev = torch.device("cuda:0")
+    i32 = dict(dtype=torch.int32, device=dev)
+    rank = torch.arange(n, **i32)
+    seeds = rank + a.seed                                  # job j: manual_seed(seed + j)
+    start, seg = rank * length, torch.full((n,), length, **i32)
+    off = start.to(torch.int64)
+    zero = torch.zeros(n, **i32)
+    idx, blen = torch.zeros(n, b, **i32), torch.zeros(n, **i32)
+    perm, perm2 = torch.zeros(n * length, **i32), torch.zeros(n * length, **i32)
+    lib = _lib.lib
+    sort_bytes = int(lib.niidmix_epoch_perm_scratch_bytes(n, length))
+    sort_scratch = torch.empty(max(sort_bytes // 8, 2), dtype=torch.int64, device=dev)
+    strm = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+    def shuffle_call():
+        return lib.niidmix_torch_randperm_i32(seeds.data_ptr(), seg.data_ptr(), off.data_ptr(), n, length,
+                                              perm.data_ptr(), perm.numel(), strm)
+
+    def sort_call():
+        return lib.niidmix_epoch_perm_i32(a.seed, rank.data_ptr(), seg.data_ptr(), zero.data_ptr(),
+                                          off.data_ptr(), n, length, perm2.data_ptr(), perm2.numel(),
+                                          sort_scratch.data_ptr(), sort_bytes, strm)
+
+    def take_call():
+        return lib.niidmix_take_batches_i32(perm.data_ptr(), perm.numel(), off.data_ptr(), start.data_ptr(),
+                                            seg.data_ptr(), zero.data_ptr(), n, b, idx.data_ptr(),
+                                            blen.data_ptr(), strm)
+
+    calls = [("torch_randperm", shuffle_call), ("epoch_perm", sort_call), ("take", take_call)]
+    times = {name: [] for name, _ in calls}
+    for rep in range(a.warmup + a.reps):
+        for name, fn in calls:
+            s0, e0 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s0.record()
+            _lib.check(fn(), name)
+            e0.record()
+            e0.synchronize()
+            if rep >= a.warmup:
+                times[name].append(s0.elapsed_time(e0) * 1e-3)
+    nb = min(b, length)
+    got, whole = idx.cpu().numpy(), perm.cpu().numpy()
+    for r in (0, n - 1):                                   # what was timed is torch's permutation
+        want = torch.randperm(length, generator=torch.Generator().manual_seed(a.seed + r)).numpy()
+        assert np.array_equal(whole[r * length:(r + 1) * length], want), r
+        assert np.array_equal(got[r, :nb], r * length + want[:nb]), r
+    rounds_per_epoch = -(-length // b)
+    out = {"step": "torch", "shape": a.shape, "n": n, "len": length, "b": b, "warmup": a.warmup,
+           "reps": a.reps, "device": torch.cuda.get_device_name(dev), "lib_sha16": _lib.lib_sha16(),
+           "rounds_per_epoch": rounds_per_epoch}
+    for name, _ in calls:
+        out[name] = _stats(times[name])
+    out["torch_randperm_over_epoch_perm"] = out["torch_randperm"]["median_ms"] / out["epoch_perm"]["median_ms"]
+    out["torch_randperm_us_per_round"] = out["torch_randperm"]["median_ms"] * 1e3 / rounds_per_epoch
+    print(json.dumps(out))
+
+
 def rounds(a):
     import torch
     import torch.nn.functional as F
@@ -250,8 +321,10 @@ def rounds(a):
                                 "unbiased-gradient": False, "deferred-writeback": True,
                                 "mixing-mode": "exact", "device-training": True,
                                 **{f: True for f in flags},
-                                **({"device-sampling": True} if on or a.cached else {}),
-                                **({"device-sampling-cached": True} if on and a.cached else {})}}
+                                **({"device-sampling": True} if on or a.cached or a.torch_stream else {}),
+                                **({"device-sampling-cached": True} if (on and a.cached) or a.torch_stream
+                                   else {}),
+                                **({"device-sampling-torch-stream": True} if on and a.torch_stream else {})}}
         nodes = []
         for r in range(n):
             mdl = Net()
@@ -271,10 +344,12 @@ def rounds(a):
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
             run["trainer"] = d_sgd._trainers[id(run["state"]["nodes"])]
-            assert run["trainer"].sampling == (on or a.cached) and run["trainer"].cached == (on and a.cached)
+            tr = run["trainer"]
+            assert tr.sampling == (on or a.cached or a.torch_stream) and tr.torch_stream == (on and a.torch_stream)
+            assert tr.cached == ((on and a.cached) or a.torch_stream)
             if rnd >= a.warmup:
                 run["times"].append(dt)
-    out = {"step": "rounds", "run": a.run, "cached": a.cached, "n": n, "k": k, "c": C, "b": b, "per_node": per_node,
+    out = {"step": "rounds", "run": a.run, "cached": a.cached, "torch_stream": a.torch_stream, "n": n, "k": k, "c": C, "b": b, "per_node": per_node,
            "sample": a.sample if a.run == "sample" else None, "momentum": a.momentum,
            "warmup": a.warmup, "rounds": a.rounds, "threads": torch.get_num_threads(),
            "device": torch.cuda.get_device_name(0)}
@@ -300,8 +375,11 @@ def rounds(a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("step", choices=["kernel", "rounds", "cached"])
-    ap.add_argument("--shape", choices=list(CACHED_SHAPES), default="small")
+    ap.add_argument("step", choices=["kernel", "rounds", "cached", "torch"])
+    ap.add_argument("--shape", choices=list({**CACHED_SHAPES, **TORCH_SHAPES}), default="small")
+    ap.add_argument("--torch-stream", action="store_true",
+                    help="rounds: flag off is --device-sampling --device-sampling-cached, flag on adds "
+                         "--device-sampling-torch-stream")
     ap.add_argument("--cached", action="store_true",
                     help="rounds: flag off is plain --device-sampling, flag on adds --device-sampling-cached")
     ap.add_argument("--run", choices=["linear", "sample", "gn"], default="linear")
@@ -322,7 +400,11 @@ def main():
         a.warmup = 2 if a.step == "rounds" else 5
     if a.step == "kernel" and a.shape not in KERNEL_SHAPES:
         sys.exit(f"device_sampling_probe: kernel --shape is one of {list(KERNEL_SHAPES)}")
-    {"kernel": kernel, "rounds": rounds, "cached": cached}[a.step](a)
+    if a.step == "cached" and a.shape not in CACHED_SHAPES:
+        sys.exit(f"device_sampling_probe: cached --shape is one of {list(CACHED_SHAPES)}")
+    if a.step == "torch" and a.shape not in TORCH_SHAPES:
+        sys.exit(f"device_sampling_probe: torch --shape is one of {list(TORCH_SHAPES)}")
+    {"kernel": kernel, "rounds": rounds, "cached": cached, "torch": torch_stream}[a.step](a)
 
 
 if __name__ == "__main__":
