@@ -945,8 +945,8 @@ int niidmix_mix_sharded_f32(niidmix_sharded *h, const niidmix_shard *shards, int
 /* Device memory for node-state slabs, with the signatures of a PyTorch pluggable allocator
  * (torch.cuda.memory.CUDAPluggableAllocator; niidmix.memory.slab_pool uses them for a MemPool).
  * The range is reserved with hipMemAddressReserve and mapped from 2 MiB physical chunks
- * (hipMemCreate / hipMemMap): the clique kernel's access pattern measured 1.32 ms per headline round
- * on every such slab, against 1.35-1.64 ms on hipMalloc'ed slabs depending on their physical
+ * (hipMemCreate / hipMemMap; at most 4096 of them, so slabs over 8 GiB take larger chunks): the
+ * clique kernel's access pattern measured 1.32 ms per headline round on every such slab, against 1.35-1.64 ms on hipMalloc'ed slabs depending on their physical
  * placement.  Returns NULL on failure (niidmix_last_error says why); free with
  * niidmix_hbm_free (size, device and stream are ignored). */
 void *niidmix_hbm_alloc(ssize_t size, int device, void *stream);

@@ -5313,8 +5313,14 @@ int launch_clique_tiled(const float *x, int64_t ld_x, float *y, int64_t ld_y, in
 // tried, but at 1.35-1.64 ms on hipMalloc'ed slabs depending on where the driver places them (a
 // physically contiguous hipExtMallocWithFlags slab: 1.49-1.57 ms every time; a linear copy is
 // unaffected).  niidmix_hbm_alloc therefore reserves a VA range and maps it chunk by chunk.
+// Every mapped chunk is a mapping of its own to the driver, and a process may hold only so many
+// (a 2^20-column slab of 10 000 rows is 20 000 chunks of 2 MiB; with some 40 000 mapped,
+// hipMemSetAccess fails with ENOMEM where the GPU is passed through to a virtual machine).  A
+// slab of more than kHbmMaxChunks chunks is therefore mapped from larger ones: the chunk doubles
+// until the slab needs no more than that.
 struct HbmBlock {
     size_t bytes;
+    size_t chunk;                    // bytes per physical chunk: kHbmChunk << k
     std::vector<hipMemGenericAllocationHandle_t> chunks;
     std::vector<size_t> slot;        // VA chunk slot of chunks[i]
 };
@@ -5322,9 +5328,10 @@ struct HbmBlock {
 std::mutex &g_hbm_mu = *new std::mutex;
 std::unordered_map<void *, HbmBlock> &g_hbm = *new std::unordered_map<void *, HbmBlock>;
 constexpr size_t kHbmChunk = 2u << 20;
+constexpr size_t kHbmMaxChunks = 4096;       // slabs of up to 8 GiB keep 2 MiB chunks
 
 void hbm_release(void *va, HbmBlock &b, size_t mapped) {
-    for (size_t i = 0; i < mapped; ++i) (void)hipMemUnmap((char *)va + b.slot[i] * kHbmChunk, kHbmChunk);
+    for (size_t i = 0; i < mapped; ++i) (void)hipMemUnmap((char *)va + b.slot[i] * b.chunk, b.chunk);
     for (auto h : b.chunks) (void)hipMemRelease(h);
     (void)hipMemAddressFree(va, b.bytes);
 }
@@ -5355,10 +5362,12 @@ void *niidmix_hbm_alloc(ssize_t size, int device, void *stream) {
         return nullptr;
     }
     HbmBlock b;
-    const size_t n = ((size_t)size + kHbmChunk - 1) / kHbmChunk;
-    b.bytes = n * kHbmChunk;
+    b.chunk = kHbmChunk;
+    while (((size_t)size + b.chunk - 1) / b.chunk > kHbmMaxChunks) b.chunk *= 2;
+    const size_t n = ((size_t)size + b.chunk - 1) / b.chunk;
+    b.bytes = n * b.chunk;
     void *va = nullptr;
-    if (hipMemAddressReserve(&va, b.bytes, kHbmChunk, nullptr, 0) != hipSuccess) {
+    if (hipMemAddressReserve(&va, b.bytes, b.chunk, nullptr, 0) != hipSuccess) {
         set_error(NIIDMIX_EHIP, "hbm_alloc: VA reservation of %zu B failed", b.bytes);
         return nullptr;
     }
@@ -5366,7 +5375,7 @@ void *niidmix_hbm_alloc(ssize_t size, int device, void *stream) {
     bool ok = true;
     for (size_t i = 0; i < n && ok; ++i) {
         hipMemGenericAllocationHandle_t h;
-        if (hipMemCreate(&h, kHbmChunk, &prop, 0) != hipSuccess) { ok = false; break; }
+        if (hipMemCreate(&h, b.chunk, &prop, 0) != hipSuccess) { ok = false; break; }
         b.chunks.push_back(h);
     }
     // chunk i goes to VA slot slot[i], a fixed pseudo-random permutation (Fisher-Yates over
@@ -5383,7 +5392,7 @@ void *niidmix_hbm_alloc(ssize_t size, int device, void *stream) {
     b.slot = slot;
     size_t mapped = 0;
     for (size_t i = 0; i < b.chunks.size() && ok; ++i) {
-        if (hipMemMap((char *)va + b.slot[i] * kHbmChunk, kHbmChunk, 0, b.chunks[i], 0) != hipSuccess) { ok = false; break; }
+        if (hipMemMap((char *)va + b.slot[i] * b.chunk, b.chunk, 0, b.chunks[i], 0) != hipSuccess) { ok = false; break; }
         ++mapped;
     }
     if (ok) {

@@ -1,8 +1,8 @@
 """Node-state slab memory in HBM.
 
 The [N, P] node slabs that stay resident in HBM are allocated by libniidmix's VMM allocator
-(niidmix_hbm_alloc: a reserved VA range mapped from 2 MiB physical chunks) through a torch MemPool
-with a pluggable allocator, so they are ordinary torch tensors.  The clique kernel's access pattern
+(niidmix_hbm_alloc: a reserved VA range mapped from 2 MiB physical chunks, larger ones for slabs
+over 8 GiB) through a torch MemPool with a pluggable allocator, so they are ordinary torch tensors.  The clique kernel's access pattern
 (the rows of a clique at one column chunk, every clique of the chunk in flight together) measured
 1.32 ms per headline round on every such slab, against 1.35-1.64 ms on hipMalloc'ed slabs
 depending on where the driver placed them physically (tools/hbm_probe7.hip); linear copies are
