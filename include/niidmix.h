@@ -709,6 +709,48 @@ int niidmix_gnlenet_eval_rows_f32(const float *theta, int64_t ld_t, const float 
                                   int64_t H, int64_t W, int64_t C, void *scratch,
                                   int64_t scratch_bytes, void *stream);
 
+/* niidmix_gnlenet_eval_rows_f32 with conv2 and conv3 on the matrix cores (k_gnl_eval_mfma; the
+ * drop-in's --device-evaluation-mfma).  Arguments, job model, outputs, forward pass and contracts
+ * are those of niidmix_gnlenet_eval_rows_f32; what differs:
+ *   tile      a workgroup takes T samples of a job: T = 4 while the weight stage, the statistics
+ *             and ONE activation buffer (conv2's input with a shared zero halo, or conv2's output
+ *             plus conv3's halo'd input) fit in 160 KiB of LDS and a wave owns at most 7 / 2
+ *             M-tiles of conv2 / conv3, which holds up to 13 x 13 pooled maps (H, W <= 28);
+ *             else T = 2, up to 20 x 20 pooled maps (H, W <= 42).  loss_sum adds the fp32
+ *             nll_s in double in sample order within a tile of T, the tiles in tile order.
+ *   conv2/3   v_mfma_f32_32x32x2_f32 (fp32 in, fp32 accumulate) over K = 800 in the order (input
+ *             channel pair, tap), the pair's two channels inside one instruction.  An output is one
+ *             such chain whatever its position in the tile, so a sample's logits do not depend on
+ *             where in a tile it falls.  Not bit-identical to niidmix_gnlenet_eval_rows_f32
+ *             (another summation order); the same bound, 4 e32 from the float64 forward
+ *             (tests/test_gpu_eval_gnlenet_mfma.py).
+ *   NaN/inf   a non-finite conv2 / conv3 weight also reaches the border positions through the
+ *             zero halo (0 * inf); GroupNorm spreads it over the group in either kernel, and it
+ *             stays in the jobs that list that row.
+ *   scratch   niidmix_gnlenet_eval_rows_mfma_scratch_bytes(...) bytes: the per (job, tile of T)
+ *             partial sums and counts only.  There are no activation slots: a shape whose tile of
+ *             2 does not fit in LDS is NIIDMIX_EUNSUPPORTED (the scratch size is then 0).
+ * Determinism, independence of the other jobs and of the cut of the job list, theta not written:
+ * as niidmix_gnlenet_eval_rows_f32.
+ * Checked before anything touches the GPU, in niidmix_gnlenet_eval_rows_f32's order:
+ *   NIIDMIX_EINVAL        a null pointer other than pred and logits
+ *   NIIDMIX_EINVAL        n_jobs, Cin, H, W or C < 1, max_len < 0
+ *   NIIDMIX_EUNSUPPORTED  C > 1024, Cin > 4, H or W outside [15, 64], then a shape whose tile of 2
+ *                         samples does not fit (2 x 40 x 36 fits, 2 x 44 x 44 does not)
+ *   NIIDMIX_EINVAL        ld_t < P
+ *   NIIDMIX_EINVAL        ld_pred < max_len (pred given), ld_logits < max_len (logits given)
+ *   NIIDMIX_EINVAL        a scratch buffer that is too small or not 8-B aligned
+ *   NIIDMIX_EALIAS        loss_sum, correct, pred, logits or scratch overlaps theta */
+int64_t niidmix_gnlenet_eval_rows_mfma_scratch_bytes(int64_t n_jobs, int64_t max_len, int64_t Cin,
+                                                     int64_t H, int64_t W, int64_t C);
+int niidmix_gnlenet_eval_rows_mfma_f32(const float *theta, int64_t ld_t, const float *data,
+                                       const int32_t *labels, const int32_t *rows,
+                                       const int32_t *seg_start, const int32_t *seg_len,
+                                       int64_t n_jobs, int64_t max_len, double *loss_sum,
+                                       int32_t *correct, int32_t *pred, int64_t ld_pred, float *logits,
+                                       int64_t ld_logits, int64_t Cin, int64_t H, int64_t W, int64_t C,
+                                       void *scratch, int64_t scratch_bytes, void *stream);
+
 /* Local training of GN-LeNet on the listed rows: gradient and loss of one mini-batch per row, for
  * every row in one call (the drop-in's --device-training-gn-lenet; niidmix.train.DeviceTrainer).
  * The job model and the argument meanings are those of niidmix_linear_nll_grad_rows_f32; the row

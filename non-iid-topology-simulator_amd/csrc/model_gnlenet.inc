@@ -81,7 +81,7 @@ __device__ __forceinline__ float gn_wave_sum(float v) {
 // clamps s to the tile), out [kGnTS, 32, h1, w1] = max over the 3 x 3 window of the conv outputs,
 // plus the bias.  AM: amax [kGnTS, 32, h1, w1] gets the window position (3 row + column) of that
 // maximum, the first one in scan order (gn_max's rule).
-template <bool AM = false, class XOf>
+template <bool AM = false, int TS = kGnTS, class XOf>
 __device__ __forceinline__ void gn_conv1_pool(XOf xof, const GnShape &g, const float *__restrict__ th,
                                               float *out, float *ws, unsigned char *amax = nullptr) {
     constexpr int WS = 32 + 4;
@@ -89,7 +89,7 @@ __device__ __forceinline__ void gn_conv1_pool(XOf xof, const GnShape &g, const f
     const int nk = g.Cin * 25;
     for (int e = tid; e < 32 * nk; e += 256) ws[(e % nk) * WS + e / nk] = th[g.c1w + e];
     __syncthreads();
-    const int hw1 = g.h1 * g.w1, per_g = kGnTS * hw1;
+    const int hw1 = g.h1 * g.w1, per_g = TS * hw1;
 #pragma unroll 1
     for (int item = tid; item < 4 * per_g; item += 256) {
         const int ocg = item / per_g, rem = item % per_g;
@@ -264,12 +264,12 @@ __device__ __forceinline__ void gn_conv(const float *in, float *out, int h, int 
 
 // GroupNorm(2, CO) statistics of buf [kGnTS, CO, hw] in two passes, then per (sample, channel)
 // scale = rstd * weight, shift = bias - scale * mean into stat[16 + 2 (s CO + c)].
-template <int CO>
+template <int CO, int TS = kGnTS>
 __device__ __forceinline__ void gn_stats(const float *buf, int hw, const float *__restrict__ gw,
                                          const float *__restrict__ gb, float *stat) {
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int n = (CO / 2) * hw;
-    for (int pair = wave; pair < kGnTS * 2; pair += 4) {
+    for (int pair = wave; pair < TS * 2; pair += 4) {
         const float *p = buf + pair * n;         // (sample, group) maps are contiguous, in this order
         float a = 0.f;
         for (int i = lane; i < n; i += 64) a += p[i];
@@ -286,7 +286,7 @@ __device__ __forceinline__ void gn_stats(const float *buf, int hw, const float *
         }
     }
     __syncthreads();
-    for (int e = tid; e < kGnTS * CO; e += 256) {
+    for (int e = tid; e < TS * CO; e += 256) {
         const int c = e % CO, pair = (e / CO) * 2 + c / (CO / 2);
         const float scale = stat[pair * 2 + 1] * gw[c];
         stat[16 + 2 * e] = scale;
@@ -295,39 +295,42 @@ __device__ __forceinline__ void gn_stats(const float *buf, int hw, const float *
     __syncthreads();
 }
 
-// out [kGnTS, CO, ho, wo] = relu(maxpool(3, 2)(in * scale + shift)), in [kGnTS, CO, h, w]
-template <int CO>
+// out [TS, CO, ho, wo] = relu(maxpool(3, 2)(in * scale + shift)), in [TS, CO, h, w].  HALO: out in
+// the matrix-core kernel's shared-halo layout (model_gnlenet_mfma.inc), whose zeros are not written.
+template <int CO, int TS = kGnTS, bool HALO = false>
 __device__ __forceinline__ void gn_norm_pool(const float *in, float *out, int h, int w, int ho, int wo,
                                              const float *stat) {
-    for (int e = threadIdx.x; e < kGnTS * CO * ho * wo; e += 256) {
+    for (int e = threadIdx.x; e < TS * CO * ho * wo; e += 256) {
         const int j = e % wo, i = (e / wo) % ho, sc = e / (wo * ho);
         const float scale = stat[16 + 2 * sc], shift = stat[16 + 2 * sc + 1];
         const float *p = in + (sc * h + 2 * i) * w + 2 * j;
         float m = __builtin_fmaf(p[0], scale, shift);
 #pragma unroll
         for (int a = 1; a < 9; ++a) m = gn_max(m, __builtin_fmaf(p[(a / 3) * w + a % 3], scale, shift));
-        out[e] = gn_relu(m);
+        if constexpr (HALO) out[(sc * (ho + 2) + i + 2) * (wo + 2) + j + 2] = gn_relu(m);
+        else out[e] = gn_relu(m);
     }
     __syncthreads();
 }
 
-// classifier: feat is [kGnTS, F] in (channel, row, column) order; logits to z [kGnTS, C]
+// classifier: feat is [TS, F] in (channel, row, column) order; logits to z [TS, C]
+template <int TS = kGnTS>
 __device__ __forceinline__ void gn_linear(const float *feat, const GnShape &g, const float *__restrict__ th,
                                           float *zout) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     for (int c = wave; c < g.C; c += 4) {
         const float *wr = th + g.fw + (int64_t)c * g.F;
-        float z[kGnTS];
+        float z[TS];
 #pragma unroll
-        for (int s = 0; s < kGnTS; ++s) z[s] = 0.f;
+        for (int s = 0; s < TS; ++s) z[s] = 0.f;
         for (int f = lane; f < g.F; f += 64) {
             const float wv = wr[f];
 #pragma unroll
-            for (int s = 0; s < kGnTS; ++s) z[s] = __builtin_fmaf(feat[s * g.F + f], wv, z[s]);
+            for (int s = 0; s < TS; ++s) z[s] = __builtin_fmaf(feat[s * g.F + f], wv, z[s]);
         }
         const float b = th[g.fb + c];
 #pragma unroll
-        for (int s = 0; s < kGnTS; ++s) {
+        for (int s = 0; s < TS; ++s) {
             const float v = gn_wave_sum(z[s]) + b;
             if (lane == 0) zout[s * g.C + c] = v;
         }

@@ -41,6 +41,8 @@
 //                      k_lin_reduce_sl                             (any batch size: slices of the batch)
 //   model_gnlenet.inc  k_gnl_eval, k_gnl_grad_sample / _conv / _fc niidmix_gnlenet_eval_rows_f32,
 //                                                                  niidmix_gnlenet_nll_grad_rows_f32
+//   model_gnlenet_mfma.inc  k_gnl_eval_mfma (conv2 / conv3 on the  niidmix_gnlenet_eval_rows_mfma_f32
+//                      fp32 matrix cores, 4 or 2 samples a tile)
 //   sampling.inc       k_draw_batches, k_epoch_perm_chunks /       niidmix_draw_batches_i32, _epoch_perm_i32,
 //                      _global / _finish, k_take_batches           _take_batches_i32
 //                      k_torch_randperm                            niidmix_torch_randperm_i32
@@ -4946,6 +4948,8 @@ __global__ __launch_bounds__(256) void k_lin_eval_sum(const int32_t *__restrict_
 
 #include "model_gnlenet.inc"
 
+#include "model_gnlenet_mfma.inc"
+
 #include "sampling.inc"
 
 // ----------------------------------------------------------------------------------------------
@@ -6367,12 +6371,21 @@ int64_t niidmix_gnlenet_eval_rows_scratch_bytes(int64_t n_jobs, int64_t max_len,
     return (n_work * 12 + 15) / 16 * 16 + gn_slots(g, n_work) * gn_act_floats(g) * 4;
 }
 
-int niidmix_gnlenet_eval_rows_f32(const float *theta, int64_t ld_t, const float *data,
-                                  const int32_t *labels, const int32_t *rows, const int32_t *seg_start,
-                                  const int32_t *seg_len, int64_t n_jobs, int64_t max_len,
-                                  double *loss_sum, int32_t *correct, int32_t *pred, int64_t ld_pred,
-                                  float *logits, int64_t ld_logits, int64_t Cin, int64_t H, int64_t W,
-                                  int64_t C, void *scratch, int64_t scratch_bytes, void *stream) {
+int64_t niidmix_gnlenet_eval_rows_mfma_scratch_bytes(int64_t n_jobs, int64_t max_len, int64_t Cin, int64_t H,
+                                                     int64_t W, int64_t C) {
+    if (n_jobs <= 0 || max_len <= 0 || !gn_supported(Cin, H, W, C)) return 0;
+    const int ts = gn_mfma_ts(gn_shape((int)Cin, (int)H, (int)W, (int)C));
+    // a double and an int32 per (job, tile of ts samples), to a multiple of 16 B; no activation slots
+    return ts ? (n_jobs * ((max_len + ts - 1) / ts) * 12 + 15) / 16 * 16 : 0;
+}
+
+// both GN-LeNet evaluation entry points: mfma picks k_gnl_eval_mfma, its tile and its tighter limit
+static int gn_eval_rows(bool mfma, const float *theta, int64_t ld_t, const float *data,
+                        const int32_t *labels, const int32_t *rows, const int32_t *seg_start,
+                        const int32_t *seg_len, int64_t n_jobs, int64_t max_len, double *loss_sum,
+                        int32_t *correct, int32_t *pred, int64_t ld_pred, float *logits, int64_t ld_logits,
+                        int64_t Cin, int64_t H, int64_t W, int64_t C, void *scratch, int64_t scratch_bytes,
+                        void *stream) {
     if (!theta || !data || !labels || !rows || !seg_start || !seg_len || !loss_sum || !correct || !scratch)
         return set_error(NIIDMIX_EINVAL, "null pointer");
     if (n_jobs <= 0 || Cin <= 0 || H <= 0 || W <= 0 || C <= 0)
@@ -6383,12 +6396,17 @@ int niidmix_gnlenet_eval_rows_f32(const float *theta, int64_t ld_t, const float 
     if (!gn_supported(Cin, H, W, C))
         return set_error(NIIDMIX_EUNSUPPORTED, "H %lld, W %lld: the kernel holds %d <= H, W <= %d",
                          (long long)H, (long long)W, kGnMinHW, kGnMaxHW);
-    if (max_len > 0x7fffffff) return set_error(NIIDMIX_EUNSUPPORTED, "max_len %lld: int32 segments", (long long)max_len);
     const GnShape g = gn_shape((int)Cin, (int)H, (int)W, (int)C);
+    const int ts = mfma ? gn_mfma_ts(g) : kGnTS;
+    if (!ts)
+        return set_error(NIIDMIX_EUNSUPPORTED, "H %lld, W %lld: the matrix-core kernel's tile of 2 "
+                         "samples does not fit in LDS", (long long)H, (long long)W);
+    if (max_len > 0x7fffffff) return set_error(NIIDMIX_EUNSUPPORTED, "max_len %lld: int32 segments", (long long)max_len);
     if (int rc = check_ld(ld_t, ld_t, g.P, "P")) return rc;
     if (pred && ld_pred < max_len) return set_error(NIIDMIX_EINVAL, "ld_pred < max_len");
     if (logits && ld_logits < max_len) return set_error(NIIDMIX_EINVAL, "ld_logits < max_len");
-    const int64_t need = niidmix_gnlenet_eval_rows_scratch_bytes(n_jobs, max_len, Cin, H, W, C);
+    const int64_t need = mfma ? niidmix_gnlenet_eval_rows_mfma_scratch_bytes(n_jobs, max_len, Cin, H, W, C)
+                              : niidmix_gnlenet_eval_rows_scratch_bytes(n_jobs, max_len, Cin, H, W, C);
     if (scratch_bytes < need || (reinterpret_cast<uintptr_t>(scratch) & 7u))
         return set_error(NIIDMIX_EINVAL, "scratch of %lld bytes (8-B aligned), %lld needed",
                          (long long)scratch_bytes, (long long)need);
@@ -6402,10 +6420,27 @@ int niidmix_gnlenet_eval_rows_f32(const float *theta, int64_t ld_t, const float 
         (logits && hits_theta(logits, ((n_jobs - 1) * ld_logits + max_len) * C * 4)) ||
         hits_theta(scratch, need))
         return set_error(NIIDMIX_EALIAS, "an output or the scratch buffer overlaps theta");
-    const int64_t n_tiles = gn_tiles(max_len), n_work = n_jobs * n_tiles;
+    const int64_t n_tiles = (max_len + ts - 1) / ts, n_work = n_jobs * n_tiles;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     double *part_loss = reinterpret_cast<double *>(scratch);
     int32_t *part_cnt = reinterpret_cast<int32_t *>(part_loss + n_work);
+    if (mfma) {
+        auto k1 = pick<4, 2>(ts, [](auto T) { return k_gnl_eval_mfma<T()>; });
+        auto k2 = pick<4, 2>(ts, [](auto T) { return k_lin_eval_sum<T()>; });
+        if (n_tiles > 0) {
+            const size_t lds = (size_t)gn_mfma_lds_bytes(g, ts);
+            if (lds > 64 * 1024)
+                if (int rc = lds_opt_in(k1, lds, "k_gnl_eval_mfma")) return rc;
+            hipLaunchKernelGGL(k1, dim3((unsigned)(n_work < kGnMaxGrid ? n_work : kGnMaxGrid)), dim3(256), lds,
+                               s, theta, ld_t, data, labels, rows, seg_start, seg_len, n_jobs, (int)max_len,
+                               (int)n_tiles, g, part_loss, part_cnt, pred, ld_pred, logits, ld_logits);
+            if (int rc = check_launch("k_gnl_eval_mfma")) return rc;
+        }
+        hipLaunchKernelGGL(k2, dim3((unsigned)((n_jobs + 255) / 256)), dim3(256), 0, s, seg_len, n_jobs,
+                           (int)max_len, (int)n_tiles, (const double *)part_loss,
+                           (const int32_t *)part_cnt, loss_sum, correct);
+        return check_launch("k_lin_eval_sum");
+    }
     if (n_tiles > 0) {
         const int64_t slots = gn_slots(g, n_work);
         float *act = reinterpret_cast<float *>(reinterpret_cast<char *>(scratch) + (n_work * 12 + 15) / 16 * 16);
@@ -6423,6 +6458,26 @@ int niidmix_gnlenet_eval_rows_f32(const float *theta, int64_t ld_t, const float 
                        seg_len, n_jobs, (int)max_len, (int)n_tiles, (const double *)part_loss,
                        (const int32_t *)part_cnt, loss_sum, correct);
     return check_launch("k_lin_eval_sum");
+}
+
+int niidmix_gnlenet_eval_rows_f32(const float *theta, int64_t ld_t, const float *data,
+                                  const int32_t *labels, const int32_t *rows, const int32_t *seg_start,
+                                  const int32_t *seg_len, int64_t n_jobs, int64_t max_len,
+                                  double *loss_sum, int32_t *correct, int32_t *pred, int64_t ld_pred,
+                                  float *logits, int64_t ld_logits, int64_t Cin, int64_t H, int64_t W,
+                                  int64_t C, void *scratch, int64_t scratch_bytes, void *stream) {
+    return gn_eval_rows(false, theta, ld_t, data, labels, rows, seg_start, seg_len, n_jobs, max_len, loss_sum,
+                        correct, pred, ld_pred, logits, ld_logits, Cin, H, W, C, scratch, scratch_bytes, stream);
+}
+
+int niidmix_gnlenet_eval_rows_mfma_f32(const float *theta, int64_t ld_t, const float *data,
+                                       const int32_t *labels, const int32_t *rows, const int32_t *seg_start,
+                                       const int32_t *seg_len, int64_t n_jobs, int64_t max_len,
+                                       double *loss_sum, int32_t *correct, int32_t *pred, int64_t ld_pred,
+                                       float *logits, int64_t ld_logits, int64_t Cin, int64_t H, int64_t W,
+                                       int64_t C, void *scratch, int64_t scratch_bytes, void *stream) {
+    return gn_eval_rows(true, theta, ld_t, data, labels, rows, seg_start, seg_len, n_jobs, max_len, loss_sum,
+                        correct, pred, ld_pred, logits, ld_logits, Cin, H, W, C, scratch, scratch_bytes, stream);
 }
 
 constexpr int64_t kGnGradMaxB = 1 << 24, kGnGradMaxRows = 1 << 24;

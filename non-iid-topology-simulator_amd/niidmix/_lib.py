@@ -112,6 +112,10 @@ SIGNATURES = {
     "niidmix_gnlenet_eval_rows_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64,
                                                      _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64,
                                                      _i64, _vp, _i64, _vp]),
+    "niidmix_gnlenet_eval_rows_mfma_scratch_bytes": (_i64, [_i64, _i64, _i64, _i64, _i64, _i64]),
+    "niidmix_gnlenet_eval_rows_mfma_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64,
+                                                          _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64,
+                                                          _i64, _vp, _i64, _vp]),
     "niidmix_gnlenet_nll_grad_rows_scratch_bytes": (_i64, [_i64, _i64, _i64, _i64, _i64, _i64]),
     "niidmix_gnlenet_nll_grad_rows_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64,
                                                          _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp,

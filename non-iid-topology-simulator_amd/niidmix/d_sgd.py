@@ -29,7 +29,9 @@ permutation in HBM, which lifts that flag's limit of 8192 samples per node, and
 --device-sampling-torch-stream fills that cache with the CPU path's own permutations (torch's
 stream restated on the device: the samples of a run without --device-sampling).
 With --device-evaluation (params['algorithm']['device-evaluation'], opt-in) the logger's accuracy
-and loss events of linear and GN-LeNet models are computed on the device as well (niidmix.evaluate).
+and loss events of linear and GN-LeNet models are computed on the device as well (niidmix.evaluate);
+--device-evaluation-mfma, with it, sends GN-LeNet's evaluation to the matrix-core kernel where that
+one takes the shape and is the faster one (niidmix.family).
 """
 import argparse
 import itertools
@@ -912,6 +914,8 @@ def init(nodes, topology, params):
     if params["algorithm"].get("device-evaluation"):
         from . import evaluate
         evaluate.check_eligible(nodes, params)            # refusals: ValueError naming the flag
+    elif params["algorithm"].get("device-evaluation-mfma"):
+        raise ValueError("--device-evaluation-mfma needs --device-evaluation")
     if params["algorithm"].get("device-training") or params["algorithm"].get("device-sampling") or \
             params["algorithm"].get("device-training-large-batch") or \
             params["algorithm"].get("device-sampling-torch-stream"):
@@ -1184,6 +1188,10 @@ def main(argv=None):
                          "accuracy and loss of every logged node (and of the global model) are "
                          "computed on the device (niidmix.evaluate); replaces Logger.state's ssh / "
                          "SLURM workers; within 1e-5 (condition-aware) of the CPU loops")
+    ap.add_argument("--device-evaluation-mfma", action="store_const", const=True, default=False,
+                    help="with --device-evaluation: GN-LeNet is evaluated by the kernel that runs "
+                         "conv2 / conv3 on the matrix cores (niidmix::gnlenet_eval_rows_mfma), at the "
+                         "shapes it takes and is measured faster at; the same bounds, other bits")
     ap.add_argument("--no-deferred-writeback", dest="deferred_writeback", action="store_false",
                     help="next_step returns only once every mixed row is back in the models (by "
                          "default it returns while they stream back, whenever the driver reads no "
@@ -1201,6 +1209,8 @@ def main(argv=None):
         ap.error("--device-sampling-cached needs --device-sampling")
     if args.device_sampling_torch_stream and not args.device_sampling:
         ap.error("--device-sampling-torch-stream needs --device-sampling")
+    if args.device_evaluation_mfma and not args.device_evaluation:
+        ap.error("--device-evaluation-mfma needs --device-evaluation")
     rundir = m.rundir(args)
     params = m.params(rundir)
     topology = load_topology(rundir)
@@ -1228,6 +1238,7 @@ def main(argv=None):
            or args.device_sampling_torch_stream else {}),
         **({"device-sampling-torch-stream": True} if args.device_sampling_torch_stream else {}),
         **({"device-evaluation": True} if args.device_evaluation else {}),
+        **({"device-evaluation-mfma": True} if args.device_evaluation_mfma else {}),
     })
     if args.rundir is None:
         print(rundir)

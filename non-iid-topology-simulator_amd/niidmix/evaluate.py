@@ -19,7 +19,9 @@ set for all nodes at once (niidmix::linear_eval_rows):
 
 The reference's other model, GN-LeNet (setup/model/gn_lenet.py: three 5 x 5 convolutions with
 GroupNorm(2), max-pooling and ReLU, then one Linear), goes through niidmix::gnlenet_eval_rows the
-same way.  Its parameters are read in place from a fresh single-stripe resident round's output slab
+same way, or through niidmix::gnlenet_eval_rows_mfma (conv2 / conv3 on the matrix cores) under
+--device-evaluation-mfma where niidmix.family's rule sends the shape; last_kernel names the kernel
+the last call took.  Its parameters are read in place from a fresh single-stripe resident round's output slab
 (niidmix.slab.ResidentRound, on its mixing stream), else stacked and uploaded; the job list of a
 call is cut (niidmix.train.cut_rows) so that the kernel's scratch stays within a fraction of the
 free HBM (a job's results do not depend on the cut).
@@ -48,6 +50,12 @@ SCRATCH_FRACTION = 0.8   # of the free HBM, for one call's scratch (DeviceTraine
 
 def enabled(params):
     return bool(params.get("algorithm", {}).get("device-evaluation"))
+
+
+def mfma_enabled(params):
+    """--device-evaluation-mfma: GN-LeNet goes to the matrix-core kernel where niidmix.family's
+    rule sends it."""
+    return bool(params.get("algorithm", {}).get("device-evaluation-mfma"))
 
 
 def chunk_jobs(offsets, chunk=CHUNK):
@@ -143,6 +151,8 @@ class DeviceEvaluator:
         self.device = torch.device(device) if device is not None else None
         self.sets = {}
         self.last_source = None          # "trainer" / "resident" (device slab read in place) or "stacked"
+        self.last_kernel = None          # the evaluation kernel the last call took (family.eval_kernel)
+        self.mfma = mfma_enabled(params)
         self.scratch_budget = None       # bytes of scratch per GN-LeNet call (None: SCRATCH_FRACTION
         self.last_calls = 0              # of the free HBM), and the calls the last job list took
         self._probed = set()             # (model class, kind, sizes) whose forward was probed
@@ -184,12 +194,20 @@ class DeviceEvaluator:
             raise ValueError(f"{FLAG}: {what} has a label outside [0, {c})")
         return fam.sizes(st.shape, shape, FLAG, what)
 
+    def _switch(self, fam):
+        """The family's kernel switch: GN-LeNet's `mfma` under --device-evaluation-mfma."""
+        return {"mfma": True} if self.mfma and fam is family.GN_LENET else {}
+
+    def _kernel(self, fam, sizes):
+        return fam.eval_kernel(sizes, **self._switch(fam)) if fam is family.GN_LENET else "k_lin_eval"
+
     def _probe(self, model, st, spec, sizes):
-        key = (type(model), spec[0].kind) + tuple(sizes)
+        key = (type(model), spec[0].kind, self._kernel(spec[0], sizes)) + tuple(sizes)
         if key in self._probed or st.probe is None:
             return
         try:
-            spec[0].probe_eval(model, st.probe[0], st.probe[1], self.params, self._dev(), sizes, FLAG)
+            spec[0].probe_eval(model, st.probe[0], st.probe[1], self.params, self._dev(), sizes, FLAG,
+                               **self._switch(spec[0]))
         except ValueError:
             raise
         except Exception as e:         # a forward that does not take these samples at all
@@ -238,7 +256,7 @@ class DeviceEvaluator:
         budget = self.scratch_budget
         if budget is None:
             budget = SCRATCH_FRACTION * torch.cuda.mem_get_info(dev)[0]
-        need = lambda k: fam.eval_scratch_bytes(k, max_len, sizes)  # noqa: E731
+        need = lambda k: fam.eval_scratch_bytes(k, max_len, sizes, **self._switch(fam))  # noqa: E731
         k = train.cut_rows(n, need, budget)
         if k is None:
             raise RuntimeError(f"{FLAG}: {need(1) / 2**30:.2f} GiB of scratch for one job of "
@@ -249,6 +267,7 @@ class DeviceEvaluator:
         dev, fam = theta.device, spec[0]
         with torch.cuda.device(dev), torch.cuda.stream(stream or torch.cuda.current_stream(dev)):
             n = len(rows)
+            self.last_kernel = self._kernel(fam, sizes)
             idx = torch.tensor([rows, start, length], dtype=torch.int32).to(dev)
             loss = torch.empty(n, dtype=torch.float64, device=dev)
             correct = torch.empty(n, dtype=torch.int32, device=dev)
@@ -259,7 +278,7 @@ class DeviceEvaluator:
             for a in starts:
                 b = min(n, a + cut)
                 fam.eval_rows(theta, st.data, st.labels, idx[0, a:b], idx[1, a:b], idx[2, a:b],
-                              max(length[a:b]), loss[a:b], correct[a:b], sizes)
+                              max(length[a:b]), loss[a:b], correct[a:b], sizes, **self._switch(fam))
             # read back on the same stream: a copy on another one would not wait for the kernel
             return loss.cpu().tolist(), correct.cpu().tolist()
 

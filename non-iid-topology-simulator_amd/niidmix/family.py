@@ -272,14 +272,34 @@ class _GNLeNet:
     def grad_rows(self, theta, data, labels, bi, bl, rows, grad, loss, sizes, large=False):
         ops.gnlenet_nll_grad_rows(theta, data, labels, bi, bl, rows, grad, loss, *sizes)
 
-    def eval_rows(self, theta, data, labels, rows, start, length, max_len, loss_sum, correct, sizes):
-        ops.gnlenet_eval_rows(theta, data, labels, rows, start, length, max_len, loss_sum, correct,
-                              None, None, *sizes)
+    # --device-evaluation-mfma's shape classes are the matrix-core kernel's tiles (ops.gn_mfma_tile):
+    # True where tools/gnlenet_eval_probe.py measured its median below k_gnl_eval's in the same run
+    # (tile 4 at 1 x 28 x 28, tile 2 at 3 x 32 x 32).  A class that is not
+    # keeps the existing kernel under the flag.
+    MFMA_FASTER = {4: True, 2: True}
+
+    def mfma(self, sizes, flag):
+        """Under --device-evaluation-mfma (`flag`) a call goes to the matrix-core op exactly when
+        that kernel takes the shape and is the measured faster one at its tile."""
+        return bool(flag) and self.MFMA_FASTER.get(ops.gn_mfma_tile(sizes[1], sizes[2]), False)
+
+    def eval_kernel(self, sizes, mfma=False):
+        return "k_gnl_eval_mfma" if self.mfma(sizes, mfma) else "k_gnl_eval"
+
+    def _eval_op(self, sizes, mfma):
+        return ops.gnlenet_eval_rows_mfma if self.mfma(sizes, mfma) else ops.gnlenet_eval_rows
+
+    def eval_rows(self, theta, data, labels, rows, start, length, max_len, loss_sum, correct, sizes,
+                  mfma=False):
+        self._eval_op(sizes, mfma)(theta, data, labels, rows, start, length, max_len, loss_sum,
+                                   correct, None, None, *sizes)
 
     def grad_scratch_bytes(self, rows, b_max, sizes, large=False):
         return int(lib.niidmix_gnlenet_nll_grad_rows_scratch_bytes(rows, b_max, *sizes))
 
-    def eval_scratch_bytes(self, jobs, max_len, sizes):
+    def eval_scratch_bytes(self, jobs, max_len, sizes, mfma=False):
+        if self.mfma(sizes, mfma):
+            return int(lib.niidmix_gnlenet_eval_rows_mfma_scratch_bytes(jobs, max_len, *sizes))
         return int(lib.niidmix_gnlenet_eval_rows_scratch_bytes(jobs, max_len, *sizes))
 
     _NOT_GN_LENET = ("the model's forward is not GN-LeNet's (5 x 5 convolutions of 32 / 32 / 64 "
@@ -318,10 +338,10 @@ class _GNLeNet:
                 f"forward + nll_loss + backward on the CPU (loss {loss:.6g}, worst gradient error "
                 f"{worst:.3g} of a tensor's largest element, bound 1e-3)")
 
-    def probe_eval(self, model, x, y, params, device, sizes, flag):
-        """The same for the evaluation kernel: require that its log-softmaxed logits on the
-        samples x agree with model.forward on the CPU within 1e-3 max(1, max |z|) (another
-        architecture differs by O(0.1))."""
+    def probe_eval(self, model, x, y, params, device, sizes, flag, mfma=False):
+        """The same for the evaluation kernel the run uses (`mfma`: --device-evaluation-mfma):
+        require that its log-softmaxed logits on the samples x agree with model.forward on the CPU
+        within 1e-3 max(1, max |z|) (another architecture differs by O(0.1))."""
         from . import d_sgd
         d_sgd.synchronize()
         nb, c = int(x.shape[0]), sizes[3]
@@ -330,9 +350,9 @@ class _GNLeNet:
         theta, data, labels, zero, bl = _one_row(model, x, y, self.P(self.shape(model)), device)
         dev = theta.device
         z = torch.zeros((1, nb, c), dtype=torch.float32, device=dev)
-        ops.gnlenet_eval_rows(theta, data, labels, zero, zero, bl, nb,
-                              torch.empty(1, dtype=torch.float64, device=dev),
-                              torch.empty(1, dtype=torch.int32, device=dev), None, z, *sizes)
+        self._eval_op(sizes, mfma)(theta, data, labels, zero, zero, bl, nb,
+                                   torch.empty(1, dtype=torch.float64, device=dev),
+                                   torch.empty(1, dtype=torch.int32, device=dev), None, z, *sizes)
         z = z[0].cpu()
         got = torch.log_softmax(z, 1)
         bound = 1e-3 * max(1.0, float(z.abs().max()))

@@ -43,6 +43,8 @@ Ops (registered in the `niidmix` namespace, usable as torch.ops.niidmix.*):
                                                     (the same for GN-LeNet, --device-training-gn-lenet)
   gnlenet_eval_rows(theta, data, labels, rows, seg_start, seg_len, max_len, loss_sum, correct, pred,
                     logits, Cin, H, W, C)           k_gnl_eval + k_lin_eval_sum (the same for GN-LeNet)
+  gnlenet_eval_rows_mfma(the same arguments)        k_gnl_eval_mfma + k_lin_eval_sum (conv2 / conv3 on
+                                                    the matrix cores, gn_mfma_tile(H, W) samples a tile)
   draw_batches(seed, rank, seg_start, seg_len, epoch, cursor, batch_idx, batch_len)
                                                     k_draw_batches (the training batches of a round,
                                                     in the gradient ops' layout, --device-sampling)
@@ -674,6 +676,8 @@ MAX_BC = 32768
 MAX_B_SLICED = 2 ** 20      # batch of niidmix::linear_nll_grad_rows_sliced, which has no MAX_BC
 GN_MAX_CIN, GN_MIN_HW, GN_MAX_HW = 4, 15, 64
 GN_CHANNELS = (32, 32, 64)          # output channels of GN-LeNet's three convolutions
+GN_LDS_MAX, GN_STAGE_FLOATS = 160 * 1024, 7200     # a workgroup's LDS; the weight stage in it
+GN_MFMA_WAVE_TILES = (7, 2)         # M-tiles of 32 positions a wave of k_gnl_eval_mfma holds: conv2, conv3
 
 
 def gnlenet_shapes(Cin, C, F):
@@ -693,6 +697,30 @@ def gnlenet_sizes(Cin, H, W, C):
         return (h - 3) // 2 + 1
     f = GN_CHANNELS[-1] * down(down(down(H))) * down(down(down(W)))
     return f, sum(math.prod(sh) for sh in gnlenet_shapes(Cin, C, f))
+
+
+def gn_mfma_tile(H, W):
+    """Samples per tile of niidmix::gnlenet_eval_rows_mfma on H x W inputs (csrc/
+    model_gnlenet_mfma.inc, gn_mfma_ts, restated): the most of 4 and 2 at which the weight stage,
+    the statistics and the one activation buffer -- the largest of conv2's input with its shared
+    zero halo, conv2's output plus conv3's halo'd input, conv3's output plus the features -- fit
+    in LDS and a wave holds its M-tiles' accumulators; 0 when the kernel does not take the shape."""
+    def down(h):
+        return (h - 3) // 2 + 1
+
+    def wave_tiles(m):
+        return ((m + 31) // 32 + 3) // 4
+    (h1, w1), (h2, w2) = (down(H), down(W)), (down(down(H)), down(down(W)))
+    h3, w3 = down(h2), down(w2)
+    for ts in (4, 2):
+        act = max(ts * 32 * (h1 + 2) * (w1 + 2) + 2 * (w1 + 2) + 2,
+                  ts * 32 * (h1 * w1 + (h2 + 2) * (w2 + 2)) + 2 * (w2 + 2) + 2,
+                  ts * 64 * (h2 * w2 + h3 * w3))
+        if 4 * (GN_STAGE_FLOATS + 16 + 2 * ts * 64 + act) <= GN_LDS_MAX and \
+                wave_tiles(ts * h1 * w1) <= GN_MFMA_WAVE_TILES[0] and \
+                wave_tiles(ts * h2 * w2) <= GN_MFMA_WAVE_TILES[1]:
+            return ts
+    return 0
 
 
 def _gnlenet_limits(Cin, H, W, C):
@@ -853,6 +881,29 @@ def linear_eval_rows(theta: torch.Tensor, data: torch.Tensor, labels: torch.Tens
     _lib.check(rc, "niidmix::linear_eval_rows")
 
 
+def _gnlenet_eval(name, theta, data, labels, rows, seg_start, seg_len, max_len, loss_sum, correct,
+                  pred, logits, Cin, H, W, C):
+    """The two GN-LeNet evaluation ops: `name` is the C entry point without its _f32."""
+    Cin, H, W, C, max_len = int(Cin), int(H), int(W), int(C), int(max_len)
+    _req(Cin >= 1 and H >= 1 and W >= 1 and C >= 1, "Cin, H, W and C must be >= 1")
+    _req(max_len >= 0, "max_len must be >= 0")
+    _gnlenet_limits(Cin, H, W, C)
+    p = gnlenet_sizes(Cin, H, W, C)[1]
+    n = _eval_rows_args(theta, data, labels, rows, seg_start, seg_len, max_len, loss_sum, correct,
+                        pred, logits, C, f"P = {p}", p, "Cin * H * W", Cin * H * W)
+    dev = theta.device
+    nbytes = max(16, int(getattr(_lib.lib, f"niidmix_{name}_scratch_bytes")(n, max_len, Cin, H, W, C)))
+    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    rc = getattr(_lib.lib, f"niidmix_{name}_f32")(
+        theta.data_ptr(), _ld(theta), data.data_ptr(), labels.data_ptr(), rows.data_ptr(),
+        seg_start.data_ptr(), seg_len.data_ptr(), n, max_len, loss_sum.data_ptr(), correct.data_ptr(),
+        pred.data_ptr() if pred is not None else None, _ld(pred) if pred is not None else 0,
+        logits.data_ptr() if logits is not None else None,
+        logits.shape[1] if logits is not None else 0,
+        Cin, H, W, C, scratch.data_ptr(), nbytes, _stream(theta))
+    _lib.check(rc, f"niidmix::{name}")
+
+
 @torch.library.custom_op("niidmix::gnlenet_eval_rows",
                          mutates_args=("loss_sum", "correct", "pred", "logits"))
 def gnlenet_eval_rows(theta: torch.Tensor, data: torch.Tensor, labels: torch.Tensor,
@@ -865,24 +916,23 @@ def gnlenet_eval_rows(theta: torch.Tensor, data: torch.Tensor, labels: torch.Ten
     seg_len[i]), data [S, Cin * H * W].  logits: None or fp32 [n_jobs, >= max_len, C], the
     classifier's output before log_softmax.  The scratch buffer comes from torch's caching
     allocator.  The index tensors' CONTENTS are not checked here."""
-    Cin, H, W, C, max_len = int(Cin), int(H), int(W), int(C), int(max_len)
-    _req(Cin >= 1 and H >= 1 and W >= 1 and C >= 1, "Cin, H, W and C must be >= 1")
-    _req(max_len >= 0, "max_len must be >= 0")
-    _gnlenet_limits(Cin, H, W, C)
-    p = gnlenet_sizes(Cin, H, W, C)[1]
-    n = _eval_rows_args(theta, data, labels, rows, seg_start, seg_len, max_len, loss_sum, correct,
-                        pred, logits, C, f"P = {p}", p, "Cin * H * W", Cin * H * W)
-    dev = theta.device
-    nbytes = max(16, int(_lib.lib.niidmix_gnlenet_eval_rows_scratch_bytes(n, max_len, Cin, H, W, C)))
-    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
-    rc = _lib.lib.niidmix_gnlenet_eval_rows_f32(
-        theta.data_ptr(), _ld(theta), data.data_ptr(), labels.data_ptr(), rows.data_ptr(),
-        seg_start.data_ptr(), seg_len.data_ptr(), n, max_len, loss_sum.data_ptr(), correct.data_ptr(),
-        pred.data_ptr() if pred is not None else None, _ld(pred) if pred is not None else 0,
-        logits.data_ptr() if logits is not None else None,
-        logits.shape[1] if logits is not None else 0,
-        Cin, H, W, C, scratch.data_ptr(), nbytes, _stream(theta))
-    _lib.check(rc, "niidmix::gnlenet_eval_rows")
+    _gnlenet_eval("gnlenet_eval_rows", theta, data, labels, rows, seg_start, seg_len, max_len,
+                  loss_sum, correct, pred, logits, Cin, H, W, C)
+
+
+@torch.library.custom_op("niidmix::gnlenet_eval_rows_mfma",
+                         mutates_args=("loss_sum", "correct", "pred", "logits"))
+def gnlenet_eval_rows_mfma(theta: torch.Tensor, data: torch.Tensor, labels: torch.Tensor,
+                           rows: torch.Tensor, seg_start: torch.Tensor, seg_len: torch.Tensor,
+                           max_len: int, loss_sum: torch.Tensor, correct: torch.Tensor,
+                           pred: Optional[torch.Tensor], logits: Optional[torch.Tensor],
+                           Cin: int, H: int, W: int, C: int) -> None:
+    """gnlenet_eval_rows with conv2 / conv3 on the matrix cores (include/niidmix.h,
+    niidmix_gnlenet_eval_rows_mfma_f32): the same arguments, outputs and bounds, other bits; a
+    workgroup takes gn_mfma_tile(H, W) samples, and a shape at which that is 0 is the launcher's
+    NIIDMIX_EUNSUPPORTED (there is no fallback to the other kernel here: niidmix.family routes)."""
+    _gnlenet_eval("gnlenet_eval_rows_mfma", theta, data, labels, rows, seg_start, seg_len, max_len,
+                  loss_sum, correct, pred, logits, Cin, H, W, C)
 
 
 @torch.library.custom_op("niidmix::gnlenet_nll_grad_rows", mutates_args=("grad", "loss"))
