@@ -818,6 +818,32 @@ int niidmix_gnlenet_nll_grad_rows_f32(const float *theta, int64_t ld_t, const fl
                                       int64_t Cin, int64_t H, int64_t W, int64_t C, void *scratch,
                                       int64_t scratch_bytes, void *stream);
 
+/* niidmix_gnlenet_nll_grad_rows_f32 with the weight gradients of conv2 and conv3 on the matrix
+ * cores (k_gnl_grad_wmfma; the drop-in's --device-training-gn-lenet-mfma).  Arguments, limits,
+ * scratch layout and size (niidmix_gnlenet_nll_grad_rows_scratch_bytes), checks and their order are
+ * those of niidmix_gnlenet_nll_grad_rows_f32, and no further shape is NIIDMIX_EUNSUPPORTED.  What
+ * differs:
+ *   conv2.w,  v_mfma_f32_32x32x2_f32 (fp32 in, fp32 accumulate): per row and per 32 output channels
+ *   conv3.w   one GEMM dW[co, (ci, tap)] = sum dY[s, co, y, x] Xpad[s, ci, y + ky - 2, x + kx - 2]
+ *             whose K runs over the samples in batch order, per sample over bands of map rows top
+ *             down (one band up to 15 x 15 maps) and in a band over the positions of the map with
+ *             two zero columns per row.  An output is ONE such chain over the whole batch, not a
+ *             chain per sample added in batch order: not bit-identical to the plain entry, the
+ *             same bound of 4 e32 (tests/test_gpu_train_gnlenet_mfma.py).
+ *   the rest  the other 12 tensors and the loss are the plain entry's, bit for bit.
+ *   NaN/inf   a non-finite conv2 / conv3 input activation also reaches the taps that the plain
+ *             entry's loop bounds keep it from at the border, through the zero halo (0 * inf).  It
+ *             stays in the rows whose parameters produced it.
+ * Determinism, independence of the other rows and of the cut of the row list, no atomics, theta
+ * not written: as niidmix_gnlenet_nll_grad_rows_f32. */
+int niidmix_gnlenet_nll_grad_rows_mfma_f32(const float *theta, int64_t ld_t, const float *data,
+                                           const int32_t *labels, const int32_t *batch_idx,
+                                           const int32_t *batch_len, int64_t b_max,
+                                           const int32_t *rows, int64_t n_rows, float *grad,
+                                           int64_t ld_g, float *loss, int64_t Cin, int64_t H, int64_t W,
+                                           int64_t C, void *scratch, int64_t scratch_bytes,
+                                           void *stream);
+
 /* Training batches drawn on the device (the drop-in's --device-sampling): job j writes the batch
  * that starts at position cursor[j] of epoch epoch[j]'s permutation of the segment
  * [seg_start[j], seg_start[j] + seg_len[j]) of the caller's concatenated data, in the layout

@@ -618,6 +618,9 @@ __global__ __launch_bounds__(256) void k_gnl_grad_sample(const float *__restrict
 
 constexpr int kGnMaxHW1 = ((kGnMaxHW - 3) / 2 + 1) * ((kGnMaxHW - 3) / 2 + 1);     // 31 x 31
 
+// W23 = false leaves conv2's and conv3's weight gradients to k_gnl_grad_wmfma
+// (model_gnlenet_grad_mfma.inc): their chain and its stores are dropped, nothing else.
+template <bool W23 = true>
 __global__ __launch_bounds__(256) void k_gnl_grad_conv(const float *__restrict__ data,
                                                        const int32_t *__restrict__ batch_idx,
                                                        const int32_t *__restrict__ batch_len, int b_max,
@@ -657,7 +660,7 @@ __global__ __launch_bounds__(256) void k_gnl_grad_conv(const float *__restrict__
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int e = tid + 256 * q;
-            if (e >= nel) continue;
+            if (e >= nel || (!W23 && layer != 1)) continue;
             const int ic = e / 25, ky = (e % 25) / 5, kx = e % 5;
             float acc = 0.f;
             if (layer == 1) {                                         // the input at the argmax positions
@@ -683,7 +686,7 @@ __global__ __launch_bounds__(256) void k_gnl_grad_conv(const float *__restrict__
     const int o_w = layer == 1 ? g.c1w : layer == 2 ? g.c2w : g.c3w;
 #pragma unroll
     for (int q = 0; q < 4; ++q)
-        if (tid + 256 * q < nel) gr[o_w + oc * nel + tid + 256 * q] = tot[q];
+        if (tid + 256 * q < nel && (W23 || layer == 1)) gr[o_w + oc * nel + tid + 256 * q] = tot[q];
     if (tid == 192) gr[o_w + CO * nel + oc] = btot;                   // the bias follows its weight
     if (tid == 0) {                                                   // GroupNorm's weight and bias
         float dg = 0.f, db = 0.f;

@@ -43,6 +43,8 @@
 //                                                                  niidmix_gnlenet_nll_grad_rows_f32
 //   model_gnlenet_mfma.inc  k_gnl_eval_mfma (conv2 / conv3 on the  niidmix_gnlenet_eval_rows_mfma_f32
 //                      fp32 matrix cores, 4 or 2 samples a tile)
+//   model_gnlenet_grad_mfma.inc  k_gnl_grad_wmfma (conv2 / conv3     niidmix_gnlenet_nll_grad_rows_mfma_f32
+//                      weight gradients on the matrix cores)
 //   sampling.inc       k_draw_batches, k_epoch_perm_chunks /       niidmix_draw_batches_i32, _epoch_perm_i32,
 //                      _global / _finish, k_take_batches           _take_batches_i32
 //                      k_torch_randperm                            niidmix_torch_randperm_i32
@@ -4949,6 +4951,7 @@ __global__ __launch_bounds__(256) void k_lin_eval_sum(const int32_t *__restrict_
 #include "model_gnlenet.inc"
 
 #include "model_gnlenet_mfma.inc"
+#include "model_gnlenet_grad_mfma.inc"
 
 #include "sampling.inc"
 
@@ -6496,12 +6499,13 @@ int64_t niidmix_gnlenet_nll_grad_rows_scratch_bytes(int64_t n_rows, int64_t b_ma
     return n_rows * gn_tiles(b_max) * gn_grad_lay(g).tile * 4;
 }
 
-int niidmix_gnlenet_nll_grad_rows_f32(const float *theta, int64_t ld_t, const float *data,
-                                      const int32_t *labels, const int32_t *batch_idx,
-                                      const int32_t *batch_len, int64_t b_max, const int32_t *rows,
-                                      int64_t n_rows, float *grad, int64_t ld_g, float *loss,
-                                      int64_t Cin, int64_t H, int64_t W, int64_t C, void *scratch,
-                                      int64_t scratch_bytes, void *stream) {
+// both GN-LeNet gradient entry points: mfma takes conv2's and conv3's weight gradients out of
+// k_gnl_grad_conv and gives them to k_gnl_grad_wmfma
+static int gn_grad_rows(bool mfma, const float *theta, int64_t ld_t, const float *data,
+                        const int32_t *labels, const int32_t *batch_idx, const int32_t *batch_len,
+                        int64_t b_max, const int32_t *rows, int64_t n_rows, float *grad, int64_t ld_g,
+                        float *loss, int64_t Cin, int64_t H, int64_t W, int64_t C, void *scratch,
+                        int64_t scratch_bytes, void *stream) {
     if (!theta || !data || !labels || !batch_idx || !batch_len || !rows || !grad || !loss || !scratch)
         return set_error(NIIDMIX_EINVAL, "null pointer");
     if (n_rows <= 0 || b_max <= 0 || Cin <= 0 || H <= 0 || W <= 0 || C <= 0)
@@ -6538,12 +6542,43 @@ int niidmix_gnlenet_nll_grad_rows_f32(const float *theta, int64_t ld_t, const fl
                        dim3(256), (size_t)gn_lds_bytes_global(), s, theta, ld_t, data, labels, batch_idx,
                        batch_len, (int)b_max, rows, n_rows, (int)n_tiles, g, L, sc);
     if (int rc = check_launch("k_gnl_grad_sample")) return rc;
-    hipLaunchKernelGGL(k_gnl_grad_conv, dim3((unsigned)(n_rows * 128)), dim3(256), 0, s, data, batch_idx,
+    if (mfma) {                                  // the units: n_rows of conv2, then 2 n_rows of conv3
+        const GnWmGeom q2 = gn_wm_geom(g.h1, g.w1), q3 = gn_wm_geom(g.h2, g.w2);
+        const size_t lds = 4 * (size_t)(gn_wm_lds_floats(q2) > gn_wm_lds_floats(q3) ? gn_wm_lds_floats(q2)
+                                                                                    : gn_wm_lds_floats(q3));
+        if (lds > 64 * 1024)
+            if (int rc = lds_opt_in(k_gnl_grad_wmfma, lds, "k_gnl_grad_wmfma")) return rc;
+        hipLaunchKernelGGL(k_gnl_grad_wmfma, dim3((unsigned)(n_rows * 3)), dim3(256), lds, s, batch_len,
+                           (int)b_max, rows, (int)n_rows, (int)n_tiles, g, L, (const float *)sc, grad, ld_g);
+        if (int rc = check_launch("k_gnl_grad_wmfma")) return rc;
+    }
+    auto kc = pick<true, false>(!mfma, [](auto W23) { return k_gnl_grad_conv<W23()>; });
+    hipLaunchKernelGGL(kc, dim3((unsigned)(n_rows * 128)), dim3(256), 0, s, data, batch_idx,
                        batch_len, (int)b_max, rows, (int)n_tiles, g, L, (const float *)sc, grad, ld_g);
     if (int rc = check_launch("k_gnl_grad_conv")) return rc;
     hipLaunchKernelGGL(k_gnl_grad_fc, dim3((unsigned)(n_rows * n_blk)), dim3(256), 0, s, batch_len,
                        (int)b_max, rows, (int)n_tiles, (int)n_blk, g, L, (const float *)sc, grad, ld_g, loss);
     return check_launch("k_gnl_grad_fc");
+}
+
+int niidmix_gnlenet_nll_grad_rows_f32(const float *theta, int64_t ld_t, const float *data,
+                                      const int32_t *labels, const int32_t *batch_idx,
+                                      const int32_t *batch_len, int64_t b_max, const int32_t *rows,
+                                      int64_t n_rows, float *grad, int64_t ld_g, float *loss,
+                                      int64_t Cin, int64_t H, int64_t W, int64_t C, void *scratch,
+                                      int64_t scratch_bytes, void *stream) {
+    return gn_grad_rows(false, theta, ld_t, data, labels, batch_idx, batch_len, b_max, rows, n_rows, grad,
+                        ld_g, loss, Cin, H, W, C, scratch, scratch_bytes, stream);
+}
+
+int niidmix_gnlenet_nll_grad_rows_mfma_f32(const float *theta, int64_t ld_t, const float *data,
+                                           const int32_t *labels, const int32_t *batch_idx,
+                                           const int32_t *batch_len, int64_t b_max, const int32_t *rows,
+                                           int64_t n_rows, float *grad, int64_t ld_g, float *loss,
+                                           int64_t Cin, int64_t H, int64_t W, int64_t C, void *scratch,
+                                           int64_t scratch_bytes, void *stream) {
+    return gn_grad_rows(true, theta, ld_t, data, labels, batch_idx, batch_len, b_max, rows, n_rows, grad,
+                        ld_g, loss, Cin, H, W, C, scratch, scratch_bytes, stream);
 }
 
 int64_t niidmix_draw_batches_max_len(void) { return kDrawMaxLen; }

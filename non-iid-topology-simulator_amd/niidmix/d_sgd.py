@@ -21,7 +21,8 @@ Gradient averaging (--clique-gradient, --unbiased-gradient) also runs on the GPU
 (niidmix.gradient); local training, optimizer steps and sampling stay on the CPU as in the reference.
 With --device-training (params['algorithm']['device-training'], opt-in) a linear model's local
 training runs on the device too: gradient, step and mixing never leave HBM (niidmix.train);
---device-training-gn-lenet does the same for GN-LeNet models, and --device-training-sample for
+--device-training-gn-lenet does the same for GN-LeNet models (--device-training-gn-lenet-mfma, with
+it, takes two of its weight gradients from a matrix-core kernel), and --device-training-sample for
 rounds of the 'sample' topology (the other two flags refuse it).  --device-sampling, with any of
 the three, draws the batches on the device too, from a sample stream of the plugin's own
 (niidmix.sampling) instead of one DataLoader per node; --device-sampling-cached keeps every epoch's
@@ -918,6 +919,7 @@ def init(nodes, topology, params):
         raise ValueError("--device-evaluation-mfma needs --device-evaluation")
     if params["algorithm"].get("device-training") or params["algorithm"].get("device-sampling") or \
             params["algorithm"].get("device-training-large-batch") or \
+            params["algorithm"].get("device-training-gn-lenet-mfma") or \
             params["algorithm"].get("device-sampling-torch-stream"):
         from . import train
         train.check_eligible(nodes, params, topology)     # refusals: ValueError naming the flag
@@ -1146,6 +1148,11 @@ def main(argv=None):
                          "keys): forward, loss and backward of every node in HIP kernels; same "
                          "samples as the CPU path, gradients within 4 x the error of torch's own "
                          "fp32 autograd, not bit-identical")
+    ap.add_argument("--device-training-gn-lenet-mfma", action="store_const", const=True, default=False,
+                    help="with --device-training-gn-lenet: conv2's and conv3's weight gradients come "
+                         "from the kernel on the matrix cores (niidmix::gnlenet_nll_grad_rows_mfma), at "
+                         "the shapes it is measured faster at; the same bound, other bits in those "
+                         "two tensors only")
     ap.add_argument("--device-training-sample", action="store_const", const=True, default=False,
                     help="--device-training for runs of the 'sample' topology (sets both keys; "
                          "the other two flags refuse 'sample'): each round the sampled nodes train "
@@ -1211,6 +1218,8 @@ def main(argv=None):
         ap.error("--device-sampling-torch-stream needs --device-sampling")
     if args.device_evaluation_mfma and not args.device_evaluation:
         ap.error("--device-evaluation-mfma needs --device-evaluation")
+    if args.device_training_gn_lenet_mfma and not args.device_training_gn_lenet:
+        ap.error("--device-training-gn-lenet-mfma needs --device-training-gn-lenet")
     rundir = m.rundir(args)
     params = m.params(rundir)
     topology = load_topology(rundir)
@@ -1231,6 +1240,7 @@ def main(argv=None):
         **({"device-training": True} if args.device_training or args.device_training_gn_lenet
            or args.device_training_sample else {}),
         **({"device-training-gn-lenet": True} if args.device_training_gn_lenet else {}),
+        **({"device-training-gn-lenet-mfma": True} if args.device_training_gn_lenet_mfma else {}),
         **({"device-training-sample": True} if args.device_training_sample else {}),
         **({"device-training-large-batch": True} if args.device_training_large_batch else {}),
         **({"device-sampling": True} if args.device_sampling else {}),

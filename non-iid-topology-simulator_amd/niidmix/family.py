@@ -269,8 +269,27 @@ class _GNLeNet:
                              f"features, the model's classifier takes F = {f}")
         return cin, h, w, c
 
-    def grad_rows(self, theta, data, labels, bi, bl, rows, grad, loss, sizes, large=False):
-        ops.gnlenet_nll_grad_rows(theta, data, labels, bi, bl, rows, grad, loss, *sizes)
+    # --device-training-gn-lenet-mfma's shape classes are the two layouts of k_gnl_grad_wmfma's
+    # conv2 stage (grad_mfma_class): True where tools/device_training_probe.py gn-kernel measured
+    # the call's median below the plain call's by more than the plain call's own spread in the same
+    # run.  A class that is not keeps the plain op under the flag.
+    GRAD_MFMA_FASTER = {"map": True, "bands": False}       # "bands": not measured
+
+    @staticmethod
+    def grad_mfma_class(sizes):
+        """"map" where conv2's whole pooled map and its gradient fit one stage of the weight-gradient
+        kernel (pooled maps with (2 h1 + 4)(w1 + 2) <= about 620: inputs up to 32 x 32), else "bands"."""
+        h1, w1 = (sizes[1] - 3) // 2 + 1, (sizes[2] - 3) // 2 + 1
+        return "map" if 32 * ((((h1 + 4) * (w1 + 2)) | 1) + ((h1 * (w1 + 2)) | 1)) + 8 <= 19968 else "bands"
+
+    def grad_mfma(self, sizes, flag):
+        """Under --device-training-gn-lenet-mfma (`flag`) a call goes to the matrix-core op exactly
+        when that op is the measured faster one at the shape's class."""
+        return bool(flag) and self.GRAD_MFMA_FASTER[self.grad_mfma_class(sizes)]
+
+    def grad_rows(self, theta, data, labels, bi, bl, rows, grad, loss, sizes, large=False, mfma=False):
+        op = ops.gnlenet_nll_grad_rows_mfma if self.grad_mfma(sizes, mfma) else ops.gnlenet_nll_grad_rows
+        op(theta, data, labels, bi, bl, rows, grad, loss, *sizes)
 
     # --device-evaluation-mfma's shape classes are the matrix-core kernel's tiles (ops.gn_mfma_tile):
     # True where tools/gnlenet_eval_probe.py measured its median below k_gnl_eval's in the same run
@@ -294,8 +313,8 @@ class _GNLeNet:
         self._eval_op(sizes, mfma)(theta, data, labels, rows, start, length, max_len, loss_sum,
                                    correct, None, None, *sizes)
 
-    def grad_scratch_bytes(self, rows, b_max, sizes, large=False):
-        return int(lib.niidmix_gnlenet_nll_grad_rows_scratch_bytes(rows, b_max, *sizes))
+    def grad_scratch_bytes(self, rows, b_max, sizes, large=False, mfma=False):
+        return int(lib.niidmix_gnlenet_nll_grad_rows_scratch_bytes(rows, b_max, *sizes))   # both ops'
 
     def eval_scratch_bytes(self, jobs, max_len, sizes, mfma=False):
         if self.mfma(sizes, mfma):

@@ -41,6 +41,9 @@ Ops (registered in the `niidmix` namespace, usable as torch.ops.niidmix.*):
   gnlenet_nll_grad_rows(theta, data, labels, batch_idx, batch_len, rows, grad, loss, Cin, H, W, C)
                                                     k_gnl_grad_sample + k_gnl_grad_conv + k_gnl_grad_fc
                                                     (the same for GN-LeNet, --device-training-gn-lenet)
+  gnlenet_nll_grad_rows_mfma(the same arguments)    the same with k_gnl_grad_wmfma for conv2's and
+                                                    conv3's weight gradients (the matrix cores,
+                                                    --device-training-gn-lenet-mfma)
   gnlenet_eval_rows(theta, data, labels, rows, seg_start, seg_len, max_len, loss_sum, correct, pred,
                     logits, Cin, H, W, C)           k_gnl_eval + k_lin_eval_sum (the same for GN-LeNet)
   gnlenet_eval_rows_mfma(the same arguments)        k_gnl_eval_mfma + k_lin_eval_sum (conv2 / conv3 on
@@ -935,17 +938,8 @@ def gnlenet_eval_rows_mfma(theta: torch.Tensor, data: torch.Tensor, labels: torc
                   loss_sum, correct, pred, logits, Cin, H, W, C)
 
 
-@torch.library.custom_op("niidmix::gnlenet_nll_grad_rows", mutates_args=("grad", "loss"))
-def gnlenet_nll_grad_rows(theta: torch.Tensor, data: torch.Tensor, labels: torch.Tensor,
-                          batch_idx: torch.Tensor, batch_len: torch.Tensor, rows: torch.Tensor,
-                          grad: torch.Tensor, loss: torch.Tensor,
-                          Cin: int, H: int, W: int, C: int) -> None:
-    """linear_nll_grad_rows for GN-LeNet (include/niidmix.h, niidmix_gnlenet_nll_grad_rows_f32): row
-    r of theta holds the model's 14 parameter tensors (P columns); batch_idx[i] lists the
-    batch_len[i] samples of data [S, Cin * H * W] / labels that rows[i] trains on; grad gets
-    F.nll_loss(forward(x), y).backward()'s gradient in the same layout, loss the mean batch loss.
-    The scratch buffer comes from torch's caching allocator.  The index tensors' CONTENTS are not
-    checked here (niidmix.train.DeviceTrainer checks them once)."""
+def _gnlenet_grad(name, theta, data, labels, batch_idx, batch_len, rows, grad, loss, Cin, H, W, C):
+    """The two GN-LeNet gradient ops: `name` is the C entry point without its niidmix_ and _f32."""
     Cin, H, W, C = int(Cin), int(H), int(W), int(C)
     _req(Cin >= 1 and H >= 1 and W >= 1 and C >= 1, "Cin, H, W and C must be >= 1")
     _gnlenet_limits(Cin, H, W, C)
@@ -957,11 +951,38 @@ def gnlenet_nll_grad_rows(theta: torch.Tensor, data: torch.Tensor, labels: torch
     dev, b_max = theta.device, batch_idx.shape[1]
     nbytes = max(16, int(_lib.lib.niidmix_gnlenet_nll_grad_rows_scratch_bytes(n, b_max, Cin, H, W, C)))
     scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
-    rc = _lib.lib.niidmix_gnlenet_nll_grad_rows_f32(
+    rc = getattr(_lib.lib, f"niidmix_{name}_f32")(
         theta.data_ptr(), _ld(theta), data.data_ptr(), labels.data_ptr(), batch_idx.data_ptr(),
         batch_len.data_ptr(), b_max, rows.data_ptr(), n, grad.data_ptr(), _ld(grad), loss.data_ptr(),
         Cin, H, W, C, scratch.data_ptr(), nbytes, _stream(theta))
-    _lib.check(rc, "niidmix::gnlenet_nll_grad_rows")
+    _lib.check(rc, f"niidmix::{name}")
+
+
+@torch.library.custom_op("niidmix::gnlenet_nll_grad_rows", mutates_args=("grad", "loss"))
+def gnlenet_nll_grad_rows(theta: torch.Tensor, data: torch.Tensor, labels: torch.Tensor,
+                          batch_idx: torch.Tensor, batch_len: torch.Tensor, rows: torch.Tensor,
+                          grad: torch.Tensor, loss: torch.Tensor,
+                          Cin: int, H: int, W: int, C: int) -> None:
+    """linear_nll_grad_rows for GN-LeNet (include/niidmix.h, niidmix_gnlenet_nll_grad_rows_f32): row
+    r of theta holds the model's 14 parameter tensors (P columns); batch_idx[i] lists the
+    batch_len[i] samples of data [S, Cin * H * W] / labels that rows[i] trains on; grad gets
+    F.nll_loss(forward(x), y).backward()'s gradient in the same layout, loss the mean batch loss.
+    The scratch buffer comes from torch's caching allocator.  The index tensors' CONTENTS are not
+    checked here (niidmix.train.DeviceTrainer checks them once)."""
+    _gnlenet_grad("gnlenet_nll_grad_rows", theta, data, labels, batch_idx, batch_len, rows, grad, loss,
+                  Cin, H, W, C)
+
+
+@torch.library.custom_op("niidmix::gnlenet_nll_grad_rows_mfma", mutates_args=("grad", "loss"))
+def gnlenet_nll_grad_rows_mfma(theta: torch.Tensor, data: torch.Tensor, labels: torch.Tensor,
+                               batch_idx: torch.Tensor, batch_len: torch.Tensor, rows: torch.Tensor,
+                               grad: torch.Tensor, loss: torch.Tensor,
+                               Cin: int, H: int, W: int, C: int) -> None:
+    """gnlenet_nll_grad_rows with conv2's and conv3's weight gradients on the matrix cores
+    (include/niidmix.h, niidmix_gnlenet_nll_grad_rows_mfma_f32): the same arguments, checks, scratch
+    and bound; those two tensors in another summation order, everything else bit for bit."""
+    _gnlenet_grad("gnlenet_nll_grad_rows_mfma", theta, data, labels, batch_idx, batch_len, rows, grad,
+                  loss, Cin, H, W, C)
 
 
 def draw_batches_max_len():

@@ -24,7 +24,9 @@ niidmix::gnlenet_nll_grad_rows as its gradient op, under a flag of its own,
 `--device-training-gn-lenet` (which also sets 'device-training'; the plain flag keeps refusing
 GN-LeNet).  The kernel's scratch is about 180 KB per sample, so the row list of a round is cut into
 several calls when one call's scratch would exceed a budget (a row's bits do not depend on the
-cut).
+cut).  `--device-training-gn-lenet-mfma`, valid only with that flag, swaps the gradient op for
+niidmix::gnlenet_nll_grad_rows_mfma (conv2's and conv3's weight gradients on the matrix cores)
+where niidmix.family's rule sends the shape; nothing else of the round changes.
 
 What depends on the model family -- shapes, the kernels' limits, the sample check, the gradient op
 and its scratch, the forward probe -- is niidmix.family's; DeviceTrainer holds a family and its
@@ -122,6 +124,7 @@ from .topology import to_csr
 
 FLAG = "--device-training"
 FLAG_GN = "--device-training-gn-lenet"
+FLAG_GN_MFMA = "--device-training-gn-lenet-mfma"
 FLAG_SAMPLE = "--device-training-sample"
 FLAG_SAMPLING = "--device-sampling"
 FLAG_CACHED = "--device-sampling-cached"
@@ -145,6 +148,12 @@ def enabled(params):
 
 def gn_enabled(params):
     return bool(params.get("algorithm", {}).get("device-training-gn-lenet"))
+
+
+def gn_mfma_enabled(params):
+    """--device-training-gn-lenet-mfma: GN-LeNet's gradient goes to the op with conv2's and conv3's
+    weight gradients on the matrix cores where niidmix.family's rule sends the shape."""
+    return bool(params.get("algorithm", {}).get("device-training-gn-lenet-mfma"))
 
 
 def sample_run(params):
@@ -329,6 +338,8 @@ def check_eligible(nodes, params, topology=None):
         raise ValueError(f"{FLAG_SAMPLING} draws the batches of a device-training round: it needs one "
                          f"of {FLAG}, {FLAG_GN} or {FLAG_SAMPLE}")
     gn_flag = gn_enabled(params)
+    if gn_mfma_enabled(params) and not gn_flag:
+        raise ValueError(f"{FLAG_GN_MFMA} needs {FLAG_GN}")
     flag = flag_of(params)
     sample = sample_run(params)
     large = large_enabled(params)
@@ -412,6 +423,8 @@ class DeviceTrainer:
         self.cached = cached_enabled(params)
         self.torch_stream = torch_stream_enabled(params)
         self.large = large_enabled(params)           # batches beyond ops.MAX_BC: the sliced op
+        # the family's kernel switch: GN-LeNet's `mfma` under --device-training-gn-lenet-mfma
+        self.switch = {"mfma": True} if gn_mfma_enabled(params) and self.family is family.GN_LENET else {}
         self.scratch_budget = None      # bytes of scratch per GN-LeNet gradient call (None:
         self.last_calls = 0              # SCRATCH_FRACTION of the free HBM); calls of the last round
         self.sizes = None                # the kernel's size arguments (family.sizes), set by _materialise
@@ -512,7 +525,7 @@ class DeviceTrainer:
                                f"{free / 2**30:.1f} GiB of free HBM")
 
     def _gn_need(self, rows):
-        return self.family.grad_scratch_bytes(rows, self.b_max, self.sizes, self.large)
+        return self.family.grad_scratch_bytes(rows, self.b_max, self.sizes, self.large, **self.switch)
 
     def _budget(self):
         """Bytes of scratch one call may take: scratch_budget when set, else SCRATCH_FRACTION of the
@@ -548,7 +561,7 @@ class DeviceTrainer:
         for a in range(0, n, cut):
             b = min(n, a + cut)
             self.family.grad_rows(x, self.data, self.labels, bi[a:b], bl[a:b], rows[a:b],
-                                  self.grad, self.loss[a:b], self.sizes, self.large)
+                                  self.grad, self.loss[a:b], self.sizes, self.large, **self.switch)
             self.last_calls += 1
 
     def _step(self, x):

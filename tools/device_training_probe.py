@@ -18,13 +18,16 @@
 
 GN-LeNet (niidmix_gnlenet_nll_grad_rows_f32, --device-training-gn-lenet), at the two shapes
     gn-cifar   N 1000, 3 x 32 x 32, C 10, B 20     gn-mnist   N 100, 1 x 28 x 28, C 10, B 128
-  gn-kernel  the gradient call against three yardsticks, all four alternating within every
+  gn-kernel  the gradient call and niidmix_gnlenet_nll_grad_rows_mfma_f32 (grad_mfma; conv2's and
+             conv3's weight gradients on the matrix cores) against three yardsticks, all five alternating within every
              repetition: the CPU loop (forward + nll_loss + backward of the module, torch's
              threads as set, on a few nodes, scaled to N), torch autograd on the device (the
              same module, looped over a few nodes, scaled to N), and niidmix_stream_copy_f32 over
              the bytes the call must read (parameters and batch samples).  Device candidates by
              device events, the CPU loop by the host clock.
-  gn-rounds  as `rounds`, for GN-LeNet models and the --device-training-gn-lenet flag.
+  gn-rounds  as `rounds`, for GN-LeNet models and the --device-training-gn-lenet flag; with
+             --gn-mfma the device run sets --device-training-gn-lenet-mfma as well (a process holds
+             one live trainer, so base and new flag are two invocations).
 
     python tools/device_training_probe.py gn-kernel --shape gn-cifar [--warmup 5] [--reps 20]
     python tools/device_training_probe.py gn-rounds --shape gn-mnist [--warmup 2] [--rounds 10]
@@ -136,8 +139,8 @@ def gn_kernel(a):
     read = n * p + n * b * k                           # floats the call must read
     src, dst = torch.empty(read - read % 4, device=dev), torch.empty(read - read % 4, device=dev)
 
-    def grad_call():
-        _lib.check(lib.niidmix_gnlenet_nll_grad_rows_f32(
+    def grad_call(entry=lib.niidmix_gnlenet_nll_grad_rows_f32):
+        _lib.check(entry(
             theta.data_ptr(), ld, data.data_ptr(), labels.data_ptr(), idx.data_ptr(), blen.data_ptr(),
             b, rows.data_ptr(), n, grad.data_ptr(), ld, loss.data_ptr(), cin, h, w, c,
             scratch.data_ptr(), nbytes, strm), "grad")
@@ -156,6 +159,7 @@ def gn_kernel(a):
     mdl_dev = copy.deepcopy(mdl).to(dev)
     xc, yc = xb[:n_cpu].cpu(), yb[:n_cpu].cpu()
     cands = [("copy", copy_call, 1.0, True), ("grad", grad_call, 1.0, True),
+             ("grad_mfma", lambda: grad_call(lib.niidmix_gnlenet_nll_grad_rows_mfma_f32), 1.0, True),
              ("device_autograd", lambda: loop(mdl_dev, xb, yb, n_dev), n / n_dev, True),
              ("cpu_loop", lambda: loop(mdl, xc, yc, n_cpu), n / n_cpu, False)]
     times = {name: [] for name, _, _, _ in cands}
@@ -182,6 +186,11 @@ def gn_kernel(a):
         out[name] = {"median_ms": statistics.median(t) * 1e3, "min_ms": min(t) * 1e3, "max_ms": max(t) * 1e3}
     for name in ("copy", "device_autograd", "cpu_loop"):
         out["grad_over_" + name] = out["grad"]["median_ms"] / out[name]["median_ms"]
+    # the acceptance rule of family.GN_LENET.GRAD_MFMA_FASTER: below the plain call's median by more
+    # than the plain call's own spread
+    out["grad_mfma_over_grad"] = out["grad_mfma"]["median_ms"] / out["grad"]["median_ms"]
+    out["grad_mfma_faster"] = out["grad"]["median_ms"] - out["grad_mfma"]["median_ms"] > \
+        out["grad"]["max_ms"] - out["grad"]["min_ms"]
     print(json.dumps(out))
 
 
@@ -353,6 +362,9 @@ def rounds(a):
         x = x.reshape(per_node, cin, h, w)
     y = torch.randint(0, c, (per_node,), generator=g)
     runs = {}
+    if gn and a.gn_mfma:                     # time the matrix-core op whatever the family's rule says
+        from niidmix import family
+        family.GN_LENET.GRAD_MFMA_FASTER = dict.fromkeys(family.GN_LENET.GRAD_MFMA_FASTER, True)
     for flag in (False, True):
         torch.manual_seed(7)
         params = {"meta": {"log": "WARNING", "seed": 7}, "model": {"input-size": k},
@@ -365,6 +377,8 @@ def rounds(a):
                                 "mixing-mode": a.mode, "device-training": flag}}
         if gn and flag:
             params["algorithm"]["device-training-gn-lenet"] = True
+        if gn and flag and a.gn_mfma:
+            params["algorithm"]["device-training-gn-lenet-mfma"] = True
         ts = [(x[j], int(y[j])) for j in range(per_node)]
         nodes = []
         for r in range(n):
@@ -384,7 +398,7 @@ def rounds(a):
             if rnd >= a.warmup:
                 times.append(dt)
     out = {"step": "gn-rounds" if gn else "rounds", "shape": a.shape, "n": n, "k": k, "c": c, "b": b, "mode": a.mode,
-           "clique_gradient": a.clique_gradient, "momentum": a.momentum,
+           "clique_gradient": a.clique_gradient, "momentum": a.momentum, "gn_mfma": bool(gn and a.gn_mfma),
            "warmup": a.warmup, "rounds": a.rounds, "threads": torch.get_num_threads(),
            "device": torch.cuda.get_device_name(0)}
     for flag, key in ((False, "flag_off"), (True, "flag_on")):
@@ -586,6 +600,8 @@ def main():
     ap.add_argument("--clique-gradient", action="store_true",
                     help="rounds / gn-rounds: both paths average the cliques' gradients")
     ap.add_argument("--momentum", type=float, default=0.0, help="rounds / gn-rounds: --learning-momentum")
+    ap.add_argument("--gn-mfma", action="store_true",
+                    help="gn-rounds: the device run also sets --device-training-gn-lenet-mfma")
     a = ap.parse_args()
     if a.step == "all":
         return run_all(a)
