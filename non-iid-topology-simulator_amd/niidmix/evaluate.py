@@ -28,7 +28,7 @@ free HBM (a job's results do not depend on the cut).
 
 What depends on the model family -- shapes, limits, the sample check, the evaluation op and its
 scratch, the forward probe -- is niidmix.family's; DeviceEvaluator calls through the family of the
-models it is given.
+models it is given and that family's evaluation plan, which binds the kernel variant.
 
 Not bit-identical to the CPU loops (another summation order; tests/test_gpu_eval.py and
 tests/test_gpu_eval_gnlenet.py state the bounds), so the path is opt-in.  A model that is neither
@@ -151,7 +151,7 @@ class DeviceEvaluator:
         self.device = torch.device(device) if device is not None else None
         self.sets = {}
         self.last_source = None          # "trainer" / "resident" (device slab read in place) or "stacked"
-        self.last_kernel = None          # the evaluation kernel the last call took (family.eval_kernel)
+        self.last_kernel = None          # the evaluation kernel the last call took (its plan's `kernel`)
         self.mfma = mfma_enabled(params)
         self.scratch_budget = None       # bytes of scratch per GN-LeNet call (None: SCRATCH_FRACTION
         self.last_calls = 0              # of the free HBM), and the calls the last job list took
@@ -194,20 +194,17 @@ class DeviceEvaluator:
             raise ValueError(f"{FLAG}: {what} has a label outside [0, {c})")
         return fam.sizes(st.shape, shape, FLAG, what)
 
-    def _switch(self, fam):
-        """The family's kernel switch: GN-LeNet's `mfma` under --device-evaluation-mfma."""
-        return {"mfma": True} if self.mfma and fam is family.GN_LENET else {}
-
-    def _kernel(self, fam, sizes):
-        return fam.eval_kernel(sizes, **self._switch(fam)) if fam is family.GN_LENET else "k_lin_eval"
+    def _plan(self, fam, sizes):
+        """The family's evaluation call, its kernel variant bound (--device-evaluation-mfma)."""
+        return fam.eval_plan(sizes, self.mfma)
 
     def _probe(self, model, st, spec, sizes):
-        key = (type(model), spec[0].kind, self._kernel(spec[0], sizes)) + tuple(sizes)
+        plan = self._plan(spec[0], sizes)
+        key = (type(model), spec[0].kind, plan.kernel) + tuple(sizes)
         if key in self._probed or st.probe is None:
             return
         try:
-            spec[0].probe_eval(model, st.probe[0], st.probe[1], self.params, self._dev(), sizes, FLAG,
-                               **self._switch(spec[0]))
+            spec[0].probe_eval(model, st.probe[0], st.probe[1], self.params, self._dev(), plan, FLAG)
         except ValueError:
             raise
         except Exception as e:         # a forward that does not take these samples at all
@@ -248,37 +245,32 @@ class DeviceEvaluator:
         self.last_source = "stacked"
         return theta, list(range(len(models))), spec, None
 
-    def _cut(self, fam, n, max_len, sizes, dev):
-        """Jobs per call of the family's kernel: all of them for a family whose calls are not cut,
-        else as many as keep the call's scratch within the budget (train.cut_rows)."""
-        if not fam.cut:
-            return n
-        budget = self.scratch_budget
-        if budget is None:
-            budget = SCRATCH_FRACTION * torch.cuda.mem_get_info(dev)[0]
-        need = lambda k: fam.eval_scratch_bytes(k, max_len, sizes, **self._switch(fam))  # noqa: E731
-        k = train.cut_rows(n, need, budget)
-        if k is None:
-            raise RuntimeError(f"{FLAG}: {need(1) / 2**30:.2f} GiB of scratch for one job of "
-                               f"{max_len} samples exceed the budget of {budget / 2**30:.2f} GiB")
-        return k
+    def _cut(self, plan, n, max_len, dev):
+        """Jobs per call of the plan's kernel over n jobs of up to max_len samples (train.cut_calls);
+        the budget is scratch_budget, else SCRATCH_FRACTION of the HBM free at this call."""
+        def budget():
+            if self.scratch_budget is not None:
+                return self.scratch_budget
+            return SCRATCH_FRACTION * torch.cuda.mem_get_info(dev)[0]
+        return train.cut_calls(plan, n, lambda k: plan.scratch_bytes(k, max_len), budget, FLAG,
+                               f"job of {max_len}")
 
     def _run(self, theta, st, rows, start, length, spec, sizes, stream=None):
-        dev, fam = theta.device, spec[0]
+        dev, plan = theta.device, self._plan(spec[0], sizes)
         with torch.cuda.device(dev), torch.cuda.stream(stream or torch.cuda.current_stream(dev)):
             n = len(rows)
-            self.last_kernel = self._kernel(fam, sizes)
+            self.last_kernel = plan.kernel
             idx = torch.tensor([rows, start, length], dtype=torch.int32).to(dev)
             loss = torch.empty(n, dtype=torch.float64, device=dev)
             correct = torch.empty(n, dtype=torch.int32, device=dev)
-            cut = self._cut(fam, n, max(length), sizes, dev)
+            cut = self._cut(plan, n, max(length), dev)
             starts = range(0, n, cut)
-            if fam.cut:                  # as it was: a list that is never cut leaves the count alone
+            if plan.cut:                 # as it was: a list that is never cut leaves the count alone
                 self.last_calls = len(starts)
             for a in starts:
                 b = min(n, a + cut)
-                fam.eval_rows(theta, st.data, st.labels, idx[0, a:b], idx[1, a:b], idx[2, a:b],
-                              max(length[a:b]), loss[a:b], correct[a:b], sizes, **self._switch(fam))
+                plan(theta, st.data, st.labels, idx[0, a:b], idx[1, a:b], idx[2, a:b],
+                     max(length[a:b]), loss[a:b], correct[a:b])
             # read back on the same stream: a copy on another one would not wait for the kernel
             return loss.cpu().tolist(), correct.cpu().tolist()
 

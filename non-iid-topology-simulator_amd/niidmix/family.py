@@ -1,17 +1,24 @@
 """The model families of the device paths: what depends on WHICH model niidmix.train trains or
 niidmix.evaluate evaluates, stated once.  LINEAR (setup/model/linear.py: one nn.Linear(K, C),
-log_softmax) and GN_LENET (setup/model/gn_lenet.py) have the same methods; family_of(model) picks
-one from the parameters' shapes.  A family knows its shape(model) -- (K, C) / (Cin, C, F), C is
+log_softmax) and GN_LENET (setup/model/gn_lenet.py) have the same methods, apart from each one's own
+routing rule (LINEAR.sliced; GN_LENET.grad_mfma, grad_mfma_class, mfma); family_of(model) picks one
+from the parameters' shapes.  A family knows its shape(model) -- (K, C) / (Cin, C, F), C is
 shape[1] in both -- and P(shape); the kernels' limits as refusals (the constants are niidmix.ops',
 which checks its arguments against the same ones); sizes(), the one sample check, giving the
-kernel's size arguments (K, C) / (Cin, H, W, C); its gradient and evaluation op and their scratch
-in bytes behind one signature; whether a call's row list may be cut; and the forward probes.
-GN-LeNet's row layout is ops.gnlenet_shapes, one table: the expected shapes, the offsets, the row
-splitter, P and F follow from it.  The float64 yardsticks of the probes and of the GPU tests live
-here as well.
+kernel's size arguments (K, C) / (Cin, H, W, C); its gradient and evaluation calls, as plans
+(below); whether a call's row list may be cut; and the forward probes.  GN-LeNet's row layout is
+ops.gnlenet_shapes, one table: the expected shapes, the offsets, the row splitter, P and F follow
+from it.  The float64 yardsticks of the probes and of the GPU tests live here as well.
+
+The kernel variant is bound once, in a plan: grad_plan(sizes, b_max, large=False, mfma=False) and
+eval_plan(sizes, mfma=False) apply the family's rule, reading its table then, to the opt-in switches
+(`large`: --device-training-large-batch; `mfma`: --device-training-gn-lenet-mfma /
+--device-evaluation-mfma) and return a GradPlan / EvalPlan.  A family ignores a switch that is not
+its own (LINEAR `mfma`, GN_LENET `large`), so the callers pass every switch to either family.
 """
 import copy
 import math
+from dataclasses import dataclass
 
 import torch
 import torch.nn.functional as F
@@ -119,6 +126,44 @@ def fp64_reference_gn_lenet(theta_row, x, y):
     return reference_gn_lenet(theta_row, x, y, torch.float64)
 
 
+# the plans
+@dataclass(frozen=True)
+class GradPlan:
+    """A family's gradient call with its kernel variant bound (grad_plan): `op` is the niidmix.ops
+    function, `cut` the family's, scratch_bytes(rows) one call's scratch.  The variant and the
+    scratch were decided for index blocks of b_max columns, so the call refuses any other."""
+    op: object
+    cut: bool
+    sizes: tuple
+    b_max: int
+    scratch_bytes: object
+
+    def __call__(self, theta, data, labels, bi, bl, rows, grad, loss):
+        if tuple(bi.shape[1:]) != (self.b_max,):
+            raise ValueError(f"an index block of shape {tuple(bi.shape)} for a gradient plan made for "
+                             f"b_max = {self.b_max}")
+        self.op(theta, data, labels, bi, bl, rows, grad, loss, *self.sizes)
+
+
+@dataclass(frozen=True)
+class EvalPlan:
+    """A family's evaluation call with its kernel variant bound (eval_plan): `op`, the name of its
+    `kernel`, `cut`, scratch_bytes(jobs, max_len).  `takes_logits`: the op has a logits output."""
+    op: object
+    kernel: str
+    cut: bool
+    sizes: tuple
+    scratch_bytes: object
+    takes_logits: bool
+
+    def __call__(self, theta, data, labels, rows, start, length, max_len, loss_sum, correct, pred=None,
+                 logits=None):
+        if logits is not None and not self.takes_logits:
+            raise ValueError(f"{self.kernel} has no logits output")
+        out = (pred, logits) if self.takes_logits else (pred,)
+        self.op(theta, data, labels, rows, start, length, max_len, loss_sum, correct, *out, *self.sizes)
+
+
 # what the probes share
 def _one_row(model, x, y, p, device):
     """A probe's one-row, one-job setup: (theta [1, P] padded as the trainer pads its slabs and
@@ -150,7 +195,7 @@ def _kernel_grad(fam, mdl, x, y, sizes, device):
     grad = torch.zeros((1, theta.stride(0)), dtype=torch.float32, device=dev)[:, :p]    # padded alike
     out = torch.empty(1, dtype=torch.float32, device=dev)
     bi = torch.arange(nb, dtype=torch.int32, device=dev).reshape(1, nb)
-    fam.grad_rows(theta, data, labels, bi, bl, zero, grad, out, sizes)
+    fam.grad_plan(sizes, nb)(theta, data, labels, bi, bl, zero, grad, out)
     return grad[0].cpu(), float(out[0])
 
 
@@ -193,22 +238,19 @@ class _Linear:
         the existing kernel does not take its shape."""
         return bool(large) and b_max * sizes[1] > MAX_BC
 
-    def grad_rows(self, theta, data, labels, bi, bl, rows, grad, loss, sizes, large=False):
-        op = ops.linear_nll_grad_rows_sliced if self.sliced(bi.shape[1], sizes, large) else \
-            ops.linear_nll_grad_rows
-        op(theta, data, labels, bi, bl, rows, grad, loss, *sizes)
+    def grad_plan(self, sizes, b_max, large=False, mfma=False):
+        if self.sliced(b_max, sizes, large):         # the scratch sizes are in fp32 elements
+            op, dims = ops.linear_nll_grad_rows_sliced, sizes
+            elems = lib.niidmix_linear_nll_grad_rows_sliced_scratch_elems
+        else:
+            op, dims = ops.linear_nll_grad_rows, sizes[1:]
+            elems = lib.niidmix_linear_nll_grad_rows_scratch_elems
+        return GradPlan(op, self.cut, sizes, b_max, lambda rows: 4 * int(elems(rows, b_max, *dims)))
 
-    def eval_rows(self, theta, data, labels, rows, start, length, max_len, loss_sum, correct, sizes):
-        ops.linear_eval_rows(theta, data, labels, rows, start, length, max_len, loss_sum, correct,
-                             None, *sizes)
-
-    def grad_scratch_bytes(self, rows, b_max, sizes, large=False):
-        if self.sliced(b_max, sizes, large):
-            return 4 * int(lib.niidmix_linear_nll_grad_rows_sliced_scratch_elems(rows, b_max, *sizes))
-        return 4 * int(lib.niidmix_linear_nll_grad_rows_scratch_elems(rows, b_max, sizes[1]))  # fp32 elements
-
-    def eval_scratch_bytes(self, jobs, max_len, sizes):
-        return int(lib.niidmix_linear_eval_rows_scratch_bytes(jobs, max_len, sizes[1]))
+    def eval_plan(self, sizes, mfma=False):
+        scratch = lib.niidmix_linear_eval_rows_scratch_bytes
+        return EvalPlan(ops.linear_eval_rows, "k_lin_eval", self.cut, sizes,
+                        lambda jobs, max_len: int(scratch(jobs, max_len, sizes[1])), False)
 
     def probe_grad(self, model, x, y, params, device, sizes, flag, whose="the"):
         """Require that model.forward + nll_loss + backward on the CPU agree with the gradient
@@ -230,7 +272,9 @@ class _Linear:
                 f"forward + nll_loss + backward on the CPU (loss {float(loss):.6g}, worst gradient "
                 f"ratio {float((dg / a.clamp_min(1e-300)).max()):.3g} of the bound)")
 
-    probe_eval = probe_grad      # the evaluation kernel computes the gradient kernel's forward
+    def probe_eval(self, model, x, y, params, device, plan, flag):
+        """The evaluation kernel computes the gradient kernel's forward: probe_grad."""
+        self.probe_grad(model, x, y, params, device, plan.sizes, flag)
 
 
 class _GNLeNet:
@@ -287,9 +331,10 @@ class _GNLeNet:
         when that op is the measured faster one at the shape's class."""
         return bool(flag) and self.GRAD_MFMA_FASTER[self.grad_mfma_class(sizes)]
 
-    def grad_rows(self, theta, data, labels, bi, bl, rows, grad, loss, sizes, large=False, mfma=False):
+    def grad_plan(self, sizes, b_max, large=False, mfma=False):
         op = ops.gnlenet_nll_grad_rows_mfma if self.grad_mfma(sizes, mfma) else ops.gnlenet_nll_grad_rows
-        op(theta, data, labels, bi, bl, rows, grad, loss, *sizes)
+        scratch = lib.niidmix_gnlenet_nll_grad_rows_scratch_bytes       # both ops'
+        return GradPlan(op, self.cut, sizes, b_max, lambda rows: int(scratch(rows, b_max, *sizes)))
 
     # --device-evaluation-mfma's shape classes are the matrix-core kernel's tiles (ops.gn_mfma_tile):
     # True where tools/gnlenet_eval_probe.py measured its median below k_gnl_eval's in the same run
@@ -302,24 +347,15 @@ class _GNLeNet:
         that kernel takes the shape and is the measured faster one at its tile."""
         return bool(flag) and self.MFMA_FASTER.get(ops.gn_mfma_tile(sizes[1], sizes[2]), False)
 
-    def eval_kernel(self, sizes, mfma=False):
-        return "k_gnl_eval_mfma" if self.mfma(sizes, mfma) else "k_gnl_eval"
-
-    def _eval_op(self, sizes, mfma):
-        return ops.gnlenet_eval_rows_mfma if self.mfma(sizes, mfma) else ops.gnlenet_eval_rows
-
-    def eval_rows(self, theta, data, labels, rows, start, length, max_len, loss_sum, correct, sizes,
-                  mfma=False):
-        self._eval_op(sizes, mfma)(theta, data, labels, rows, start, length, max_len, loss_sum,
-                                   correct, None, None, *sizes)
-
-    def grad_scratch_bytes(self, rows, b_max, sizes, large=False, mfma=False):
-        return int(lib.niidmix_gnlenet_nll_grad_rows_scratch_bytes(rows, b_max, *sizes))   # both ops'
-
-    def eval_scratch_bytes(self, jobs, max_len, sizes, mfma=False):
+    def eval_plan(self, sizes, mfma=False):
         if self.mfma(sizes, mfma):
-            return int(lib.niidmix_gnlenet_eval_rows_mfma_scratch_bytes(jobs, max_len, *sizes))
-        return int(lib.niidmix_gnlenet_eval_rows_scratch_bytes(jobs, max_len, *sizes))
+            op, kernel, scratch = (ops.gnlenet_eval_rows_mfma, "k_gnl_eval_mfma",
+                                   lib.niidmix_gnlenet_eval_rows_mfma_scratch_bytes)
+        else:
+            op, kernel, scratch = (ops.gnlenet_eval_rows, "k_gnl_eval",
+                                   lib.niidmix_gnlenet_eval_rows_scratch_bytes)
+        return EvalPlan(op, kernel, self.cut, sizes, lambda jobs, max_len: int(scratch(jobs, max_len, *sizes)),
+                        True)
 
     _NOT_GN_LENET = ("the model's forward is not GN-LeNet's (5 x 5 convolutions of 32 / 32 / 64 "
                      "channels, GroupNorm(2), conv-pool-norm then conv-norm-pool twice, one Linear)")
@@ -357,21 +393,20 @@ class _GNLeNet:
                 f"forward + nll_loss + backward on the CPU (loss {loss:.6g}, worst gradient error "
                 f"{worst:.3g} of a tensor's largest element, bound 1e-3)")
 
-    def probe_eval(self, model, x, y, params, device, sizes, flag, mfma=False):
-        """The same for the evaluation kernel the run uses (`mfma`: --device-evaluation-mfma):
-        require that its log-softmaxed logits on the samples x agree with model.forward on the CPU
-        within 1e-3 max(1, max |z|) (another architecture differs by O(0.1))."""
+    def probe_eval(self, model, x, y, params, device, plan, flag):
+        """The same for the evaluation kernel the run uses (`plan`, its eval_plan): require that
+        its log-softmaxed logits on the samples x agree with model.forward on the CPU within
+        1e-3 max(1, max |z|) (another architecture differs by O(0.1))."""
         from . import d_sgd
         d_sgd.synchronize()
-        nb, c = int(x.shape[0]), sizes[3]
+        nb, c = int(x.shape[0]), plan.sizes[3]
         with torch.no_grad():
             want = model.forward(x, params).detach().to(torch.float32)
         theta, data, labels, zero, bl = _one_row(model, x, y, self.P(self.shape(model)), device)
         dev = theta.device
         z = torch.zeros((1, nb, c), dtype=torch.float32, device=dev)
-        self._eval_op(sizes, mfma)(theta, data, labels, zero, zero, bl, nb,
-                                   torch.empty(1, dtype=torch.float64, device=dev),
-                                   torch.empty(1, dtype=torch.int32, device=dev), None, z, *sizes)
+        plan(theta, data, labels, zero, zero, bl, nb, torch.empty(1, dtype=torch.float64, device=dev),
+             torch.empty(1, dtype=torch.int32, device=dev), logits=z)
         z = z[0].cpu()
         got = torch.log_softmax(z, 1)
         bound = 1e-3 * max(1.0, float(z.abs().max()))

@@ -29,9 +29,10 @@ niidmix::gnlenet_nll_grad_rows_mfma (conv2's and conv3's weight gradients on the
 where niidmix.family's rule sends the shape; nothing else of the round changes.
 
 What depends on the model family -- shapes, the kernels' limits, the sample check, the gradient op
-and its scratch, the forward probe -- is niidmix.family's; DeviceTrainer holds a family and its
-`sizes` and calls through them.  This module keeps what is about the run: the flags, eligibility,
-the averaging lists, sampling, the slabs' padding and the cut of a row list (cut_rows).
+and its scratch, the forward probe -- is niidmix.family's; DeviceTrainer holds a family, its
+`sizes` and the family's gradient plan (the kernel variant bound once) and calls through them.
+This module keeps what is about the run: the flags, eligibility, the averaging lists, sampling, the
+slabs' padding and the cut of a row list (cut_rows, cut_calls).
 
 Gradient averaging (--clique-gradient, --unbiased-gradient; d_sgd.py:47-94) runs under both flags,
 between the gradient op and the mixing, on the lists of niidmix.gradient.build_grad_plan:
@@ -406,6 +407,20 @@ def cut_rows(n, need, budget):
     return k
 
 
+def cut_calls(plan, n, need, budget, flag, one):
+    """Rows per call of `plan`'s kernel over n jobs, for both device paths: all of them when the
+    plan's calls are not cut, else cut_rows of need(rows) under budget() bytes (read only then); a
+    RuntimeError naming `flag` when `one`, a single row or job with its sample count, does not fit."""
+    if not plan.cut:
+        return n
+    limit = budget()
+    k = cut_rows(n, need, limit)
+    if k is None:
+        raise RuntimeError(f"{flag}: {need(1) / 2**30:.2f} GiB of scratch for one {one} samples exceed "
+                           f"the budget of {limit / 2**30:.2f} GiB")
+    return k
+
+
 class DeviceTrainer:
     """Data, parameters, gradients (and momentum) of one node list in HBM, and the round above."""
 
@@ -423,8 +438,6 @@ class DeviceTrainer:
         self.cached = cached_enabled(params)
         self.torch_stream = torch_stream_enabled(params)
         self.large = large_enabled(params)           # batches beyond ops.MAX_BC: the sliced op
-        # the family's kernel switch: GN-LeNet's `mfma` under --device-training-gn-lenet-mfma
-        self.switch = {"mfma": True} if gn_mfma_enabled(params) and self.family is family.GN_LENET else {}
         self.scratch_budget = None      # bytes of scratch per GN-LeNet gradient call (None:
         self.last_calls = 0              # SCRATCH_FRACTION of the free HBM); calls of the last round
         self.sizes = None                # the kernel's size arguments (family.sizes), set by _materialise
@@ -448,6 +461,8 @@ class DeviceTrainer:
         # the per-row kinds average into a slab of their own; the clique kind needs none
         self.n_buf = 3 + (self.momentum != 0.0) + (self.grad_kind in ("clique-removed", "unbiased"))
         xs, ys, self.offsets = self._materialise(nodes)
+        # the gradient call, its kernel variant bound for the trainer's life
+        self.plan = self.family.grad_plan(self.sizes, self.b_max, self.large, gn_mfma_enabled(params))
         self._check_fit(xs)
         dev = self.device
         self.data = xs.to(dev)
@@ -513,7 +528,7 @@ class DeviceTrainer:
         n_buf = self.n_buf
         need = n_buf * self.n * self.ld * 4 + xs.numel() * 4
         # where calls are cut, one row's scratch at least: _cut sizes the calls every round
-        need += self._gn_need(1 if self.family.cut else self.n)
+        need += self.plan.scratch_bytes(1 if self.plan.cut else self.n)
         if self.cached:      # the permutation cache, and the sort's scratch for the longest row alone
             longest = max(b - a for a, b in zip(self.offsets, self.offsets[1:]))
             need += self.offsets[-1] * 4
@@ -523,9 +538,6 @@ class DeviceTrainer:
             raise RuntimeError(f"{self.flag}: {need / 2**30:.1f} GiB of device buffers ({n_buf} slabs of "
                                f"[{self.n}, {self.p}], the train-sets, scratch) do not fit in "
                                f"{free / 2**30:.1f} GiB of free HBM")
-
-    def _gn_need(self, rows):
-        return self.family.grad_scratch_bytes(rows, self.b_max, self.sizes, self.large, **self.switch)
 
     def _budget(self):
         """Bytes of scratch one call may take: scratch_budget when set, else SCRATCH_FRACTION of the
@@ -537,17 +549,9 @@ class DeviceTrainer:
         return self._free_budget
 
     def _cut(self, n):
-        """Rows per call of the gradient kernel over n jobs: all of them for a family whose calls
-        are not cut, else as many as keep the call's scratch within the budget."""
-        if not self.family.cut:
-            return n
-        budget = self._budget()
-        k = cut_rows(n, self._gn_need, budget)
-        if k is None:
-            raise RuntimeError(f"{self.flag}: {self._gn_need(1) / 2**30:.2f} GiB of scratch for one "
-                               f"row of {self.b_max} samples exceed the budget of "
-                               f"{budget / 2**30:.2f} GiB")
-        return k
+        """Rows per call of the gradient kernel over n jobs (cut_calls)."""
+        return cut_calls(self.plan, n, self.plan.scratch_bytes, self._budget, self.flag,
+                         f"row of {self.b_max}")
 
     def _gradient(self, x, rows=None):
         """Gradient and loss of the rows `rows` of x (default: every row) on this round's batches
@@ -560,8 +564,7 @@ class DeviceTrainer:
         self.last_calls = 0
         for a in range(0, n, cut):
             b = min(n, a + cut)
-            self.family.grad_rows(x, self.data, self.labels, bi[a:b], bl[a:b], rows[a:b],
-                                  self.grad, self.loss[a:b], self.sizes, self.large, **self.switch)
+            self.plan(x, self.data, self.labels, bi[a:b], bl[a:b], rows[a:b], self.grad, self.loss[a:b])
             self.last_calls += 1
 
     def _step(self, x):

@@ -78,11 +78,15 @@ def test_family_routing_rule(monkeypatch):
         sizes = (3, *hw, 10)
         want = bool(ts) and fam.MFMA_FASTER[ts]
         assert fam.mfma(sizes, True) == want and not fam.mfma(sizes, False)
-        assert fam.eval_kernel(sizes, True) == ("k_gnl_eval_mfma" if want else "k_gnl_eval")
-        assert fam._eval_op(sizes, True) is (ops.gnlenet_eval_rows_mfma if want else ops.gnlenet_eval_rows)
+        flagged, plain = fam.eval_plan(sizes, mfma=True), fam.eval_plan(sizes)
+        assert flagged.kernel == ("k_gnl_eval_mfma" if want else "k_gnl_eval") and plain.kernel == "k_gnl_eval"
+        assert flagged.op is (ops.gnlenet_eval_rows_mfma if want else ops.gnlenet_eval_rows)
+        assert plain.op is ops.gnlenet_eval_rows
         old = lib.niidmix_gnlenet_eval_rows_scratch_bytes(5, 100, *sizes)
         new = lib.niidmix_gnlenet_eval_rows_mfma_scratch_bytes(5, 100, *sizes)
-        assert fam.eval_scratch_bytes(5, 100, sizes) == old
-        assert fam.eval_scratch_bytes(5, 100, sizes, mfma=True) == (new if want else old)
+        assert plain.scratch_bytes(5, 100) == old
+        assert flagged.scratch_bytes(5, 100) == (new if want else old)
     monkeypatch.setattr(fam, "MFMA_FASTER", {4: True, 2: False})      # a class measured slower
     assert fam.mfma((1, 28, 28, 10), True) and not fam.mfma((3, 32, 32, 10), True)
+    assert fam.eval_plan((1, 28, 28, 10), mfma=True).kernel == "k_gnl_eval_mfma"      # read when made
+    assert fam.eval_plan((3, 32, 32, 10), mfma=True).kernel == "k_gnl_eval"

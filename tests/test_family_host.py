@@ -278,22 +278,125 @@ def test_cut_rows_is_the_only_cut(monkeypatch):
     sizes, max_len = (1, 28, 28, 10), 50
     asked = []
 
-    def scratch(jobs, ml, sz):
+    def scratch(jobs, ml, *sz):
         asked.append((ml, sz))
         return 1024 + 4096 * jobs * ml
-    monkeypatch.setattr(family.GN_LENET, "eval_scratch_bytes", scratch)
+    # what the evaluation plans ask for their scratch
+    monkeypatch.setattr(family.lib, "niidmix_gnlenet_eval_rows_scratch_bytes", scratch)
     need = lambda k: 1024 + 4096 * k * max_len  # noqa: E731
     ev = evaluate.DeviceEvaluator({}, device="cpu")
+    plan = ev._plan(family.GN_LENET, sizes)
     for n in (1, 2, 7, 1000):
         for fits, want in ((n, n), ((n + 1) // 2, (n + 1) // 2), (1, 1)):
             ev.scratch_budget = need(fits)
-            got = ev._cut(family.GN_LENET, n, max_len, sizes, None)
+            got = ev._cut(plan, n, max_len, None)
             assert got == train.cut_rows(n, need, ev.scratch_budget) == want, (n, fits)
     assert asked and set(asked) == {(max_len, sizes)}
     ev.scratch_budget = need(1) - 1
     assert train.cut_rows(7, need, ev.scratch_budget) is None
-    with pytest.raises(RuntimeError, match="device-evaluation"):
-        ev._cut(family.GN_LENET, 7, max_len, sizes, None)
-    monkeypatch.setattr(family.LINEAR, "eval_scratch_bytes", scratch)
+    with pytest.raises(RuntimeError, match=r"^--device-evaluation: 0\.00 GiB of scratch for one job of 50 "
+                                           r"samples exceed the budget of 0\.00 GiB$"):
+        ev._cut(plan, 7, max_len, None)
+    monkeypatch.setattr(family.lib, "niidmix_linear_eval_rows_scratch_bytes", scratch)
     del asked[:]
-    assert ev._cut(family.LINEAR, 1000, max_len, (784, 10), None) == 1000 and not asked
+    assert ev._cut(ev._plan(family.LINEAR, (784, 10)), 1000, max_len, None) == 1000 and not asked
+
+
+def test_cut_calls_is_both_paths_refusal():
+    """train.cut_calls, which both _cut methods call: a plan that is not cut reads no budget; the
+    refusal names the flag and the one row or job, in the words both paths had."""
+    from niidmix import family, train
+    need = lambda k: (1 << 30) * k  # noqa: E731
+    lin, gn = family.LINEAR.grad_plan((6, 4), 3), family.GN_LENET.grad_plan((1, 15, 15, 3), 3)
+    assert train.cut_calls(lin, 9, need, None, "--flag", "row of 3") == 9
+    assert train.cut_calls(gn, 9, need, lambda: 3 << 30, "--flag", "row of 3") == 3
+    with pytest.raises(RuntimeError, match=r"^--flag: 1\.00 GiB of scratch for one row of 3 samples "
+                                           r"exceed the budget of 0\.50 GiB$"):
+        train.cut_calls(gn, 9, need, lambda: 1 << 29, "--flag", "row of 3")
+
+
+# ------------------------------------------------------------------------------------------------
+RULES = {"linear": {"sliced"}, "gn-lenet": {"grad_mfma", "grad_mfma_class", "mfma"}}
+
+
+def test_both_families_expose_the_same_callables():
+    """Apart from each family's own routing rule, which its plans apply."""
+    from niidmix import family
+    names = [{n for n in dir(fam) if not n.startswith("_") and callable(getattr(fam, n))} - RULES[fam.kind]
+             for fam in (family.LINEAR, family.GN_LENET)]
+    assert names[0] == names[1] == {"shape", "P", "limits", "sizes", "grad_plan", "eval_plan",
+                                    "probe_grad", "probe_eval"}
+    for fam in (family.LINEAR, family.GN_LENET):
+        assert RULES[fam.kind] <= set(dir(fam))
+
+
+def test_a_family_ignores_the_other_familys_switch(monkeypatch):
+    from niidmix import family, ops
+    lin, gn = family.LINEAR, family.GN_LENET
+    b = ops.MAX_BC // 4 + 1
+    for mfma in (False, True):
+        plan = lin.grad_plan((6, 4), b, large=True, mfma=mfma)
+        assert plan.op is ops.linear_nll_grad_rows_sliced and not plan.cut
+        elems = family.lib.niidmix_linear_nll_grad_rows_sliced_scratch_elems(2, b, 6, 4)
+        assert plan.scratch_bytes(2) == 4 * elems
+    assert lin.grad_plan((6, 4), 3, large=True, mfma=True).op is ops.linear_nll_grad_rows
+    assert lin.eval_plan((6, 4), mfma=True).op is ops.linear_eval_rows
+    assert lin.eval_plan((6, 4), mfma=True).kernel == lin.eval_plan((6, 4)).kernel == "k_lin_eval"
+    sizes = (1, 15, 15, 3)
+    monkeypatch.setattr(gn, "GRAD_MFMA_FASTER", {"map": True, "bands": True})
+    for mfma, op in ((False, ops.gnlenet_nll_grad_rows), (True, ops.gnlenet_nll_grad_rows_mfma)):
+        plain, large = gn.grad_plan(sizes, b, mfma=mfma), gn.grad_plan(sizes, b, large=True, mfma=mfma)
+        assert plain.op is large.op is op and plain.cut and large.cut
+        assert plain.scratch_bytes(2) == large.scratch_bytes(2) == \
+            family.lib.niidmix_gnlenet_nll_grad_rows_scratch_bytes(2, b, *sizes)
+    with pytest.raises(Exception):       # a plan is immutable
+        plain.op = None
+
+
+def test_a_gradient_plan_refuses_another_width(monkeypatch):
+    from niidmix import family, ops
+    called = []
+    for name in ("linear_nll_grad_rows", "gnlenet_nll_grad_rows"):
+        monkeypatch.setattr(ops, name, lambda *a: called.append(a[8:]))
+    for fam, sizes in ((family.LINEAR, (6, 4)), (family.GN_LENET, (1, 15, 15, 3))):
+        plan = fam.grad_plan(sizes, 3)
+        for bad in (torch.zeros(2, 4, dtype=I32), torch.zeros(2, 2, dtype=I32), torch.zeros(3, dtype=I32)):
+            with pytest.raises(ValueError, match="b_max = 3"):
+                plan(None, None, None, bad, *[None] * 4)
+        assert not called
+        plan(None, None, None, torch.zeros(2, 3, dtype=I32), *[None] * 4)
+        assert called.pop() == sizes
+
+
+def test_a_linear_evaluation_plan_refuses_logits(monkeypatch):
+    from niidmix import family, ops
+    called = []
+    monkeypatch.setattr(ops, "linear_eval_rows", lambda *a: called.append(a[9:]))
+    monkeypatch.setattr(ops, "gnlenet_eval_rows", lambda *a: called.append(a[9:]))
+    lin, gn = family.LINEAR.eval_plan((6, 4)), family.GN_LENET.eval_plan((1, 15, 15, 3))
+    z = torch.zeros(1, 5, 4)
+    with pytest.raises(ValueError, match="k_lin_eval has no logits"):
+        lin(*[None] * 9, logits=z)
+    assert not called
+    lin(*[None] * 9, pred="p")
+    gn(*[None] * 9, pred="p", logits=z)
+    assert called == [("p", 6, 4), ("p", z, 1, 15, 15, 3)]
+
+
+def test_last_kernel_comes_from_the_plan_for_a_linear_model(monkeypatch):
+    """DeviceEvaluator._run names the kernel of the plan it calls, whatever the family (CPU tensors,
+    stubbed op and streams: nothing is launched)."""
+    import contextlib
+    from niidmix import evaluate, family, ops
+    seen = []
+    monkeypatch.setattr(ops, "linear_eval_rows", lambda *a: seen.append(a[-2:]))
+    monkeypatch.setattr(torch.cuda, "device", lambda dev: contextlib.nullcontext())
+    monkeypatch.setattr(torch.cuda, "stream", lambda s: contextlib.nullcontext())
+    for mfma in (False, True):
+        ev = evaluate.DeviceEvaluator({"algorithm": {"device-evaluation-mfma": mfma}}, device="cpu")
+        assert ev.last_kernel is None
+        st = evaluate._Set(torch.zeros(5, 6), torch.zeros(5, dtype=I32), 0, 3, None)
+        ev._run(torch.zeros(2, 28), st, [0, 1], [0, 0], [5, 5], (family.LINEAR, (6, 4)), (6, 4),
+                stream=object())
+        assert ev.last_kernel == ev._plan(family.LINEAR, (6, 4)).kernel == "k_lin_eval"
+        assert seen.pop() == (6, 4) and not seen and ev.last_calls == 0

@@ -436,7 +436,7 @@ def test_one_round_equals_its_parts(momentum, gpu, oracle_mod):
     # the row list cut by a scratch budget of two rows: two calls, the same bits
     params3, third, _, state3 = _setup("gn", momentum)
     tr3 = d_sgd._trainer(third, state3["topology"], params3)
-    tr3.scratch_budget = tr3._gn_need(2)
+    tr3.scratch_budget = tr3.plan.scratch_bytes(2)
     d_sgd.next_step(state3, params3, None)
     d_sgd.synchronize()
     assert tr3.last_calls == 2

@@ -51,15 +51,21 @@ def test_the_flag_needs_its_base_flag(tmp_path, monkeypatch):
                                        ((3, 32, 32, 10), "map"), ((3, 35, 32, 10), "bands"),
                                        ((2, 40, 36, 4), "bands"), ((4, 64, 64, 3), "bands")])
 def test_the_family_rule_follows_its_table(sizes, cls, monkeypatch):
+    import torch
     from niidmix import family, ops
     fam = family.GN_LENET
     assert fam.grad_mfma_class(sizes) == cls and set(fam.GRAD_MFMA_FASTER) == {"map", "bands"}
+    b = 5
+    bi = torch.zeros(2, b, dtype=torch.int32)
     for table in ({"map": True, "bands": False}, {"map": False, "bands": True}):
         monkeypatch.setattr(fam, "GRAD_MFMA_FASTER", table)
         assert fam.grad_mfma(sizes, True) is table[cls] and fam.grad_mfma(sizes, False) is False
         called = []
-        monkeypatch.setattr(ops, "gnlenet_nll_grad_rows_mfma", lambda *a: called.append("mfma"))
-        monkeypatch.setattr(ops, "gnlenet_nll_grad_rows", lambda *a: called.append("plain"))
-        fam.grad_rows(*[None] * 8, sizes, mfma=True)
-        fam.grad_rows(*[None] * 8, sizes)
-        assert called == ["mfma" if table[cls] else "plain", "plain"]
+        monkeypatch.setattr(ops, "gnlenet_nll_grad_rows_mfma", lambda *a: called.append(("mfma",) + a[8:]))
+        monkeypatch.setattr(ops, "gnlenet_nll_grad_rows", lambda *a: called.append(("plain",) + a[8:]))
+        flagged, plain = fam.grad_plan(sizes, b, mfma=True), fam.grad_plan(sizes, b)
+        assert flagged.op is (ops.gnlenet_nll_grad_rows_mfma if table[cls] else ops.gnlenet_nll_grad_rows)
+        assert plain.op is ops.gnlenet_nll_grad_rows
+        flagged(None, None, None, bi, *[None] * 4)
+        plain(None, None, None, bi, *[None] * 4)
+        assert called == [("mfma" if table[cls] else "plain",) + sizes, ("plain",) + sizes]

@@ -69,9 +69,10 @@ def test_training_limit_with_and_without_the_flag():
     assert not lin.sliced(ops.MAX_BC // 4, (6, 4), True)
     assert not lin.sliced(ops.MAX_BC // 4 + 1, (6, 4), False)
     L = __import__("niidmix")._lib.lib
-    assert lin.grad_scratch_bytes(2, 8192, (6, 4), True) == lin.grad_scratch_bytes(2, 8192, (6, 4)) == \
+    assert lin.grad_plan((6, 4), 8192, large=True).scratch_bytes(2) == \
+        lin.grad_plan((6, 4), 8192).scratch_bytes(2) == \
         4 * L.niidmix_linear_nll_grad_rows_scratch_elems(2, 8192, 4)
-    assert lin.grad_scratch_bytes(2, 8193, (6, 4), True) == \
+    assert lin.grad_plan((6, 4), 8193, large=True).scratch_bytes(2) == \
         4 * L.niidmix_linear_nll_grad_rows_sliced_scratch_elems(2, 8193, 6, 4)
     assert lin.cut is False
 
