@@ -844,6 +844,33 @@ int niidmix_gnlenet_nll_grad_rows_mfma_f32(const float *theta, int64_t ld_t, con
                                            int64_t C, void *scratch, int64_t scratch_bytes,
                                            void *stream);
 
+/* niidmix_gnlenet_nll_grad_rows_mfma_f32 with the sample pass's conv2 and conv3, and the data
+ * gradients through them, on the matrix cores as well (k_gnl_grad_sample_mfma; the drop-in's
+ * --device-training-gn-lenet-mfma-sample).  Arguments, limits, scratch layout and size
+ * (niidmix_gnlenet_nll_grad_rows_scratch_bytes), checks and their order are those of
+ * niidmix_gnlenet_nll_grad_rows_f32, with one more refusal where that entry tests H and W:
+ *   shapes    NIIDMIX_EUNSUPPORTED unless the tile of 2 samples fits the workgroup's LDS and a wave
+ *             holds its M-tiles: pooled conv1 maps up to 20 x 20, i.e. 15 <= H, W <= 42 (the shapes
+ *             niidmix_gnlenet_eval_rows_mfma_f32 takes).
+ *   the GEMMs four per tile of 2 samples on v_mfma_f32_32x32x2_f32: conv2 and conv3 forward, dY3 ->
+ *             dX3 and dY2 -> dX2 with flipped taps and transposed weights.  M is the tile's output
+ *             positions, K = (input channel, ky, kx) ascending; every output is one such chain
+ *             from 0 (the bias added last), whatever its position in the tile.
+ *   bits      all 14 tensors and the loss may differ from the other two entries' in the last bits
+ *             (another summation order in the forward); the same bound of 4 e32
+ *             (tests/test_gpu_train_gnlenet_mfma_sample.py).
+ *   NaN/inf   a non-finite conv2 / conv3 weight also reaches the border outputs through the zero
+ *             halo (0 * inf) and spreads over its own samples' maps.  It stays in its row.
+ * Determinism, independence of the other rows and of the cut of the row list, no atomics, theta
+ * not written: as niidmix_gnlenet_nll_grad_rows_f32. */
+int niidmix_gnlenet_nll_grad_rows_mfma_sample_f32(const float *theta, int64_t ld_t, const float *data,
+                                                  const int32_t *labels, const int32_t *batch_idx,
+                                                  const int32_t *batch_len, int64_t b_max,
+                                                  const int32_t *rows, int64_t n_rows, float *grad,
+                                                  int64_t ld_g, float *loss, int64_t Cin, int64_t H,
+                                                  int64_t W, int64_t C, void *scratch,
+                                                  int64_t scratch_bytes, void *stream);
+
 /* Training batches drawn on the device (the drop-in's --device-sampling): job j writes the batch
  * that starts at position cursor[j] of epoch epoch[j]'s permutation of the segment
  * [seg_start[j], seg_start[j] + seg_len[j]) of the caller's concatenated data, in the layout

@@ -68,19 +68,23 @@ __device__ __forceinline__ void gn_halo_zero(float *buf, int nch, int h, int w) 
     for (int e = threadIdx.x; e < gn_halo_tail(w); e += 256) buf[nch * gn_halo_cp(h, w) + e] = 0.f;
 }
 
-// buf [TS, 32, h, w] compact -> relu(buf * scale + shift) in the shared-halo layout, in place.  An
-// element never moves down, so chunks of 2048 go from the top: read, barrier, write, barrier.
-template <int TS>
+// buf [NCH, h, w] compact (NCH = samples x channels) -> the shared-halo layout, in place; ACT: as
+// relu(buf * scale + shift) on the way, else unchanged (a gradient map).  An element never moves
+// down, so chunks of 2048 go from the top: read, barrier, write, barrier.
+template <int NCH, bool ACT = true>
 __device__ __forceinline__ void gn_halo_expand(float *buf, int h, int w, const float *stat) {
     constexpr int R = 8;
-    const int hw = h * w, n = TS * 32 * hw, pitch = w + 2, cp = gn_halo_cp(h, w);
+    const int hw = h * w, n = NCH * hw, pitch = w + 2, cp = gn_halo_cp(h, w);
 #pragma unroll 1
     for (int top = n; top > 0; top -= 256 * R) {
         float v[R];
 #pragma unroll
         for (int q = 0; q < R; ++q) {
             const int e = top - 1 - (q * 256 + (int)threadIdx.x);
-            if (e >= 0) v[q] = gn_relu(__builtin_fmaf(buf[e], stat[16 + 2 * (e / hw)], stat[16 + 2 * (e / hw) + 1]));
+            if (e >= 0) {
+                if constexpr (ACT) v[q] = gn_relu(__builtin_fmaf(buf[e], stat[16 + 2 * (e / hw)], stat[16 + 2 * (e / hw) + 1]));
+                else v[q] = buf[e];
+            }
         }
         __syncthreads();
 #pragma unroll
@@ -93,7 +97,7 @@ __device__ __forceinline__ void gn_halo_expand(float *buf, int h, int w, const f
         }
         __syncthreads();
     }
-    gn_halo_zero(buf, TS * 32, h, w);
+    gn_halo_zero(buf, NCH, h, w);
     __syncthreads();
 }
 
@@ -134,14 +138,17 @@ __device__ __forceinline__ void gn_mma_pick(int my, floatx16 (&acc)[MTMAX][CO / 
     else if constexpr (MT < MTMAX) gn_mma_pick<CO, MT + 1, MTMAX>(my, acc, in, ab, ws, pitch, cp);
 }
 
-// 5 x 5 convolution, 32 -> CO channels, zero padding 2, on the matrix cores: in = TS * 32 channels
+// 5 x 5 convolution, CI -> CO channels, zero padding 2, on the matrix cores: in = TS * CI channels
 // of h x w in the shared-halo layout, out [TS, CO, h, w] compact (bias added), which may lie over
-// `in`.  wg: the weights [CO, 32, 5, 5] of the job's row, bg the bias.
-template <int CO, int TS, int MTMAX>
+// `in`.  wg: the weights [CO, CI, 5, 5] of the job's row, bg the bias.
+// TR: the data gradient of such a convolution instead (gn_conv's TR): wg is the forward weight
+// [CI, CO, 5, 5], the stage holds tap 24 - k of (k-channel c, output o) at k row (c, k) -- the taps
+// are flipped when the stage is written, A is read as in the forward -- and there is no bias.
+template <int CO, int CI, bool TR, int TS, int MTMAX>
 __device__ __forceinline__ void gn_conv_mfma(const float *in, float *out, int h, int w,
                                              const float *__restrict__ wg, const float *__restrict__ bg,
                                              float *ws) {
-    constexpr int ICB = kGnStage / (25 * CO), KR = ICB * 25, WS = CO + 4, NST = 32 / ICB;
+    constexpr int ICB = kGnStage / (25 * CO), KR = ICB * 25, WS = CO + 4, NST = CI / ICB;
     constexpr int NPRE = kGnStage / 256, NT = CO / 32;
     static_assert(KR * WS <= kGnWFloats && NPRE * 256 == kGnStage && ICB % 2 == 0, "stage size");
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, half = lane >> 5, col = lane & 31;
@@ -154,7 +161,7 @@ __device__ __forceinline__ void gn_conv_mfma(const float *in, float *out, int h,
     for (int j = 0; j < MTMAX; ++j) {
         const int m = (wave + 4 * j) * 32 + col, mm = m < m_all ? m : 0;      // padding rows read row 0
         const int s = mm / hw, pos = mm % hw;
-        ab[j] = (s * 32 + half) * cp + (pos / w) * pitch + pos % w;
+        ab[j] = (s * CI + half) * cp + (pos / w) * pitch + pos % w;
 #pragma unroll
         for (int n = 0; n < NT; ++n)
 #pragma unroll
@@ -165,7 +172,8 @@ __device__ __forceinline__ void gn_conv_mfma(const float *in, float *out, int h,
 #pragma unroll
         for (int q = 0; q < NPRE; ++q) {
             const int e = q * 256 + tid;
-            pre[q] = wg[((e / KR) * 32 + st * ICB) * 25 + e % KR];
+            if constexpr (TR) pre[q] = wg[((st * ICB + (e % KR) / 25) * CO + e / KR) * 25 + 24 - (e % KR) % 25];
+            else pre[q] = wg[((e / KR) * CI + st * ICB) * 25 + e % KR];
         }
     };
     fetch(0);
@@ -188,13 +196,14 @@ __device__ __forceinline__ void gn_conv_mfma(const float *in, float *out, int h,
 #pragma unroll
         for (int n = 0; n < NT; ++n) {
             const int oc = n * 32 + col;
-            const float b = bg[oc];
+            float b = 0.f;
+            if constexpr (!TR) b = bg[oc];
 #pragma unroll
             for (int r = 0; r < 16; ++r) {       // D row of register r: k_mix_dense's mapping
                 const int m = (wave + 4 * j) * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
                 if (m < m_all) {
                     const int s = (m >= hw) + (m >= 2 * hw) + (m >= 3 * hw);      // TS <= 4
-                    out[(s * CO + oc) * hw + m - s * hw] = acc[j][n][r] + b;
+                    out[(s * CO + oc) * hw + m - s * hw] = TR ? acc[j][n][r] : acc[j][n][r] + b;
                 }
             }
         }
@@ -240,12 +249,12 @@ __global__ __launch_bounds__(256) __attribute__((target("no-packed-fp32-ops"))) 
         const float *x0 = data + s0 * sample;
         gn_conv1_pool<false, TS>([&](int s) { return x0 + (int64_t)(s < ns ? s : 0) * sample; }, g, th, buf, ws);
         gn_stats<32, TS>(buf, hw1, th + g.g1w, th + g.g1b, stat);
-        gn_halo_expand<TS>(buf, g.h1, g.w1, stat);
-        gn_conv_mfma<32, TS, kGnMfmaMT2>(buf, buf, g.h1, g.w1, th + g.c2w, th + g.c2b, ws);
+        gn_halo_expand<TS * 32>(buf, g.h1, g.w1, stat);
+        gn_conv_mfma<32, 32, false, TS, kGnMfmaMT2>(buf, buf, g.h1, g.w1, th + g.c2w, th + g.c2b, ws);
         gn_stats<32, TS>(buf, hw1, th + g.g2w, th + g.g2b, stat);
         gn_halo_zero(x3, TS * 32, g.h2, g.w2);
         gn_norm_pool<32, TS, true>(buf, x3, g.h1, g.w1, g.h2, g.w2, stat);
-        gn_conv_mfma<64, TS, kGnMfmaMT3>(x3, buf, g.h2, g.w2, th + g.c3w, th + g.c3b, ws);
+        gn_conv_mfma<64, 32, false, TS, kGnMfmaMT3>(x3, buf, g.h2, g.w2, th + g.c3w, th + g.c3b, ws);
         gn_stats<64, TS>(buf, hw2, th + g.g3w, th + g.g3b, stat);
         gn_norm_pool<64, TS>(buf, feat, g.h2, g.w2, g.h3, g.w3, stat);
 

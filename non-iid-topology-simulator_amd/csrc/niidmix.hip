@@ -45,6 +45,9 @@
 //                      fp32 matrix cores, 4 or 2 samples a tile)
 //   model_gnlenet_grad_mfma.inc  k_gnl_grad_wmfma (conv2 / conv3     niidmix_gnlenet_nll_grad_rows_mfma_f32
 //                      weight gradients on the matrix cores)
+//   model_gnlenet_grad_sample_mfma.inc  k_gnl_grad_sample_mfma     niidmix_gnlenet_nll_grad_rows_mfma_sample_f32
+//                      (the sample pass's conv2 / conv3 and their
+//                      data gradients on the matrix cores)
 //   sampling.inc       k_draw_batches, k_epoch_perm_chunks /       niidmix_draw_batches_i32, _epoch_perm_i32,
 //                      _global / _finish, k_take_batches           _take_batches_i32
 //                      k_torch_randperm                            niidmix_torch_randperm_i32
@@ -4952,6 +4955,7 @@ __global__ __launch_bounds__(256) void k_lin_eval_sum(const int32_t *__restrict_
 
 #include "model_gnlenet_mfma.inc"
 #include "model_gnlenet_grad_mfma.inc"
+#include "model_gnlenet_grad_sample_mfma.inc"
 
 #include "sampling.inc"
 
@@ -6499,13 +6503,17 @@ int64_t niidmix_gnlenet_nll_grad_rows_scratch_bytes(int64_t n_rows, int64_t b_ma
     return n_rows * gn_tiles(b_max) * gn_grad_lay(g).tile * 4;
 }
 
-// both GN-LeNet gradient entry points: mfma takes conv2's and conv3's weight gradients out of
-// k_gnl_grad_conv and gives them to k_gnl_grad_wmfma
-static int gn_grad_rows(bool mfma, const float *theta, int64_t ld_t, const float *data,
+// the GN-LeNet gradient entry points.  kGnGradWmfma takes conv2's and conv3's weight gradients out
+// of k_gnl_grad_conv and gives them to k_gnl_grad_wmfma; kGnGradSampleMfma does that and runs the
+// sample pass as k_gnl_grad_sample_mfma, at the shapes that kernel takes
+enum GnGradVariant { kGnGradPlain, kGnGradWmfma, kGnGradSampleMfma };
+
+static int gn_grad_rows(GnGradVariant variant, const float *theta, int64_t ld_t, const float *data,
                         const int32_t *labels, const int32_t *batch_idx, const int32_t *batch_len,
                         int64_t b_max, const int32_t *rows, int64_t n_rows, float *grad, int64_t ld_g,
                         float *loss, int64_t Cin, int64_t H, int64_t W, int64_t C, void *scratch,
                         int64_t scratch_bytes, void *stream) {
+    const bool mfma = variant != kGnGradPlain;
     if (!theta || !data || !labels || !batch_idx || !batch_len || !rows || !grad || !loss || !scratch)
         return set_error(NIIDMIX_EINVAL, "null pointer");
     if (n_rows <= 0 || b_max <= 0 || Cin <= 0 || H <= 0 || W <= 0 || C <= 0)
@@ -6515,6 +6523,9 @@ static int gn_grad_rows(bool mfma, const float *theta, int64_t ld_t, const float
     if (!gn_supported(Cin, H, W, C))
         return set_error(NIIDMIX_EUNSUPPORTED, "H %lld, W %lld: the kernel holds %d <= H, W <= %d",
                          (long long)H, (long long)W, kGnMinHW, kGnMaxHW);
+    if (variant == kGnGradSampleMfma && !gn_gsm_takes(gn_shape((int)Cin, (int)H, (int)W, (int)C)))
+        return set_error(NIIDMIX_EUNSUPPORTED, "H %lld, W %lld: the matrix-core sample pass's tile of 2 "
+                         "samples does not fit in LDS", (long long)H, (long long)W);
     if (b_max > kGnGradMaxB)
         return set_error(NIIDMIX_EUNSUPPORTED, "b_max %lld > 2^24", (long long)b_max);
     const GnShape g = gn_shape((int)Cin, (int)H, (int)W, (int)C);
@@ -6538,10 +6549,20 @@ static int gn_grad_rows(bool mfma, const float *theta, int64_t ld_t, const float
     const GnGradLay L = gn_grad_lay(g);
     const int64_t n_tiles = gn_tiles(b_max), n_work = n_rows * n_tiles;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(k_gnl_grad_sample, dim3((unsigned)(n_work < kGnMaxGrid ? n_work : kGnMaxGrid)),
-                       dim3(256), (size_t)gn_lds_bytes_global(), s, theta, ld_t, data, labels, batch_idx,
-                       batch_len, (int)b_max, rows, n_rows, (int)n_tiles, g, L, sc);
-    if (int rc = check_launch("k_gnl_grad_sample")) return rc;
+    const unsigned grid = (unsigned)(n_work < kGnMaxGrid ? n_work : kGnMaxGrid);
+    if (variant == kGnGradSampleMfma) {
+        const size_t lds = (size_t)gn_gsm_lds_bytes(g);
+        if (lds > 64 * 1024)
+            if (int rc = lds_opt_in(k_gnl_grad_sample_mfma, lds, "k_gnl_grad_sample_mfma")) return rc;
+        hipLaunchKernelGGL(k_gnl_grad_sample_mfma, dim3(grid), dim3(256), lds, s, theta, ld_t, data, labels,
+                           batch_idx, batch_len, (int)b_max, rows, n_rows, (int)n_tiles, g, L, sc);
+        if (int rc = check_launch("k_gnl_grad_sample_mfma")) return rc;
+    } else {
+        hipLaunchKernelGGL(k_gnl_grad_sample, dim3(grid), dim3(256), (size_t)gn_lds_bytes_global(), s, theta,
+                           ld_t, data, labels, batch_idx, batch_len, (int)b_max, rows, n_rows, (int)n_tiles,
+                           g, L, sc);
+        if (int rc = check_launch("k_gnl_grad_sample")) return rc;
+    }
     if (mfma) {                                  // the units: n_rows of conv2, then 2 n_rows of conv3
         const GnWmGeom q2 = gn_wm_geom(g.h1, g.w1), q3 = gn_wm_geom(g.h2, g.w2);
         const size_t lds = 4 * (size_t)(gn_wm_lds_floats(q2) > gn_wm_lds_floats(q3) ? gn_wm_lds_floats(q2)
@@ -6567,7 +6588,7 @@ int niidmix_gnlenet_nll_grad_rows_f32(const float *theta, int64_t ld_t, const fl
                                       int64_t n_rows, float *grad, int64_t ld_g, float *loss,
                                       int64_t Cin, int64_t H, int64_t W, int64_t C, void *scratch,
                                       int64_t scratch_bytes, void *stream) {
-    return gn_grad_rows(false, theta, ld_t, data, labels, batch_idx, batch_len, b_max, rows, n_rows, grad,
+    return gn_grad_rows(kGnGradPlain, theta, ld_t, data, labels, batch_idx, batch_len, b_max, rows, n_rows, grad,
                         ld_g, loss, Cin, H, W, C, scratch, scratch_bytes, stream);
 }
 
@@ -6577,8 +6598,19 @@ int niidmix_gnlenet_nll_grad_rows_mfma_f32(const float *theta, int64_t ld_t, con
                                            int64_t n_rows, float *grad, int64_t ld_g, float *loss,
                                            int64_t Cin, int64_t H, int64_t W, int64_t C, void *scratch,
                                            int64_t scratch_bytes, void *stream) {
-    return gn_grad_rows(true, theta, ld_t, data, labels, batch_idx, batch_len, b_max, rows, n_rows, grad,
+    return gn_grad_rows(kGnGradWmfma, theta, ld_t, data, labels, batch_idx, batch_len, b_max, rows, n_rows, grad,
                         ld_g, loss, Cin, H, W, C, scratch, scratch_bytes, stream);
+}
+
+int niidmix_gnlenet_nll_grad_rows_mfma_sample_f32(const float *theta, int64_t ld_t, const float *data,
+                                                  const int32_t *labels, const int32_t *batch_idx,
+                                                  const int32_t *batch_len, int64_t b_max,
+                                                  const int32_t *rows, int64_t n_rows, float *grad,
+                                                  int64_t ld_g, float *loss, int64_t Cin, int64_t H,
+                                                  int64_t W, int64_t C, void *scratch,
+                                                  int64_t scratch_bytes, void *stream) {
+    return gn_grad_rows(kGnGradSampleMfma, theta, ld_t, data, labels, batch_idx, batch_len, b_max, rows,
+                        n_rows, grad, ld_g, loss, Cin, H, W, C, scratch, scratch_bytes, stream);
 }
 
 int64_t niidmix_draw_batches_max_len(void) { return kDrawMaxLen; }

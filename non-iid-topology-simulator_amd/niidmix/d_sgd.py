@@ -22,7 +22,9 @@ Gradient averaging (--clique-gradient, --unbiased-gradient) also runs on the GPU
 With --device-training (params['algorithm']['device-training'], opt-in) a linear model's local
 training runs on the device too: gradient, step and mixing never leave HBM (niidmix.train);
 --device-training-gn-lenet does the same for GN-LeNet models (--device-training-gn-lenet-mfma, with
-it, takes two of its weight gradients from a matrix-core kernel), and --device-training-sample for
+it, takes two of its weight gradients from a matrix-core kernel, and
+--device-training-gn-lenet-mfma-sample, with both, its sample pass's convolutions too), and
+--device-training-sample for
 rounds of the 'sample' topology (the other two flags refuse it).  --device-sampling, with any of
 the three, draws the batches on the device too, from a sample stream of the plugin's own
 (niidmix.sampling) instead of one DataLoader per node; --device-sampling-cached keeps every epoch's
@@ -920,6 +922,7 @@ def init(nodes, topology, params):
     if params["algorithm"].get("device-training") or params["algorithm"].get("device-sampling") or \
             params["algorithm"].get("device-training-large-batch") or \
             params["algorithm"].get("device-training-gn-lenet-mfma") or \
+            params["algorithm"].get("device-training-gn-lenet-mfma-sample") or \
             params["algorithm"].get("device-sampling-torch-stream"):
         from . import train
         train.check_eligible(nodes, params, topology)     # refusals: ValueError naming the flag
@@ -1153,6 +1156,12 @@ def main(argv=None):
                          "from the kernel on the matrix cores (niidmix::gnlenet_nll_grad_rows_mfma), at "
                          "the shapes it is measured faster at; the same bound, other bits in those "
                          "two tensors only")
+    ap.add_argument("--device-training-gn-lenet-mfma-sample", action="store_const", const=True,
+                    default=False,
+                    help="with --device-training-gn-lenet-mfma: the sample pass's conv2 / conv3 and "
+                         "their data gradients run on the matrix cores as well "
+                         "(niidmix::gnlenet_nll_grad_rows_mfma_sample), at the shapes it is measured "
+                         "faster at; the same bound, other bits in every tensor")
     ap.add_argument("--device-training-sample", action="store_const", const=True, default=False,
                     help="--device-training for runs of the 'sample' topology (sets both keys; "
                          "the other two flags refuse 'sample'): each round the sampled nodes train "
@@ -1220,6 +1229,8 @@ def main(argv=None):
         ap.error("--device-evaluation-mfma needs --device-evaluation")
     if args.device_training_gn_lenet_mfma and not args.device_training_gn_lenet:
         ap.error("--device-training-gn-lenet-mfma needs --device-training-gn-lenet")
+    if args.device_training_gn_lenet_mfma_sample and not args.device_training_gn_lenet_mfma:
+        ap.error("--device-training-gn-lenet-mfma-sample needs --device-training-gn-lenet-mfma")
     rundir = m.rundir(args)
     params = m.params(rundir)
     topology = load_topology(rundir)
@@ -1241,6 +1252,8 @@ def main(argv=None):
            or args.device_training_sample else {}),
         **({"device-training-gn-lenet": True} if args.device_training_gn_lenet else {}),
         **({"device-training-gn-lenet-mfma": True} if args.device_training_gn_lenet_mfma else {}),
+        **({"device-training-gn-lenet-mfma-sample": True} if args.device_training_gn_lenet_mfma_sample
+           else {}),
         **({"device-training-sample": True} if args.device_training_sample else {}),
         **({"device-training-large-batch": True} if args.device_training_large_batch else {}),
         **({"device-sampling": True} if args.device_sampling else {}),

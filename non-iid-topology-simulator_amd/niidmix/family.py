@@ -1,7 +1,8 @@
 """The model families of the device paths: what depends on WHICH model niidmix.train trains or
 niidmix.evaluate evaluates, stated once.  LINEAR (setup/model/linear.py: one nn.Linear(K, C),
 log_softmax) and GN_LENET (setup/model/gn_lenet.py) have the same methods, apart from each one's own
-routing rule (LINEAR.sliced; GN_LENET.grad_mfma, grad_mfma_class, mfma); family_of(model) picks one
+routing rule (LINEAR.sliced; GN_LENET.grad_mfma, grad_mfma_class, mfma; the module's
+grad_mfma_sample); family_of(model) picks one
 from the parameters' shapes.  A family knows its shape(model) -- (K, C) / (Cin, C, F), C is
 shape[1] in both -- and P(shape); the kernels' limits as refusals (the constants are niidmix.ops',
 which checks its arguments against the same ones); sizes(), the one sample check, giving the
@@ -10,11 +11,13 @@ kernel's size arguments (K, C) / (Cin, H, W, C); its gradient and evaluation cal
 ops.gnlenet_shapes, one table: the expected shapes, the offsets, the row splitter, P and F follow
 from it.  The float64 yardsticks of the probes and of the GPU tests live here as well.
 
-The kernel variant is bound once, in a plan: grad_plan(sizes, b_max, large=False, mfma=False) and
-eval_plan(sizes, mfma=False) apply the family's rule, reading its table then, to the opt-in switches
-(`large`: --device-training-large-batch; `mfma`: --device-training-gn-lenet-mfma /
---device-evaluation-mfma) and return a GradPlan / EvalPlan.  A family ignores a switch that is not
-its own (LINEAR `mfma`, GN_LENET `large`), so the callers pass every switch to either family.
+The kernel variant is bound once, in a plan: grad_plan(sizes, b_max, large=False, mfma=False,
+mfma_sample=False) and eval_plan(sizes, mfma=False) apply the family's rule, reading its table then,
+to the opt-in switches (`large`: --device-training-large-batch; `mfma`:
+--device-training-gn-lenet-mfma / --device-evaluation-mfma; `mfma_sample`:
+--device-training-gn-lenet-mfma-sample) and return a GradPlan / EvalPlan.  A family ignores a switch
+that is not its own (LINEAR `mfma` and `mfma_sample`, GN_LENET `large`), so the callers pass every
+switch to either family.
 """
 import copy
 import math
@@ -238,7 +241,7 @@ class _Linear:
         the existing kernel does not take its shape."""
         return bool(large) and b_max * sizes[1] > MAX_BC
 
-    def grad_plan(self, sizes, b_max, large=False, mfma=False):
+    def grad_plan(self, sizes, b_max, large=False, mfma=False, mfma_sample=False):
         if self.sliced(b_max, sizes, large):         # the scratch sizes are in fp32 elements
             op, dims = ops.linear_nll_grad_rows_sliced, sizes
             elems = lib.niidmix_linear_nll_grad_rows_sliced_scratch_elems
@@ -275,6 +278,23 @@ class _Linear:
     def probe_eval(self, model, x, y, params, device, plan, flag):
         """The evaluation kernel computes the gradient kernel's forward: probe_grad."""
         self.probe_grad(model, x, y, params, device, plan.sizes, flag)
+
+
+# --device-training-gn-lenet-mfma-sample's shape classes are the tiles of ops.gn_mfma_tile (4: the
+# MNIST-sized shapes, 2: the CIFAR-sized ones; 0: k_gnl_grad_sample_mfma does not take the shape).
+# True where tools/device_training_probe.py gn-kernel measured the call's median below
+# gnlenet_nll_grad_rows_mfma's by more than that call's own spread in the same run (DESIGN.md
+# section 5: tile 4 at 100 rows x 1 x 28 x 28 x batch 128, tile 2 at 1000 rows x 3 x 32 x 32 x batch
+# 20; profiles/gnlenet_grad_sample_mfma/).  A class that is not keeps the plan it had without the flag.
+GRAD_MFMA_SAMPLE_FASTER = {4: True, 2: True}
+
+
+def grad_mfma_sample(sizes, mfma, flag):
+    """Under --device-training-gn-lenet-mfma (`mfma`) and --device-training-gn-lenet-mfma-sample
+    (`flag`) a GN-LeNet call goes to the op with the matrix-core sample pass exactly when that
+    kernel takes the shape and is the measured faster one at the shape's class."""
+    return bool(mfma) and bool(flag) and \
+        GRAD_MFMA_SAMPLE_FASTER.get(ops.gn_mfma_tile(sizes[1], sizes[2]), False)
 
 
 class _GNLeNet:
@@ -331,9 +351,12 @@ class _GNLeNet:
         when that op is the measured faster one at the shape's class."""
         return bool(flag) and self.GRAD_MFMA_FASTER[self.grad_mfma_class(sizes)]
 
-    def grad_plan(self, sizes, b_max, large=False, mfma=False):
-        op = ops.gnlenet_nll_grad_rows_mfma if self.grad_mfma(sizes, mfma) else ops.gnlenet_nll_grad_rows
-        scratch = lib.niidmix_gnlenet_nll_grad_rows_scratch_bytes       # both ops'
+    def grad_plan(self, sizes, b_max, large=False, mfma=False, mfma_sample=False):
+        if grad_mfma_sample(sizes, mfma, mfma_sample):
+            op = ops.gnlenet_nll_grad_rows_mfma_sample
+        else:
+            op = ops.gnlenet_nll_grad_rows_mfma if self.grad_mfma(sizes, mfma) else ops.gnlenet_nll_grad_rows
+        scratch = lib.niidmix_gnlenet_nll_grad_rows_scratch_bytes       # every op'
         return GradPlan(op, self.cut, sizes, b_max, lambda rows: int(scratch(rows, b_max, *sizes)))
 
     # --device-evaluation-mfma's shape classes are the matrix-core kernel's tiles (ops.gn_mfma_tile):

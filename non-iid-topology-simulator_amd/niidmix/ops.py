@@ -44,6 +44,11 @@ Ops (registered in the `niidmix` namespace, usable as torch.ops.niidmix.*):
   gnlenet_nll_grad_rows_mfma(the same arguments)    the same with k_gnl_grad_wmfma for conv2's and
                                                     conv3's weight gradients (the matrix cores,
                                                     --device-training-gn-lenet-mfma)
+  gnlenet_nll_grad_rows_mfma_sample(the same arguments)
+                                                    the same with k_gnl_grad_sample_mfma as the sample
+                                                    pass (its conv2 / conv3 and their data gradients
+                                                    on the matrix cores, where gn_mfma_tile(H, W) > 0,
+                                                    --device-training-gn-lenet-mfma-sample)
   gnlenet_eval_rows(theta, data, labels, rows, seg_start, seg_len, max_len, loss_sum, correct, pred,
                     logits, Cin, H, W, C)           k_gnl_eval + k_lin_eval_sum (the same for GN-LeNet)
   gnlenet_eval_rows_mfma(the same arguments)        k_gnl_eval_mfma + k_lin_eval_sum (conv2 / conv3 on
@@ -939,7 +944,7 @@ def gnlenet_eval_rows_mfma(theta: torch.Tensor, data: torch.Tensor, labels: torc
 
 
 def _gnlenet_grad(name, theta, data, labels, batch_idx, batch_len, rows, grad, loss, Cin, H, W, C):
-    """The two GN-LeNet gradient ops: `name` is the C entry point without its niidmix_ and _f32."""
+    """The GN-LeNet gradient ops: `name` is the C entry point without its niidmix_ and _f32."""
     Cin, H, W, C = int(Cin), int(H), int(W), int(C)
     _req(Cin >= 1 and H >= 1 and W >= 1 and C >= 1, "Cin, H, W and C must be >= 1")
     _gnlenet_limits(Cin, H, W, C)
@@ -983,6 +988,21 @@ def gnlenet_nll_grad_rows_mfma(theta: torch.Tensor, data: torch.Tensor, labels: 
     and bound; those two tensors in another summation order, everything else bit for bit."""
     _gnlenet_grad("gnlenet_nll_grad_rows_mfma", theta, data, labels, batch_idx, batch_len, rows, grad,
                   loss, Cin, H, W, C)
+
+
+@torch.library.custom_op("niidmix::gnlenet_nll_grad_rows_mfma_sample", mutates_args=("grad", "loss"))
+def gnlenet_nll_grad_rows_mfma_sample(theta: torch.Tensor, data: torch.Tensor, labels: torch.Tensor,
+                                      batch_idx: torch.Tensor, batch_len: torch.Tensor, rows: torch.Tensor,
+                                      grad: torch.Tensor, loss: torch.Tensor,
+                                      Cin: int, H: int, W: int, C: int) -> None:
+    """gnlenet_nll_grad_rows_mfma with the sample pass's conv2 / conv3 and their data gradients on
+    the matrix cores as well (include/niidmix.h, niidmix_gnlenet_nll_grad_rows_mfma_sample_f32): the
+    same arguments, checks, scratch and bound; every tensor and the loss in another summation order.
+    The kernel takes the shapes at which gn_mfma_tile(H, W) > 0 (its tile is 2 samples at all of
+    them, and its backward's buffers fit wherever its forward's do); any other is the launcher's
+    NIIDMIX_EUNSUPPORTED."""
+    _gnlenet_grad("gnlenet_nll_grad_rows_mfma_sample", theta, data, labels, batch_idx, batch_len, rows,
+                  grad, loss, Cin, H, W, C)
 
 
 def draw_batches_max_len():

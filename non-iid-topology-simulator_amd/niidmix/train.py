@@ -27,6 +27,9 @@ several calls when one call's scratch would exceed a budget (a row's bits do not
 cut).  `--device-training-gn-lenet-mfma`, valid only with that flag, swaps the gradient op for
 niidmix::gnlenet_nll_grad_rows_mfma (conv2's and conv3's weight gradients on the matrix cores)
 where niidmix.family's rule sends the shape; nothing else of the round changes.
+`--device-training-gn-lenet-mfma-sample`, valid only with both, swaps it for
+niidmix::gnlenet_nll_grad_rows_mfma_sample (the sample pass's conv2 / conv3 and their data gradients
+on the matrix cores too) under the same kind of rule.
 
 What depends on the model family -- shapes, the kernels' limits, the sample check, the gradient op
 and its scratch, the forward probe -- is niidmix.family's; DeviceTrainer holds a family, its
@@ -126,6 +129,7 @@ from .topology import to_csr
 FLAG = "--device-training"
 FLAG_GN = "--device-training-gn-lenet"
 FLAG_GN_MFMA = "--device-training-gn-lenet-mfma"
+FLAG_GN_MFMA_SAMPLE = "--device-training-gn-lenet-mfma-sample"
 FLAG_SAMPLE = "--device-training-sample"
 FLAG_SAMPLING = "--device-sampling"
 FLAG_CACHED = "--device-sampling-cached"
@@ -155,6 +159,13 @@ def gn_mfma_enabled(params):
     """--device-training-gn-lenet-mfma: GN-LeNet's gradient goes to the op with conv2's and conv3's
     weight gradients on the matrix cores where niidmix.family's rule sends the shape."""
     return bool(params.get("algorithm", {}).get("device-training-gn-lenet-mfma"))
+
+
+def gn_mfma_sample_enabled(params):
+    """--device-training-gn-lenet-mfma-sample: with --device-training-gn-lenet-mfma, the gradient
+    goes to the op whose sample pass runs conv2 / conv3 on the matrix cores as well, where
+    niidmix.family's rule sends the shape."""
+    return bool(params.get("algorithm", {}).get("device-training-gn-lenet-mfma-sample"))
 
 
 def sample_run(params):
@@ -341,6 +352,8 @@ def check_eligible(nodes, params, topology=None):
     gn_flag = gn_enabled(params)
     if gn_mfma_enabled(params) and not gn_flag:
         raise ValueError(f"{FLAG_GN_MFMA} needs {FLAG_GN}")
+    if gn_mfma_sample_enabled(params) and not gn_mfma_enabled(params):
+        raise ValueError(f"{FLAG_GN_MFMA_SAMPLE} needs {FLAG_GN_MFMA}")
     flag = flag_of(params)
     sample = sample_run(params)
     large = large_enabled(params)
@@ -462,7 +475,8 @@ class DeviceTrainer:
         self.n_buf = 3 + (self.momentum != 0.0) + (self.grad_kind in ("clique-removed", "unbiased"))
         xs, ys, self.offsets = self._materialise(nodes)
         # the gradient call, its kernel variant bound for the trainer's life
-        self.plan = self.family.grad_plan(self.sizes, self.b_max, self.large, gn_mfma_enabled(params))
+        self.plan = self.family.grad_plan(self.sizes, self.b_max, self.large, gn_mfma_enabled(params),
+                                          gn_mfma_sample_enabled(params))
         self._check_fit(xs)
         dev = self.device
         self.data = xs.to(dev)

@@ -18,16 +18,19 @@
 
 GN-LeNet (niidmix_gnlenet_nll_grad_rows_f32, --device-training-gn-lenet), at the two shapes
     gn-cifar   N 1000, 3 x 32 x 32, C 10, B 20     gn-mnist   N 100, 1 x 28 x 28, C 10, B 128
-  gn-kernel  the gradient call and niidmix_gnlenet_nll_grad_rows_mfma_f32 (grad_mfma; conv2's and
-             conv3's weight gradients on the matrix cores) against three yardsticks, all five alternating within every
+  gn-kernel  the gradient call, niidmix_gnlenet_nll_grad_rows_mfma_f32 (grad_mfma; conv2's and
+             conv3's weight gradients on the matrix cores) and
+             niidmix_gnlenet_nll_grad_rows_mfma_sample_f32 (grad_mfma_sample; the sample pass's
+             convolutions there too) against three yardsticks, all six alternating within every
              repetition: the CPU loop (forward + nll_loss + backward of the module, torch's
              threads as set, on a few nodes, scaled to N), torch autograd on the device (the
              same module, looped over a few nodes, scaled to N), and niidmix_stream_copy_f32 over
              the bytes the call must read (parameters and batch samples).  Device candidates by
              device events, the CPU loop by the host clock.
   gn-rounds  as `rounds`, for GN-LeNet models and the --device-training-gn-lenet flag; with
-             --gn-mfma the device run sets --device-training-gn-lenet-mfma as well (a process holds
-             one live trainer, so base and new flag are two invocations).
+             --gn-mfma the device run sets --device-training-gn-lenet-mfma as well, with
+             --gn-mfma-sample --device-training-gn-lenet-mfma-sample too (a process holds one live
+             trainer, so base and new flag are two invocations).
 
     python tools/device_training_probe.py gn-kernel --shape gn-cifar [--warmup 5] [--reps 20]
     python tools/device_training_probe.py gn-rounds --shape gn-mnist [--warmup 2] [--rounds 10]
@@ -160,6 +163,8 @@ def gn_kernel(a):
     xc, yc = xb[:n_cpu].cpu(), yb[:n_cpu].cpu()
     cands = [("copy", copy_call, 1.0, True), ("grad", grad_call, 1.0, True),
              ("grad_mfma", lambda: grad_call(lib.niidmix_gnlenet_nll_grad_rows_mfma_f32), 1.0, True),
+             ("grad_mfma_sample", lambda: grad_call(lib.niidmix_gnlenet_nll_grad_rows_mfma_sample_f32), 1.0,
+              True),
              ("device_autograd", lambda: loop(mdl_dev, xb, yb, n_dev), n / n_dev, True),
              ("cpu_loop", lambda: loop(mdl, xc, yc, n_cpu), n / n_cpu, False)]
     times = {name: [] for name, _, _, _ in cands}
@@ -191,6 +196,10 @@ def gn_kernel(a):
     out["grad_mfma_over_grad"] = out["grad_mfma"]["median_ms"] / out["grad"]["median_ms"]
     out["grad_mfma_faster"] = out["grad"]["median_ms"] - out["grad_mfma"]["median_ms"] > \
         out["grad"]["max_ms"] - out["grad"]["min_ms"]
+    # the same rule for family.GRAD_MFMA_SAMPLE_FASTER, against grad_mfma
+    out["grad_mfma_sample_over_grad_mfma"] = out["grad_mfma_sample"]["median_ms"] / out["grad_mfma"]["median_ms"]
+    out["grad_mfma_sample_faster"] = out["grad_mfma"]["median_ms"] - out["grad_mfma_sample"]["median_ms"] > \
+        out["grad_mfma"]["max_ms"] - out["grad_mfma"]["min_ms"]
     print(json.dumps(out))
 
 
@@ -365,6 +374,8 @@ def rounds(a):
     if gn and a.gn_mfma:                     # time the matrix-core op whatever the family's rule says
         from niidmix import family
         family.GN_LENET.GRAD_MFMA_FASTER = dict.fromkeys(family.GN_LENET.GRAD_MFMA_FASTER, True)
+        if a.gn_mfma_sample:
+            family.GRAD_MFMA_SAMPLE_FASTER = dict.fromkeys(family.GRAD_MFMA_SAMPLE_FASTER, True)
     for flag in (False, True):
         torch.manual_seed(7)
         params = {"meta": {"log": "WARNING", "seed": 7}, "model": {"input-size": k},
@@ -379,6 +390,8 @@ def rounds(a):
             params["algorithm"]["device-training-gn-lenet"] = True
         if gn and flag and a.gn_mfma:
             params["algorithm"]["device-training-gn-lenet-mfma"] = True
+            if a.gn_mfma_sample:
+                params["algorithm"]["device-training-gn-lenet-mfma-sample"] = True
         ts = [(x[j], int(y[j])) for j in range(per_node)]
         nodes = []
         for r in range(n):
@@ -399,6 +412,7 @@ def rounds(a):
                 times.append(dt)
     out = {"step": "gn-rounds" if gn else "rounds", "shape": a.shape, "n": n, "k": k, "c": c, "b": b, "mode": a.mode,
            "clique_gradient": a.clique_gradient, "momentum": a.momentum, "gn_mfma": bool(gn and a.gn_mfma),
+           "gn_mfma_sample": bool(gn and a.gn_mfma and a.gn_mfma_sample),
            "warmup": a.warmup, "rounds": a.rounds, "threads": torch.get_num_threads(),
            "device": torch.cuda.get_device_name(0)}
     for flag, key in ((False, "flag_off"), (True, "flag_on")):
@@ -602,6 +616,8 @@ def main():
     ap.add_argument("--momentum", type=float, default=0.0, help="rounds / gn-rounds: --learning-momentum")
     ap.add_argument("--gn-mfma", action="store_true",
                     help="gn-rounds: the device run also sets --device-training-gn-lenet-mfma")
+    ap.add_argument("--gn-mfma-sample", action="store_true",
+                    help="gn-rounds, with --gn-mfma: and --device-training-gn-lenet-mfma-sample")
     a = ap.parse_args()
     if a.step == "all":
         return run_all(a)
