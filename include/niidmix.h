@@ -871,6 +871,33 @@ int niidmix_gnlenet_nll_grad_rows_mfma_sample_f32(const float *theta, int64_t ld
                                                   int64_t W, int64_t C, void *scratch,
                                                   int64_t scratch_bytes, void *stream);
 
+/* niidmix_gnlenet_nll_grad_rows_mfma_sample_f32 with conv1's weight gradient on the matrix cores as
+ * well (k_gnl_grad_w1mfma; the drop-in's --device-training-gn-lenet-mfma-conv1).  Arguments, limits
+ * (the same shapes: 15 <= H, W <= 42), scratch layout and size, checks and their order are those of
+ * niidmix_gnlenet_nll_grad_rows_mfma_sample_f32.  What differs:
+ *   conv1.w   v_mfma_f32_32x32x2_f32, one GEMM per row: the pooled gradient goes back to full
+ *             resolution (a position gets the gradients of the <= 4 pool windows whose saved argmax
+ *             it is, in ascending window order), and dW1[oc, (ci, tap)] = sum dYf[s, oc, Y, X]
+ *             Xpad[s, ci, Y + ky - 2, X + kx - 2] with K over the samples in batch order, bands of
+ *             rows top down and the positions of a band with two zero columns per row.  A band's
+ *             positions are cut in four runs, one per wave; an output is the four runs' chains over
+ *             the whole batch, added in run order.  Not bit-identical to the other entries, the
+ *             same bound of 4 e32 (tests/test_gpu_train_gnlenet_mfma_conv1.py).
+ *   the rest  the other 13 tensors and the loss are niidmix_gnlenet_nll_grad_rows_mfma_sample_f32's,
+ *             bit for bit.
+ *   NaN/inf   a non-finite input pixel reaches every tap of its channel in all 32 filters (0 * inf
+ *             at the positions that are no window's argmax), where the other entries read the
+ *             argmax positions only.  It stays in the rows that train on that sample.
+ * Determinism, independence of the other rows and of the cut of the row list, no atomics, theta
+ * not written: as niidmix_gnlenet_nll_grad_rows_f32. */
+int niidmix_gnlenet_nll_grad_rows_mfma_conv1_f32(const float *theta, int64_t ld_t, const float *data,
+                                                 const int32_t *labels, const int32_t *batch_idx,
+                                                 const int32_t *batch_len, int64_t b_max,
+                                                 const int32_t *rows, int64_t n_rows, float *grad,
+                                                 int64_t ld_g, float *loss, int64_t Cin, int64_t H,
+                                                 int64_t W, int64_t C, void *scratch,
+                                                 int64_t scratch_bytes, void *stream);
+
 /* Training batches drawn on the device (the drop-in's --device-sampling): job j writes the batch
  * that starts at position cursor[j] of epoch epoch[j]'s permutation of the segment
  * [seg_start[j], seg_start[j] + seg_len[j]) of the caller's concatenated data, in the layout

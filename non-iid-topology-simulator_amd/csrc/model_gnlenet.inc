@@ -619,8 +619,10 @@ __global__ __launch_bounds__(256) void k_gnl_grad_sample(const float *__restrict
 constexpr int kGnMaxHW1 = ((kGnMaxHW - 3) / 2 + 1) * ((kGnMaxHW - 3) / 2 + 1);     // 31 x 31
 
 // W23 = false leaves conv2's and conv3's weight gradients to k_gnl_grad_wmfma
-// (model_gnlenet_grad_mfma.inc): their chain and its stores are dropped, nothing else.
-template <bool W23 = true>
+// (model_gnlenet_grad_mfma.inc): their chain and its stores are dropped, nothing else.  W1 = false
+// leaves conv1's to k_gnl_grad_w1mfma (model_gnlenet_grad_conv1_mfma.inc) in the same way, with the
+// argmax staging that only its chain reads.
+template <bool W23 = true, bool W1 = true>
 __global__ __launch_bounds__(256) void k_gnl_grad_conv(const float *__restrict__ data,
                                                        const int32_t *__restrict__ batch_idx,
                                                        const int32_t *__restrict__ batch_len, int b_max,
@@ -649,7 +651,7 @@ __global__ __launch_bounds__(256) void k_gnl_grad_conv(const float *__restrict__
         __syncthreads();                                              // the last sample has been read
         for (int p = tid; p < hw; p += 256) {
             dys[p] = T[o_dy + (sl * CO + oc) * hw + p];
-            if (layer == 1) ams[p] = reinterpret_cast<const unsigned char *>(T + L.amax)[(sl * 32 + oc) * hw + p];
+            if (W1 && layer == 1) ams[p] = reinterpret_cast<const unsigned char *>(T + L.amax)[(sl * 32 + oc) * hw + p];
         }
         __syncthreads();
         if (wave == 3) {                                              // the bias: lanes stride the map
@@ -660,7 +662,7 @@ __global__ __launch_bounds__(256) void k_gnl_grad_conv(const float *__restrict__
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int e = tid + 256 * q;
-            if (e >= nel || (!W23 && layer != 1)) continue;
+            if (e >= nel || !(layer == 1 ? W1 : W23)) continue;
             const int ic = e / 25, ky = (e % 25) / 5, kx = e % 5;
             float acc = 0.f;
             if (layer == 1) {                                         // the input at the argmax positions
@@ -686,7 +688,7 @@ __global__ __launch_bounds__(256) void k_gnl_grad_conv(const float *__restrict__
     const int o_w = layer == 1 ? g.c1w : layer == 2 ? g.c2w : g.c3w;
 #pragma unroll
     for (int q = 0; q < 4; ++q)
-        if (tid + 256 * q < nel && (W23 || layer == 1)) gr[o_w + oc * nel + tid + 256 * q] = tot[q];
+        if (tid + 256 * q < nel && (layer == 1 ? W1 : W23)) gr[o_w + oc * nel + tid + 256 * q] = tot[q];
     if (tid == 192) gr[o_w + CO * nel + oc] = btot;                   // the bias follows its weight
     if (tid == 0) {                                                   // GroupNorm's weight and bias
         float dg = 0.f, db = 0.f;

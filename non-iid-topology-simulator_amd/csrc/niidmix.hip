@@ -48,6 +48,8 @@
 //   model_gnlenet_grad_sample_mfma.inc  k_gnl_grad_sample_mfma     niidmix_gnlenet_nll_grad_rows_mfma_sample_f32
 //                      (the sample pass's conv2 / conv3 and their
 //                      data gradients on the matrix cores)
+//   model_gnlenet_grad_conv1_mfma.inc  k_gnl_grad_w1mfma (conv1's  niidmix_gnlenet_nll_grad_rows_mfma_conv1_f32
+//                      weight gradient on the matrix cores)
 //   sampling.inc       k_draw_batches, k_epoch_perm_chunks /       niidmix_draw_batches_i32, _epoch_perm_i32,
 //                      _global / _finish, k_take_batches           _take_batches_i32
 //                      k_torch_randperm                            niidmix_torch_randperm_i32
@@ -4956,6 +4958,7 @@ __global__ __launch_bounds__(256) void k_lin_eval_sum(const int32_t *__restrict_
 #include "model_gnlenet_mfma.inc"
 #include "model_gnlenet_grad_mfma.inc"
 #include "model_gnlenet_grad_sample_mfma.inc"
+#include "model_gnlenet_grad_conv1_mfma.inc"
 
 #include "sampling.inc"
 
@@ -6505,15 +6508,17 @@ int64_t niidmix_gnlenet_nll_grad_rows_scratch_bytes(int64_t n_rows, int64_t b_ma
 
 // the GN-LeNet gradient entry points.  kGnGradWmfma takes conv2's and conv3's weight gradients out
 // of k_gnl_grad_conv and gives them to k_gnl_grad_wmfma; kGnGradSampleMfma does that and runs the
-// sample pass as k_gnl_grad_sample_mfma, at the shapes that kernel takes
-enum GnGradVariant { kGnGradPlain, kGnGradWmfma, kGnGradSampleMfma };
+// sample pass as k_gnl_grad_sample_mfma, at the shapes that kernel takes; kGnGradConv1Mfma does both
+// and gives conv1's weight gradient to k_gnl_grad_w1mfma
+enum GnGradVariant { kGnGradPlain, kGnGradWmfma, kGnGradSampleMfma, kGnGradConv1Mfma };
 
 static int gn_grad_rows(GnGradVariant variant, const float *theta, int64_t ld_t, const float *data,
                         const int32_t *labels, const int32_t *batch_idx, const int32_t *batch_len,
                         int64_t b_max, const int32_t *rows, int64_t n_rows, float *grad, int64_t ld_g,
                         float *loss, int64_t Cin, int64_t H, int64_t W, int64_t C, void *scratch,
                         int64_t scratch_bytes, void *stream) {
-    const bool mfma = variant != kGnGradPlain;
+    const bool mfma = variant != kGnGradPlain, conv1 = variant == kGnGradConv1Mfma;
+    const bool sample = variant == kGnGradSampleMfma || conv1;
     if (!theta || !data || !labels || !batch_idx || !batch_len || !rows || !grad || !loss || !scratch)
         return set_error(NIIDMIX_EINVAL, "null pointer");
     if (n_rows <= 0 || b_max <= 0 || Cin <= 0 || H <= 0 || W <= 0 || C <= 0)
@@ -6523,7 +6528,7 @@ static int gn_grad_rows(GnGradVariant variant, const float *theta, int64_t ld_t,
     if (!gn_supported(Cin, H, W, C))
         return set_error(NIIDMIX_EUNSUPPORTED, "H %lld, W %lld: the kernel holds %d <= H, W <= %d",
                          (long long)H, (long long)W, kGnMinHW, kGnMaxHW);
-    if (variant == kGnGradSampleMfma && !gn_gsm_takes(gn_shape((int)Cin, (int)H, (int)W, (int)C)))
+    if (sample && !gn_gsm_takes(gn_shape((int)Cin, (int)H, (int)W, (int)C)))
         return set_error(NIIDMIX_EUNSUPPORTED, "H %lld, W %lld: the matrix-core sample pass's tile of 2 "
                          "samples does not fit in LDS", (long long)H, (long long)W);
     if (b_max > kGnGradMaxB)
@@ -6550,7 +6555,7 @@ static int gn_grad_rows(GnGradVariant variant, const float *theta, int64_t ld_t,
     const int64_t n_tiles = gn_tiles(b_max), n_work = n_rows * n_tiles;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const unsigned grid = (unsigned)(n_work < kGnMaxGrid ? n_work : kGnMaxGrid);
-    if (variant == kGnGradSampleMfma) {
+    if (sample) {
         const size_t lds = (size_t)gn_gsm_lds_bytes(g);
         if (lds > 64 * 1024)
             if (int rc = lds_opt_in(k_gnl_grad_sample_mfma, lds, "k_gnl_grad_sample_mfma")) return rc;
@@ -6573,7 +6578,16 @@ static int gn_grad_rows(GnGradVariant variant, const float *theta, int64_t ld_t,
                            (int)b_max, rows, (int)n_rows, (int)n_tiles, g, L, (const float *)sc, grad, ld_g);
         if (int rc = check_launch("k_gnl_grad_wmfma")) return rc;
     }
-    auto kc = pick<true, false>(!mfma, [](auto W23) { return k_gnl_grad_conv<W23()>; });
+    if (conv1) {                                 // a workgroup per row
+        const size_t lds = 4 * (size_t)gn_w1_lds_floats(g.Cin, g.W, gn_w1_geom(g.Cin, g.H, g.W));
+        auto k1 = pick<1, 2, 3, 4>((g.Cin * 25 + 31) / 32, [](auto NT) { return k_gnl_grad_w1mfma<NT()>; });
+        if (lds > 64 * 1024)
+            if (int rc = lds_opt_in(k1, lds, "k_gnl_grad_w1mfma")) return rc;
+        hipLaunchKernelGGL(k1, dim3((unsigned)n_rows), dim3(256), lds, s, data, batch_idx, batch_len,
+                           (int)b_max, rows, (int)n_tiles, g, L, (const float *)sc, grad, ld_g);
+        if (int rc = check_launch("k_gnl_grad_w1mfma")) return rc;
+    }
+    auto kc = conv1 ? k_gnl_grad_conv<false, false> : mfma ? k_gnl_grad_conv<false> : k_gnl_grad_conv<true>;
     hipLaunchKernelGGL(kc, dim3((unsigned)(n_rows * 128)), dim3(256), 0, s, data, batch_idx,
                        batch_len, (int)b_max, rows, (int)n_tiles, g, L, (const float *)sc, grad, ld_g);
     if (int rc = check_launch("k_gnl_grad_conv")) return rc;
@@ -6610,6 +6624,17 @@ int niidmix_gnlenet_nll_grad_rows_mfma_sample_f32(const float *theta, int64_t ld
                                                   int64_t W, int64_t C, void *scratch,
                                                   int64_t scratch_bytes, void *stream) {
     return gn_grad_rows(kGnGradSampleMfma, theta, ld_t, data, labels, batch_idx, batch_len, b_max, rows,
+                        n_rows, grad, ld_g, loss, Cin, H, W, C, scratch, scratch_bytes, stream);
+}
+
+int niidmix_gnlenet_nll_grad_rows_mfma_conv1_f32(const float *theta, int64_t ld_t, const float *data,
+                                                 const int32_t *labels, const int32_t *batch_idx,
+                                                 const int32_t *batch_len, int64_t b_max,
+                                                 const int32_t *rows, int64_t n_rows, float *grad,
+                                                 int64_t ld_g, float *loss, int64_t Cin, int64_t H,
+                                                 int64_t W, int64_t C, void *scratch,
+                                                 int64_t scratch_bytes, void *stream) {
+    return gn_grad_rows(kGnGradConv1Mfma, theta, ld_t, data, labels, batch_idx, batch_len, b_max, rows,
                         n_rows, grad, ld_g, loss, Cin, H, W, C, scratch, scratch_bytes, stream);
 }
 

@@ -23,7 +23,8 @@ With --device-training (params['algorithm']['device-training'], opt-in) a linear
 training runs on the device too: gradient, step and mixing never leave HBM (niidmix.train);
 --device-training-gn-lenet does the same for GN-LeNet models (--device-training-gn-lenet-mfma, with
 it, takes two of its weight gradients from a matrix-core kernel, and
---device-training-gn-lenet-mfma-sample, with both, its sample pass's convolutions too), and
+--device-training-gn-lenet-mfma-sample, with both, its sample pass's convolutions too, and
+--device-training-gn-lenet-mfma-conv1, with all three, conv1's weight gradient), and
 --device-training-sample for
 rounds of the 'sample' topology (the other two flags refuse it).  --device-sampling, with any of
 the three, draws the batches on the device too, from a sample stream of the plugin's own
@@ -923,6 +924,7 @@ def init(nodes, topology, params):
             params["algorithm"].get("device-training-large-batch") or \
             params["algorithm"].get("device-training-gn-lenet-mfma") or \
             params["algorithm"].get("device-training-gn-lenet-mfma-sample") or \
+            params["algorithm"].get("device-training-gn-lenet-mfma-conv1") or \
             params["algorithm"].get("device-sampling-torch-stream"):
         from . import train
         train.check_eligible(nodes, params, topology)     # refusals: ValueError naming the flag
@@ -1162,6 +1164,12 @@ def main(argv=None):
                          "their data gradients run on the matrix cores as well "
                          "(niidmix::gnlenet_nll_grad_rows_mfma_sample), at the shapes it is measured "
                          "faster at; the same bound, other bits in every tensor")
+    ap.add_argument("--device-training-gn-lenet-mfma-conv1", action="store_const", const=True,
+                    default=False,
+                    help="with --device-training-gn-lenet-mfma-sample: conv1's weight gradient comes "
+                         "from a kernel on the matrix cores as well "
+                         "(niidmix::gnlenet_nll_grad_rows_mfma_conv1), at the shapes it is measured "
+                         "faster at; the same bound, other bits in conv1.weight only")
     ap.add_argument("--device-training-sample", action="store_const", const=True, default=False,
                     help="--device-training for runs of the 'sample' topology (sets both keys; "
                          "the other two flags refuse 'sample'): each round the sampled nodes train "
@@ -1231,6 +1239,8 @@ def main(argv=None):
         ap.error("--device-training-gn-lenet-mfma needs --device-training-gn-lenet")
     if args.device_training_gn_lenet_mfma_sample and not args.device_training_gn_lenet_mfma:
         ap.error("--device-training-gn-lenet-mfma-sample needs --device-training-gn-lenet-mfma")
+    if args.device_training_gn_lenet_mfma_conv1 and not args.device_training_gn_lenet_mfma_sample:
+        ap.error("--device-training-gn-lenet-mfma-conv1 needs --device-training-gn-lenet-mfma-sample")
     rundir = m.rundir(args)
     params = m.params(rundir)
     topology = load_topology(rundir)
@@ -1253,6 +1263,8 @@ def main(argv=None):
         **({"device-training-gn-lenet": True} if args.device_training_gn_lenet else {}),
         **({"device-training-gn-lenet-mfma": True} if args.device_training_gn_lenet_mfma else {}),
         **({"device-training-gn-lenet-mfma-sample": True} if args.device_training_gn_lenet_mfma_sample
+           else {}),
+        **({"device-training-gn-lenet-mfma-conv1": True} if args.device_training_gn_lenet_mfma_conv1
            else {}),
         **({"device-training-sample": True} if args.device_training_sample else {}),
         **({"device-training-large-batch": True} if args.device_training_large_batch else {}),

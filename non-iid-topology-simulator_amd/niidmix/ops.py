@@ -49,6 +49,10 @@ Ops (registered in the `niidmix` namespace, usable as torch.ops.niidmix.*):
                                                     pass (its conv2 / conv3 and their data gradients
                                                     on the matrix cores, where gn_mfma_tile(H, W) > 0,
                                                     --device-training-gn-lenet-mfma-sample)
+  gnlenet_nll_grad_rows_mfma_conv1(the same arguments)
+                                                    the same with k_gnl_grad_w1mfma for conv1's weight
+                                                    gradient (the matrix cores, the same shapes,
+                                                    --device-training-gn-lenet-mfma-conv1)
   gnlenet_eval_rows(theta, data, labels, rows, seg_start, seg_len, max_len, loss_sum, correct, pred,
                     logits, Cin, H, W, C)           k_gnl_eval + k_lin_eval_sum (the same for GN-LeNet)
   gnlenet_eval_rows_mfma(the same arguments)        k_gnl_eval_mfma + k_lin_eval_sum (conv2 / conv3 on
@@ -1002,6 +1006,18 @@ def gnlenet_nll_grad_rows_mfma_sample(theta: torch.Tensor, data: torch.Tensor, l
     them, and its backward's buffers fit wherever its forward's do); any other is the launcher's
     NIIDMIX_EUNSUPPORTED."""
     _gnlenet_grad("gnlenet_nll_grad_rows_mfma_sample", theta, data, labels, batch_idx, batch_len, rows,
+                  grad, loss, Cin, H, W, C)
+
+
+@torch.library.custom_op("niidmix::gnlenet_nll_grad_rows_mfma_conv1", mutates_args=("grad", "loss"))
+def gnlenet_nll_grad_rows_mfma_conv1(theta: torch.Tensor, data: torch.Tensor, labels: torch.Tensor,
+                                     batch_idx: torch.Tensor, batch_len: torch.Tensor, rows: torch.Tensor,
+                                     grad: torch.Tensor, loss: torch.Tensor,
+                                     Cin: int, H: int, W: int, C: int) -> None:
+    """gnlenet_nll_grad_rows_mfma_sample with conv1's weight gradient on the matrix cores as well
+    (include/niidmix.h, niidmix_gnlenet_nll_grad_rows_mfma_conv1_f32): the same arguments, checks,
+    shapes, scratch and bound; conv1.weight in another summation order, everything else bit for bit."""
+    _gnlenet_grad("gnlenet_nll_grad_rows_mfma_conv1", theta, data, labels, batch_idx, batch_len, rows,
                   grad, loss, Cin, H, W, C)
 
 

@@ -19,9 +19,11 @@
 GN-LeNet (niidmix_gnlenet_nll_grad_rows_f32, --device-training-gn-lenet), at the two shapes
     gn-cifar   N 1000, 3 x 32 x 32, C 10, B 20     gn-mnist   N 100, 1 x 28 x 28, C 10, B 128
   gn-kernel  the gradient call, niidmix_gnlenet_nll_grad_rows_mfma_f32 (grad_mfma; conv2's and
-             conv3's weight gradients on the matrix cores) and
+             conv3's weight gradients on the matrix cores),
              niidmix_gnlenet_nll_grad_rows_mfma_sample_f32 (grad_mfma_sample; the sample pass's
-             convolutions there too) against three yardsticks, all six alternating within every
+             convolutions there too) and niidmix_gnlenet_nll_grad_rows_mfma_conv1_f32
+             (grad_mfma_conv1; conv1's weight gradient too) against three yardsticks, all seven
+             alternating within every
              repetition: the CPU loop (forward + nll_loss + backward of the module, torch's
              threads as set, on a few nodes, scaled to N), torch autograd on the device (the
              same module, looped over a few nodes, scaled to N), and niidmix_stream_copy_f32 over
@@ -29,7 +31,8 @@ GN-LeNet (niidmix_gnlenet_nll_grad_rows_f32, --device-training-gn-lenet), at the
              device events, the CPU loop by the host clock.
   gn-rounds  as `rounds`, for GN-LeNet models and the --device-training-gn-lenet flag; with
              --gn-mfma the device run sets --device-training-gn-lenet-mfma as well, with
-             --gn-mfma-sample --device-training-gn-lenet-mfma-sample too (a process holds one live
+             --gn-mfma-sample --device-training-gn-lenet-mfma-sample too, with --gn-mfma-conv1
+             --device-training-gn-lenet-mfma-conv1 on top of both (a process holds one live
              trainer, so base and new flag are two invocations).
 
     python tools/device_training_probe.py gn-kernel --shape gn-cifar [--warmup 5] [--reps 20]
@@ -165,6 +168,8 @@ def gn_kernel(a):
              ("grad_mfma", lambda: grad_call(lib.niidmix_gnlenet_nll_grad_rows_mfma_f32), 1.0, True),
              ("grad_mfma_sample", lambda: grad_call(lib.niidmix_gnlenet_nll_grad_rows_mfma_sample_f32), 1.0,
               True),
+             ("grad_mfma_conv1", lambda: grad_call(lib.niidmix_gnlenet_nll_grad_rows_mfma_conv1_f32), 1.0,
+              True),
              ("device_autograd", lambda: loop(mdl_dev, xb, yb, n_dev), n / n_dev, True),
              ("cpu_loop", lambda: loop(mdl, xc, yc, n_cpu), n / n_cpu, False)]
     times = {name: [] for name, _, _, _ in cands}
@@ -200,6 +205,12 @@ def gn_kernel(a):
     out["grad_mfma_sample_over_grad_mfma"] = out["grad_mfma_sample"]["median_ms"] / out["grad_mfma"]["median_ms"]
     out["grad_mfma_sample_faster"] = out["grad_mfma"]["median_ms"] - out["grad_mfma_sample"]["median_ms"] > \
         out["grad_mfma"]["max_ms"] - out["grad_mfma"]["min_ms"]
+    # and for family.GRAD_MFMA_CONV1_FASTER, against grad_mfma_sample
+    out["grad_mfma_conv1_over_grad_mfma_sample"] = \
+        out["grad_mfma_conv1"]["median_ms"] / out["grad_mfma_sample"]["median_ms"]
+    out["grad_mfma_conv1_faster"] = \
+        out["grad_mfma_sample"]["median_ms"] - out["grad_mfma_conv1"]["median_ms"] > \
+        out["grad_mfma_sample"]["max_ms"] - out["grad_mfma_sample"]["min_ms"]
     print(json.dumps(out))
 
 
@@ -376,6 +387,8 @@ def rounds(a):
         family.GN_LENET.GRAD_MFMA_FASTER = dict.fromkeys(family.GN_LENET.GRAD_MFMA_FASTER, True)
         if a.gn_mfma_sample:
             family.GRAD_MFMA_SAMPLE_FASTER = dict.fromkeys(family.GRAD_MFMA_SAMPLE_FASTER, True)
+            if a.gn_mfma_conv1:
+                family.GRAD_MFMA_CONV1_FASTER = dict.fromkeys(family.GRAD_MFMA_CONV1_FASTER, True)
     for flag in (False, True):
         torch.manual_seed(7)
         params = {"meta": {"log": "WARNING", "seed": 7}, "model": {"input-size": k},
@@ -392,6 +405,8 @@ def rounds(a):
             params["algorithm"]["device-training-gn-lenet-mfma"] = True
             if a.gn_mfma_sample:
                 params["algorithm"]["device-training-gn-lenet-mfma-sample"] = True
+                if a.gn_mfma_conv1:
+                    params["algorithm"]["device-training-gn-lenet-mfma-conv1"] = True
         ts = [(x[j], int(y[j])) for j in range(per_node)]
         nodes = []
         for r in range(n):
@@ -413,6 +428,7 @@ def rounds(a):
     out = {"step": "gn-rounds" if gn else "rounds", "shape": a.shape, "n": n, "k": k, "c": c, "b": b, "mode": a.mode,
            "clique_gradient": a.clique_gradient, "momentum": a.momentum, "gn_mfma": bool(gn and a.gn_mfma),
            "gn_mfma_sample": bool(gn and a.gn_mfma and a.gn_mfma_sample),
+           "gn_mfma_conv1": bool(gn and a.gn_mfma and a.gn_mfma_sample and a.gn_mfma_conv1),
            "warmup": a.warmup, "rounds": a.rounds, "threads": torch.get_num_threads(),
            "device": torch.cuda.get_device_name(0)}
     for flag, key in ((False, "flag_off"), (True, "flag_on")):
@@ -618,6 +634,8 @@ def main():
                     help="gn-rounds: the device run also sets --device-training-gn-lenet-mfma")
     ap.add_argument("--gn-mfma-sample", action="store_true",
                     help="gn-rounds, with --gn-mfma: and --device-training-gn-lenet-mfma-sample")
+    ap.add_argument("--gn-mfma-conv1", action="store_true",
+                    help="gn-rounds, with both: and --device-training-gn-lenet-mfma-conv1")
     a = ap.parse_args()
     if a.step == "all":
         return run_all(a)
