@@ -898,6 +898,32 @@ int niidmix_gnlenet_nll_grad_rows_mfma_conv1_f32(const float *theta, int64_t ld_
                                                  int64_t W, int64_t C, void *scratch,
                                                  int64_t scratch_bytes, void *stream);
 
+/* niidmix_gnlenet_nll_grad_rows_mfma_conv1_f32 with the sample pass's conv1 on the matrix cores as
+ * well (k_gnl_grad_sample_mfma<true>; the drop-in's --device-training-gn-lenet-mfma-fwd1).
+ * Arguments, limits (the same shapes: 15 <= H, W <= 42; anything beyond is NIIDMIX_EUNSUPPORTED),
+ * scratch layout and size, checks and their order are those of
+ * niidmix_gnlenet_nll_grad_rows_mfma_conv1_f32.  What differs:
+ *   conv1     conv1 + max-pool is a banded implicit GEMM on v_mfma_f32_32x32x2_f32: M = the
+ *             full-resolution output positions of a band of pooled rows of one sample, N = the 32
+ *             output channels, K = 25 Cin in the order (ci, ky, kx) ascending from 0 (an odd K gets
+ *             one pad k of 0 * 0).  Every conv output is computed once per band (the row two bands
+ *             share twice, to the same bits) and is one K-order chain whatever its place; the pool
+ *             takes the first maximum in window order (a NaN wins and stays) and adds the bias after
+ *             it, as the other entries do.
+ *   the bits  all 14 tensors and the loss may differ in the last bits from the _mfma_conv1 entry's;
+ *             the same bound of 4 e32 (tests/test_gpu_train_gnlenet_mfma_fwd1.py).
+ *   NaN/inf   a halo position contributes 0 * w: a non-finite conv1 weight reaches the border
+ *             outputs through the halo as well.  It stays in its row.
+ * Determinism, independence of the other rows and of the cut of the row list, no atomics, theta
+ * not written: as niidmix_gnlenet_nll_grad_rows_f32. */
+int niidmix_gnlenet_nll_grad_rows_mfma_fwd1_f32(const float *theta, int64_t ld_t, const float *data,
+                                                const int32_t *labels, const int32_t *batch_idx,
+                                                const int32_t *batch_len, int64_t b_max,
+                                                const int32_t *rows, int64_t n_rows, float *grad,
+                                                int64_t ld_g, float *loss, int64_t Cin, int64_t H,
+                                                int64_t W, int64_t C, void *scratch,
+                                                int64_t scratch_bytes, void *stream);
+
 /* Training batches drawn on the device (the drop-in's --device-sampling): job j writes the batch
  * that starts at position cursor[j] of epoch epoch[j]'s permutation of the segment
  * [seg_start[j], seg_start[j] + seg_len[j]) of the caller's concatenated data, in the layout

@@ -3,6 +3,8 @@
 // after model_gnlenet_grad_mfma.inc; it uses gn_conv_mfma, gn_halo_expand and gn_halo_zero of
 // model_gnlenet_mfma.inc and the VALU functions of model_gnlenet.inc.
 // ----------------------------------------------------------------------------------------------
+// k_gnl_grad_sample_mfma<true> (niidmix_gnlenet_nll_grad_rows_mfma_fwd1_f32) runs conv1 there as well,
+// through gn_conv1_pool_mfma of model_gnlenet_conv1_mfma.inc; what follows describes both.
 // Job model, scratch slot (GnGradLay) and outputs are k_gnl_grad_sample's: one work item per (row
 // entry, tile of kGnTS = 2 samples) on a persistent grid, and every array a later kernel reads
 // (p1, x2, y2, dy2, dx2, x3, y3, dy3, feat, dz, nll, st1..3, gp1..3, amax) lands in the slot in the
@@ -59,6 +61,10 @@ __device__ __forceinline__ void gn_gsm_store(float *dst, const float *src, int n
     for (int e = threadIdx.x; e < n; e += 256) dst[e] = src[e];
 }
 
+// C1M: conv1 + pool as gn_conv1_pool_mfma (model_gnlenet_conv1_mfma.inc), its stage behind p1 in
+// `buf` (and in the unused part of `ws`), in a dynamic LDS of gn_c1_geom's size where that is more;
+// every later step is the same.  <false> is the kernel as it was.
+template <bool C1M>
 __global__ __launch_bounds__(256) void k_gnl_grad_sample_mfma(const float *__restrict__ theta, int64_t ld_t,
                                                               const float *__restrict__ data,
                                                               const int32_t *__restrict__ labels,
@@ -88,8 +94,13 @@ __global__ __launch_bounds__(256) void k_gnl_grad_sample_mfma(const float *__res
         float *T = scratch + wk * L.tile;
 
         // forward: every map passes through LDS and is kept in the slot
-        gn_conv1_pool<true>([&](int s) { return data + (int64_t)bi[s < ns ? s : 0] * sample; }, g, th,
-                            buf, ws, reinterpret_cast<unsigned char *>(T + L.amax));
+        if constexpr (C1M)
+            gn_conv1_pool_mfma<true>([&](int s) { return data + (int64_t)bi[s < ns ? s : 0] * sample; }, g, th,
+                                     buf, ws, buf + a1, gn_c1_geom(g.Cin, g.H, g.W, kGnTS, kGnWFloats + kGnStat),
+                                     reinterpret_cast<unsigned char *>(T + L.amax));
+        else
+            gn_conv1_pool<true>([&](int s) { return data + (int64_t)bi[s < ns ? s : 0] * sample; }, g, th,
+                                buf, ws, reinterpret_cast<unsigned char *>(T + L.amax));
         gn_stats<32>(buf, hw1, th + g.g1w, th + g.g1b, stat);
         gn_gsm_store(T + L.st1, stat, kGnStat);
         for (int e = tid; e < a1; e += 256) {

@@ -43,6 +43,8 @@
 //                                                                  niidmix_gnlenet_nll_grad_rows_f32
 //   model_gnlenet_mfma.inc  k_gnl_eval_mfma (conv2 / conv3 on the  niidmix_gnlenet_eval_rows_mfma_f32
 //                      fp32 matrix cores, 4 or 2 samples a tile)
+//   model_gnlenet_conv1_mfma.inc  gn_conv1_pool_mfma (conv1 + pool  niidmix_gnlenet_nll_grad_rows_mfma_fwd1_f32
+//                      as a banded GEMM on the matrix cores)
 //   model_gnlenet_grad_mfma.inc  k_gnl_grad_wmfma (conv2 / conv3     niidmix_gnlenet_nll_grad_rows_mfma_f32
 //                      weight gradients on the matrix cores)
 //   model_gnlenet_grad_sample_mfma.inc  k_gnl_grad_sample_mfma     niidmix_gnlenet_nll_grad_rows_mfma_sample_f32
@@ -4956,6 +4958,7 @@ __global__ __launch_bounds__(256) void k_lin_eval_sum(const int32_t *__restrict_
 #include "model_gnlenet.inc"
 
 #include "model_gnlenet_mfma.inc"
+#include "model_gnlenet_conv1_mfma.inc"
 #include "model_gnlenet_grad_mfma.inc"
 #include "model_gnlenet_grad_sample_mfma.inc"
 #include "model_gnlenet_grad_conv1_mfma.inc"
@@ -6509,15 +6512,17 @@ int64_t niidmix_gnlenet_nll_grad_rows_scratch_bytes(int64_t n_rows, int64_t b_ma
 // the GN-LeNet gradient entry points.  kGnGradWmfma takes conv2's and conv3's weight gradients out
 // of k_gnl_grad_conv and gives them to k_gnl_grad_wmfma; kGnGradSampleMfma does that and runs the
 // sample pass as k_gnl_grad_sample_mfma, at the shapes that kernel takes; kGnGradConv1Mfma does both
-// and gives conv1's weight gradient to k_gnl_grad_w1mfma
-enum GnGradVariant { kGnGradPlain, kGnGradWmfma, kGnGradSampleMfma, kGnGradConv1Mfma };
+// and gives conv1's weight gradient to k_gnl_grad_w1mfma; kGnGradFwd1Mfma is that with the sample
+// pass's conv1 on the matrix cores too (k_gnl_grad_sample_mfma<true>, LDS by gn_c1_geom)
+enum GnGradVariant { kGnGradPlain, kGnGradWmfma, kGnGradSampleMfma, kGnGradConv1Mfma, kGnGradFwd1Mfma };
 
 static int gn_grad_rows(GnGradVariant variant, const float *theta, int64_t ld_t, const float *data,
                         const int32_t *labels, const int32_t *batch_idx, const int32_t *batch_len,
                         int64_t b_max, const int32_t *rows, int64_t n_rows, float *grad, int64_t ld_g,
                         float *loss, int64_t Cin, int64_t H, int64_t W, int64_t C, void *scratch,
                         int64_t scratch_bytes, void *stream) {
-    const bool mfma = variant != kGnGradPlain, conv1 = variant == kGnGradConv1Mfma;
+    const bool mfma = variant != kGnGradPlain, fwd1 = variant == kGnGradFwd1Mfma;
+    const bool conv1 = variant == kGnGradConv1Mfma || fwd1;
     const bool sample = variant == kGnGradSampleMfma || conv1;
     if (!theta || !data || !labels || !batch_idx || !batch_len || !rows || !grad || !loss || !scratch)
         return set_error(NIIDMIX_EINVAL, "null pointer");
@@ -6531,6 +6536,14 @@ static int gn_grad_rows(GnGradVariant variant, const float *theta, int64_t ld_t,
     if (sample && !gn_gsm_takes(gn_shape((int)Cin, (int)H, (int)W, (int)C)))
         return set_error(NIIDMIX_EUNSUPPORTED, "H %lld, W %lld: the matrix-core sample pass's tile of 2 "
                          "samples does not fit in LDS", (long long)H, (long long)W);
+    int c1_lds_floats = 0;
+    if (fwd1) {                                  // a band of pooled rows next to the tile's p1
+        const GnC1Geom q1 = gn_c1_geom((int)Cin, (int)H, (int)W, kGnTS, kGnWFloats + kGnStat);
+        if (q1.pb < 1)
+            return set_error(NIIDMIX_EUNSUPPORTED, "H %lld, W %lld: no band of conv1's matrix-core pass "
+                             "fits in LDS", (long long)H, (long long)W);
+        c1_lds_floats = q1.lds_floats;
+    }
     if (b_max > kGnGradMaxB)
         return set_error(NIIDMIX_EUNSUPPORTED, "b_max %lld > 2^24", (long long)b_max);
     const GnShape g = gn_shape((int)Cin, (int)H, (int)W, (int)C);
@@ -6556,10 +6569,12 @@ static int gn_grad_rows(GnGradVariant variant, const float *theta, int64_t ld_t,
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const unsigned grid = (unsigned)(n_work < kGnMaxGrid ? n_work : kGnMaxGrid);
     if (sample) {
-        const size_t lds = (size_t)gn_gsm_lds_bytes(g);
+        size_t lds = (size_t)gn_gsm_lds_bytes(g);
+        if (fwd1 && 4 * (size_t)c1_lds_floats > lds) lds = 4 * (size_t)c1_lds_floats;
+        auto k1 = fwd1 ? k_gnl_grad_sample_mfma<true> : k_gnl_grad_sample_mfma<false>;
         if (lds > 64 * 1024)
-            if (int rc = lds_opt_in(k_gnl_grad_sample_mfma, lds, "k_gnl_grad_sample_mfma")) return rc;
-        hipLaunchKernelGGL(k_gnl_grad_sample_mfma, dim3(grid), dim3(256), lds, s, theta, ld_t, data, labels,
+            if (int rc = lds_opt_in(k1, lds, "k_gnl_grad_sample_mfma")) return rc;
+        hipLaunchKernelGGL(k1, dim3(grid), dim3(256), lds, s, theta, ld_t, data, labels,
                            batch_idx, batch_len, (int)b_max, rows, n_rows, (int)n_tiles, g, L, sc);
         if (int rc = check_launch("k_gnl_grad_sample_mfma")) return rc;
     } else {
@@ -6635,6 +6650,17 @@ int niidmix_gnlenet_nll_grad_rows_mfma_conv1_f32(const float *theta, int64_t ld_
                                                  int64_t W, int64_t C, void *scratch,
                                                  int64_t scratch_bytes, void *stream) {
     return gn_grad_rows(kGnGradConv1Mfma, theta, ld_t, data, labels, batch_idx, batch_len, b_max, rows,
+                        n_rows, grad, ld_g, loss, Cin, H, W, C, scratch, scratch_bytes, stream);
+}
+
+int niidmix_gnlenet_nll_grad_rows_mfma_fwd1_f32(const float *theta, int64_t ld_t, const float *data,
+                                                const int32_t *labels, const int32_t *batch_idx,
+                                                const int32_t *batch_len, int64_t b_max,
+                                                const int32_t *rows, int64_t n_rows, float *grad,
+                                                int64_t ld_g, float *loss, int64_t Cin, int64_t H,
+                                                int64_t W, int64_t C, void *scratch,
+                                                int64_t scratch_bytes, void *stream) {
+    return gn_grad_rows(kGnGradFwd1Mfma, theta, ld_t, data, labels, batch_idx, batch_len, b_max, rows,
                         n_rows, grad, ld_g, loss, Cin, H, W, C, scratch, scratch_bytes, stream);
 }
 

@@ -2,7 +2,7 @@
 niidmix.evaluate evaluates, stated once.  LINEAR (setup/model/linear.py: one nn.Linear(K, C),
 log_softmax) and GN_LENET (setup/model/gn_lenet.py) have the same methods, apart from each one's own
 routing rule (LINEAR.sliced; GN_LENET.grad_mfma, grad_mfma_class, mfma; the module's
-grad_mfma_sample and grad_mfma_conv1); family_of(model) picks one
+grad_mfma_sample, grad_mfma_conv1 and grad_mfma_fwd1); family_of(model) picks one
 from the parameters' shapes.  A family knows its shape(model) -- (K, C) / (Cin, C, F), C is
 shape[1] in both -- and P(shape); the kernels' limits as refusals (the constants are niidmix.ops',
 which checks its arguments against the same ones); sizes(), the one sample check, giving the
@@ -12,13 +12,14 @@ ops.gnlenet_shapes, one table: the expected shapes, the offsets, the row splitte
 from it.  The float64 yardsticks of the probes and of the GPU tests live here as well.
 
 The kernel variant is bound once, in a plan: grad_plan(sizes, b_max, large=False, mfma=False,
-mfma_sample=False, mfma_conv1=False) and eval_plan(sizes, mfma=False) apply the family's rule,
+mfma_sample=False, mfma_conv1=False, mfma_fwd1=False) and eval_plan(sizes, mfma=False) apply the
+family's rule,
 reading its table then, to the opt-in switches (`large`: --device-training-large-batch; `mfma`:
 --device-training-gn-lenet-mfma / --device-evaluation-mfma; `mfma_sample`:
---device-training-gn-lenet-mfma-sample; `mfma_conv1`: --device-training-gn-lenet-mfma-conv1) and
-return a GradPlan / EvalPlan.  A family ignores a switch that is not its own (LINEAR `mfma`,
-`mfma_sample` and `mfma_conv1`, GN_LENET `large`), so the callers pass every switch to either
-family.
+--device-training-gn-lenet-mfma-sample; `mfma_conv1`: --device-training-gn-lenet-mfma-conv1;
+`mfma_fwd1`: --device-training-gn-lenet-mfma-fwd1) and return a GradPlan / EvalPlan.  A family
+ignores a switch that is not its own (LINEAR `mfma`, `mfma_sample`, `mfma_conv1` and `mfma_fwd1`,
+GN_LENET `large`), so the callers pass every switch to either family.
 """
 import copy
 import math
@@ -242,7 +243,8 @@ class _Linear:
         the existing kernel does not take its shape."""
         return bool(large) and b_max * sizes[1] > MAX_BC
 
-    def grad_plan(self, sizes, b_max, large=False, mfma=False, mfma_sample=False, mfma_conv1=False):
+    def grad_plan(self, sizes, b_max, large=False, mfma=False, mfma_sample=False, mfma_conv1=False,
+                  mfma_fwd1=False):
         if self.sliced(b_max, sizes, large):         # the scratch sizes are in fp32 elements
             op, dims = ops.linear_nll_grad_rows_sliced, sizes
             elems = lib.niidmix_linear_nll_grad_rows_sliced_scratch_elems
@@ -314,6 +316,22 @@ def grad_mfma_conv1(sizes, mfma, mfma_sample, flag):
         GRAD_MFMA_CONV1_FASTER.get(ops.gn_mfma_tile(sizes[1], sizes[2]), False)
 
 
+# --device-training-gn-lenet-mfma-fwd1's shape classes are the same tiles.  True where
+# tools/device_training_probe.py gn-kernel measured the call's median below
+# gnlenet_nll_grad_rows_mfma_conv1's by more than that call's own spread in the same run (DESIGN.md
+# section 5: tile 4 at 100 rows x 1 x 28 x 28 x batch 128, tile 2 at 1000 rows x 3 x 32 x 32 x batch
+# 20; profiles/gnlenet_grad_fwd1_mfma/).  A class that is not keeps the plan it had.
+GRAD_MFMA_FWD1_FASTER = {4: False, 2: False}
+
+
+def grad_mfma_fwd1(sizes, mfma, mfma_sample, mfma_conv1, flag):
+    """Under the four flags a GN-LeNet call goes to the op with the sample pass's conv1 on the matrix
+    cores exactly when grad_mfma_conv1 routes the shape to its op (the new one is that op with
+    another sample kernel) and the new op is the measured faster one at the shape's class."""
+    return grad_mfma_conv1(sizes, mfma, mfma_sample, mfma_conv1) and bool(flag) and \
+        GRAD_MFMA_FWD1_FASTER.get(ops.gn_mfma_tile(sizes[1], sizes[2]), False)
+
+
 class _GNLeNet:
     kind = "gn-lenet"
     cut = True           # a row's bits do not depend on the cut
@@ -368,8 +386,11 @@ class _GNLeNet:
         when that op is the measured faster one at the shape's class."""
         return bool(flag) and self.GRAD_MFMA_FASTER[self.grad_mfma_class(sizes)]
 
-    def grad_plan(self, sizes, b_max, large=False, mfma=False, mfma_sample=False, mfma_conv1=False):
-        if grad_mfma_conv1(sizes, mfma, mfma_sample, mfma_conv1):
+    def grad_plan(self, sizes, b_max, large=False, mfma=False, mfma_sample=False, mfma_conv1=False,
+                  mfma_fwd1=False):
+        if grad_mfma_fwd1(sizes, mfma, mfma_sample, mfma_conv1, mfma_fwd1):
+            op = ops.gnlenet_nll_grad_rows_mfma_fwd1
+        elif grad_mfma_conv1(sizes, mfma, mfma_sample, mfma_conv1):
             op = ops.gnlenet_nll_grad_rows_mfma_conv1
         elif grad_mfma_sample(sizes, mfma, mfma_sample):
             op = ops.gnlenet_nll_grad_rows_mfma_sample

@@ -53,6 +53,10 @@ Ops (registered in the `niidmix` namespace, usable as torch.ops.niidmix.*):
                                                     the same with k_gnl_grad_w1mfma for conv1's weight
                                                     gradient (the matrix cores, the same shapes,
                                                     --device-training-gn-lenet-mfma-conv1)
+  gnlenet_nll_grad_rows_mfma_fwd1(the same arguments)
+                                                    the same with k_gnl_grad_sample_mfma<true> as the
+                                                    sample pass (its conv1 on the matrix cores too,
+                                                    --device-training-gn-lenet-mfma-fwd1)
   gnlenet_eval_rows(theta, data, labels, rows, seg_start, seg_len, max_len, loss_sum, correct, pred,
                     logits, Cin, H, W, C)           k_gnl_eval + k_lin_eval_sum (the same for GN-LeNet)
   gnlenet_eval_rows_mfma(the same arguments)        k_gnl_eval_mfma + k_lin_eval_sum (conv2 / conv3 on
@@ -1018,6 +1022,18 @@ def gnlenet_nll_grad_rows_mfma_conv1(theta: torch.Tensor, data: torch.Tensor, la
     (include/niidmix.h, niidmix_gnlenet_nll_grad_rows_mfma_conv1_f32): the same arguments, checks,
     shapes, scratch and bound; conv1.weight in another summation order, everything else bit for bit."""
     _gnlenet_grad("gnlenet_nll_grad_rows_mfma_conv1", theta, data, labels, batch_idx, batch_len, rows,
+                  grad, loss, Cin, H, W, C)
+
+
+@torch.library.custom_op("niidmix::gnlenet_nll_grad_rows_mfma_fwd1", mutates_args=("grad", "loss"))
+def gnlenet_nll_grad_rows_mfma_fwd1(theta: torch.Tensor, data: torch.Tensor, labels: torch.Tensor,
+                                    batch_idx: torch.Tensor, batch_len: torch.Tensor, rows: torch.Tensor,
+                                    grad: torch.Tensor, loss: torch.Tensor,
+                                    Cin: int, H: int, W: int, C: int) -> None:
+    """gnlenet_nll_grad_rows_mfma_conv1 with the sample pass's conv1 on the matrix cores as well
+    (include/niidmix.h, niidmix_gnlenet_nll_grad_rows_mfma_fwd1_f32): the same arguments, checks,
+    shapes, scratch and bound; every tensor and the loss may differ in the last bits."""
+    _gnlenet_grad("gnlenet_nll_grad_rows_mfma_fwd1", theta, data, labels, batch_idx, batch_len, rows,
                   grad, loss, Cin, H, W, C)
 
 

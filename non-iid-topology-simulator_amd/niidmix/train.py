@@ -31,7 +31,8 @@ where niidmix.family's rule sends the shape; nothing else of the round changes.
 niidmix::gnlenet_nll_grad_rows_mfma_sample (the sample pass's conv2 / conv3 and their data gradients
 on the matrix cores too) under the same kind of rule, and `--device-training-gn-lenet-mfma-conv1`,
 valid only with all three, for niidmix::gnlenet_nll_grad_rows_mfma_conv1 (conv1's weight gradient on
-the matrix cores as well).
+the matrix cores as well), and `--device-training-gn-lenet-mfma-fwd1`, valid only with all four, for
+niidmix::gnlenet_nll_grad_rows_mfma_fwd1 (the sample pass's conv1 there too).
 
 What depends on the model family -- shapes, the kernels' limits, the sample check, the gradient op
 and its scratch, the forward probe -- is niidmix.family's; DeviceTrainer holds a family, its
@@ -133,6 +134,7 @@ FLAG_GN = "--device-training-gn-lenet"
 FLAG_GN_MFMA = "--device-training-gn-lenet-mfma"
 FLAG_GN_MFMA_SAMPLE = "--device-training-gn-lenet-mfma-sample"
 FLAG_GN_MFMA_CONV1 = "--device-training-gn-lenet-mfma-conv1"
+FLAG_GN_MFMA_FWD1 = "--device-training-gn-lenet-mfma-fwd1"
 FLAG_SAMPLE = "--device-training-sample"
 FLAG_SAMPLING = "--device-sampling"
 FLAG_CACHED = "--device-sampling-cached"
@@ -176,6 +178,13 @@ def gn_mfma_conv1_enabled(params):
     gradient goes to the op that also computes conv1's weight gradient on the matrix cores, where
     niidmix.family's rule sends the shape."""
     return bool(params.get("algorithm", {}).get("device-training-gn-lenet-mfma-conv1"))
+
+
+def gn_mfma_fwd1_enabled(params):
+    """--device-training-gn-lenet-mfma-fwd1: with --device-training-gn-lenet-mfma-conv1, the
+    gradient goes to the op whose sample pass runs conv1 on the matrix cores as well, where
+    niidmix.family's rule sends the shape."""
+    return bool(params.get("algorithm", {}).get("device-training-gn-lenet-mfma-fwd1"))
 
 
 def sample_run(params):
@@ -366,6 +375,8 @@ def check_eligible(nodes, params, topology=None):
         raise ValueError(f"{FLAG_GN_MFMA_SAMPLE} needs {FLAG_GN_MFMA}")
     if gn_mfma_conv1_enabled(params) and not gn_mfma_sample_enabled(params):
         raise ValueError(f"{FLAG_GN_MFMA_CONV1} needs {FLAG_GN_MFMA_SAMPLE}")
+    if gn_mfma_fwd1_enabled(params) and not gn_mfma_conv1_enabled(params):
+        raise ValueError(f"{FLAG_GN_MFMA_FWD1} needs {FLAG_GN_MFMA_CONV1}")
     flag = flag_of(params)
     sample = sample_run(params)
     large = large_enabled(params)
@@ -488,7 +499,8 @@ class DeviceTrainer:
         xs, ys, self.offsets = self._materialise(nodes)
         # the gradient call, its kernel variant bound for the trainer's life
         self.plan = self.family.grad_plan(self.sizes, self.b_max, self.large, gn_mfma_enabled(params),
-                                          gn_mfma_sample_enabled(params), gn_mfma_conv1_enabled(params))
+                                          gn_mfma_sample_enabled(params), gn_mfma_conv1_enabled(params),
+                                          gn_mfma_fwd1_enabled(params))
         self._check_fit(xs)
         dev = self.device
         self.data = xs.to(dev)

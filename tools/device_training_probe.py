@@ -24,7 +24,8 @@ GN-LeNet (niidmix_gnlenet_nll_grad_rows_f32, --device-training-gn-lenet), at the
              convolutions there too) and niidmix_gnlenet_nll_grad_rows_mfma_conv1_f32
              (grad_mfma_conv1; conv1's weight gradient too) against three yardsticks, all seven
              alternating within every
-             repetition: the CPU loop (forward + nll_loss + backward of the module, torch's
+             repetition (with --gn-mfma-fwd1 niidmix_gnlenet_nll_grad_rows_mfma_fwd1_f32,
+             grad_mfma_fwd1, the sample pass's conv1 too, is an eighth): the CPU loop (forward + nll_loss + backward of the module, torch's
              threads as set, on a few nodes, scaled to N), torch autograd on the device (the
              same module, looped over a few nodes, scaled to N), and niidmix_stream_copy_f32 over
              the bytes the call must read (parameters and batch samples).  Device candidates by
@@ -32,7 +33,8 @@ GN-LeNet (niidmix_gnlenet_nll_grad_rows_f32, --device-training-gn-lenet), at the
   gn-rounds  as `rounds`, for GN-LeNet models and the --device-training-gn-lenet flag; with
              --gn-mfma the device run sets --device-training-gn-lenet-mfma as well, with
              --gn-mfma-sample --device-training-gn-lenet-mfma-sample too, with --gn-mfma-conv1
-             --device-training-gn-lenet-mfma-conv1 on top of both (a process holds one live
+             --device-training-gn-lenet-mfma-conv1 on top of both, with --gn-mfma-fwd1
+             --device-training-gn-lenet-mfma-fwd1 on top of the three (a process holds one live
              trainer, so base and new flag are two invocations).
 
     python tools/device_training_probe.py gn-kernel --shape gn-cifar [--warmup 5] [--reps 20]
@@ -170,6 +172,8 @@ def gn_kernel(a):
               True),
              ("grad_mfma_conv1", lambda: grad_call(lib.niidmix_gnlenet_nll_grad_rows_mfma_conv1_f32), 1.0,
               True),
+             *([("grad_mfma_fwd1", lambda: grad_call(lib.niidmix_gnlenet_nll_grad_rows_mfma_fwd1_f32), 1.0,
+                 True)] if a.gn_mfma_fwd1 else []),
              ("device_autograd", lambda: loop(mdl_dev, xb, yb, n_dev), n / n_dev, True),
              ("cpu_loop", lambda: loop(mdl, xc, yc, n_cpu), n / n_cpu, False)]
     times = {name: [] for name, _, _, _ in cands}
@@ -211,6 +215,12 @@ def gn_kernel(a):
     out["grad_mfma_conv1_faster"] = \
         out["grad_mfma_sample"]["median_ms"] - out["grad_mfma_conv1"]["median_ms"] > \
         out["grad_mfma_sample"]["max_ms"] - out["grad_mfma_sample"]["min_ms"]
+    if a.gn_mfma_fwd1:                       # and for family.GRAD_MFMA_FWD1_FASTER, against grad_mfma_conv1
+        out["grad_mfma_fwd1_over_grad_mfma_conv1"] = \
+            out["grad_mfma_fwd1"]["median_ms"] / out["grad_mfma_conv1"]["median_ms"]
+        out["grad_mfma_fwd1_faster"] = \
+            out["grad_mfma_conv1"]["median_ms"] - out["grad_mfma_fwd1"]["median_ms"] > \
+            out["grad_mfma_conv1"]["max_ms"] - out["grad_mfma_conv1"]["min_ms"]
     print(json.dumps(out))
 
 
@@ -389,6 +399,8 @@ def rounds(a):
             family.GRAD_MFMA_SAMPLE_FASTER = dict.fromkeys(family.GRAD_MFMA_SAMPLE_FASTER, True)
             if a.gn_mfma_conv1:
                 family.GRAD_MFMA_CONV1_FASTER = dict.fromkeys(family.GRAD_MFMA_CONV1_FASTER, True)
+                if a.gn_mfma_fwd1:
+                    family.GRAD_MFMA_FWD1_FASTER = dict.fromkeys(family.GRAD_MFMA_FWD1_FASTER, True)
     for flag in (False, True):
         torch.manual_seed(7)
         params = {"meta": {"log": "WARNING", "seed": 7}, "model": {"input-size": k},
@@ -407,6 +419,8 @@ def rounds(a):
                 params["algorithm"]["device-training-gn-lenet-mfma-sample"] = True
                 if a.gn_mfma_conv1:
                     params["algorithm"]["device-training-gn-lenet-mfma-conv1"] = True
+                    if a.gn_mfma_fwd1:
+                        params["algorithm"]["device-training-gn-lenet-mfma-fwd1"] = True
         ts = [(x[j], int(y[j])) for j in range(per_node)]
         nodes = []
         for r in range(n):
@@ -429,6 +443,7 @@ def rounds(a):
            "clique_gradient": a.clique_gradient, "momentum": a.momentum, "gn_mfma": bool(gn and a.gn_mfma),
            "gn_mfma_sample": bool(gn and a.gn_mfma and a.gn_mfma_sample),
            "gn_mfma_conv1": bool(gn and a.gn_mfma and a.gn_mfma_sample and a.gn_mfma_conv1),
+           "gn_mfma_fwd1": bool(gn and a.gn_mfma and a.gn_mfma_sample and a.gn_mfma_conv1 and a.gn_mfma_fwd1),
            "warmup": a.warmup, "rounds": a.rounds, "threads": torch.get_num_threads(),
            "device": torch.cuda.get_device_name(0)}
     for flag, key in ((False, "flag_off"), (True, "flag_on")):
@@ -636,6 +651,9 @@ def main():
                     help="gn-rounds, with --gn-mfma: and --device-training-gn-lenet-mfma-sample")
     ap.add_argument("--gn-mfma-conv1", action="store_true",
                     help="gn-rounds, with both: and --device-training-gn-lenet-mfma-conv1")
+    ap.add_argument("--gn-mfma-fwd1", action="store_true",
+                    help="gn-kernel: time niidmix_gnlenet_nll_grad_rows_mfma_fwd1_f32 too; gn-rounds, "
+                         "with all three: and --device-training-gn-lenet-mfma-fwd1")
     a = ap.parse_args()
     if a.step == "all":
         return run_all(a)
