@@ -924,6 +924,45 @@ int niidmix_gnlenet_nll_grad_rows_mfma_fwd1_f32(const float *theta, int64_t ld_t
                                                 int64_t W, int64_t C, void *scratch,
                                                 int64_t scratch_bytes, void *stream);
 
+/* The chunk length CH, in samples, by which niidmix_gnlenet_nll_grad_rows_mfma_split_f32 cuts a row's
+ * batch: a function of the shape alone (never of n_rows or of the batch lengths), the same for
+ * every call.  0 where that entry refuses the shape. */
+int64_t niidmix_gnlenet_grad_split_chunk(int64_t Cin, int64_t H, int64_t W, int64_t C);
+
+/* Scratch bytes of niidmix_gnlenet_nll_grad_rows_mfma_split_f32: niidmix_gnlenet_nll_grad_rows_
+ * scratch_bytes' slots, followed where b_max > CH by the partial weight-gradient blocks,
+ * n_rows * ceil(b_max / CH) * (3 * 32 * 800 + 32 * Cin * 25) * 4 bytes.  0 as that function. */
+int64_t niidmix_gnlenet_nll_grad_rows_mfma_split_scratch_bytes(int64_t n_rows, int64_t b_max, int64_t Cin,
+                                                               int64_t H, int64_t W, int64_t C);
+
+/* niidmix_gnlenet_nll_grad_rows_mfma_conv1_f32 with the batch of the three convolution weight
+ * gradients cut over several workgroups per row (k_gnl_grad_wmfma<GnSplit>, k_gnl_grad_w1mfma<NT,
+ * GnSplit>, k_gnl_grad_wsum; the drop-in's --device-training-gn-lenet-mfma-split): for few rows
+ * with long batches, where a workgroup per (row, unit) leaves most of the card idle.  Arguments,
+ * limits (the same shapes: 15 <= H, W <= 42; anything beyond is NIIDMIX_EUNSUPPORTED), checks and
+ * their order are those of niidmix_gnlenet_nll_grad_rows_mfma_conv1_f32, but the scratch is
+ * niidmix_gnlenet_nll_grad_rows_mfma_split_scratch_bytes long and the overlap checks cover all of it;
+ * n_rows * 3 * ceil(b_max / CH) >= 2^31 is NIIDMIX_EUNSUPPORTED.  What differs:
+ *   the cut   with CH = niidmix_gnlenet_grad_split_chunk, chunk c of a row holds its samples
+ *             [c CH, min(len, (c + 1) CH)) in batch order.  A row of len <= CH samples is computed
+ *             and written exactly as by the _mfma_conv1 entry: the same bits.  A longer row's chunks
+ *             each run that entry's K loop over their own samples into a partial block, and
+ *             conv1.w, conv2.w, conv3.w are ((p0 + p1) + p2) + ... over the chunks in ascending
+ *             order.  Not bit-identical to the _mfma_conv1 entry there, the same bound of 4 e32
+ *             (tests/test_gpu_train_gnlenet_mfma_split.py).
+ *   b_max     when b_max <= CH the launches are the _mfma_conv1 entry's.
+ *   the rest  the other 11 tensors and the loss are the _mfma_conv1 entry's, bit for bit.
+ * Determinism, independence of the other rows and of the cut of the row list (the chunks depend on
+ * the shape and the row's own length only), no atomics, theta not written: as
+ * niidmix_gnlenet_nll_grad_rows_f32. */
+int niidmix_gnlenet_nll_grad_rows_mfma_split_f32(const float *theta, int64_t ld_t, const float *data,
+                                                 const int32_t *labels, const int32_t *batch_idx,
+                                                 const int32_t *batch_len, int64_t b_max,
+                                                 const int32_t *rows, int64_t n_rows, float *grad,
+                                                 int64_t ld_g, float *loss, int64_t Cin, int64_t H,
+                                                 int64_t W, int64_t C, void *scratch,
+                                                 int64_t scratch_bytes, void *stream);
+
 /* Training batches drawn on the device (the drop-in's --device-sampling): job j writes the batch
  * that starts at position cursor[j] of epoch epoch[j]'s permutation of the segment
  * [seg_start[j], seg_start[j] + seg_len[j]) of the caller's concatenated data, in the layout

@@ -102,19 +102,28 @@ __device__ __forceinline__ void gn_w1_steps(floatx16 (&acc)[NT], const float *ap
 }
 
 // Compiled without the packed fp32 VALU forms, as k_gnl_grad_wmfma is: the gather's adds are scalar
-// chains of at most four terms.
-template <int NT>
+// chains of at most four terms.  k_gnl_grad_w1mfma<NT> is a workgroup per row;
+// k_gnl_grad_w1mfma<NT, GnSplit> takes that one argument more and is a workgroup per (row, chunk)
+// over the chunk's samples (k_gnl_grad_wmfma's rule), with the same ((w0 + w1) + w2) + w3 at its end.
+template <int NT, class... SP>
 __global__ __launch_bounds__(256, 2) NIIDMIX_GN_NO_PK void k_gnl_grad_w1mfma(
         const float *__restrict__ data, const int32_t *__restrict__ batch_idx,
         const int32_t *__restrict__ batch_len, int b_max, const int32_t *__restrict__ rows, int n_tiles,
         const GnShape g, const GnGradLay L, const float *__restrict__ scratch, float *__restrict__ grad,
-        int64_t ld_g) {
+        int64_t ld_g, const SP... sp) {
     extern __shared__ __attribute__((aligned(16))) float gn_smem[];
+    constexpr bool SPLIT = sizeof...(SP) > 0;
     const int tid = threadIdx.x, wave = wave_id(), lane = tid & 63, half = lane >> 5, col = lane & 31;
-    const int64_t i = blockIdx.x;
+    int64_t i = blockIdx.x;
+    if constexpr (SPLIT) i /= (sp, ...).nchm;
     const int H = g.H, W = g.W, h1 = g.h1, w1 = g.w1, hw1 = h1 * w1, nel = g.Cin * 25;
     const GnW1Geom q = gn_w1_geom(g.Cin, H, W);
     const int len = lin_len(batch_len, i, b_max), sn = q.npr * w1;
+    int s_lo = 0, s_hi = len;
+    float *part = nullptr;
+    if constexpr (SPLIT)                         // block-uniform, before the first barrier
+        if (gn_split_range((sp, ...), i, (int)(blockIdx.x % (unsigned)(sp, ...).nchm), len, g.Cin, s_lo, s_hi, part))
+            return;
     const int64_t sample = (int64_t)g.Cin * H * W;
     float *xs = gn_smem, *as = xs + g.Cin * q.chanX + 8, *dys = as + 32 * q.chanA + 8;
     unsigned char *ams = reinterpret_cast<unsigned char *>(dys + 32 * sn);
@@ -138,7 +147,7 @@ __global__ __launch_bounds__(256, 2) NIIDMIX_GN_NO_PK void k_gnl_grad_w1mfma(
     const int gdx = 256 % W, gdr = 256 / W;
     const float *T0 = scratch + i * n_tiles * L.tile;        // the row's first slot
 #pragma unroll 1
-    for (int s = 0; s < len; ++s) {
+    for (int s = s_lo; s < s_hi; ++s) {
         // sample s lives in tile s / kGnTS of the row, at place s % kGnTS
         const float *T = T0 + (int64_t)(s / kGnTS) * L.tile;
         const float *dy1 = T + L.dx2 + (s % kGnTS) * 32 * hw1;
@@ -233,5 +242,7 @@ __global__ __launch_bounds__(256, 2) NIIDMIX_GN_NO_PK void k_gnl_grad_w1mfma(
     }
     gn_sync();
     float *out = grad + (int64_t)rows[i] * ld_g + g.c1w;
+    if constexpr (SPLIT)
+        if (part) out = part + kGnSplitC1;
     for (int e = tid; e < 32 * nel; e += 256) out[e] = gn_smem[e];
 }

@@ -129,22 +129,60 @@ __device__ __forceinline__ void gn_wm_fill(float *dst0, int chan, int pitch, int
 #define NIIDMIX_GN_NO_PK
 #endif
 
+// The batch cut over several workgroups per row (model_gnlenet_grad_split_mfma.inc has the rule and
+// the reduction): chunk c of a row holds its samples [c ch, min(len, (c + 1) ch)), and a row of len
+// samples has max(1, ceil(len / ch)) chunks, whatever the call's other rows are.  part holds, per
+// (row, chunk of b_max's nchm), the row's three weight blocks in the order conv2, conv3, conv1.
+struct GnSplit {
+    int ch, nchm;                                // samples per chunk; chunks of a batch of b_max
+    float *part;                                 // [n_rows, nchm, gn_split_floats(Cin)]
+};
+constexpr int kGnSplitC3 = 32 * 800, kGnSplitC1 = 3 * 32 * 800;     // conv3's, conv1's block in a partial
+
+__host__ __device__ __forceinline__ int gn_split_floats(int cin) { return kGnSplitC1 + 32 * cin * 25; }
+
+// A (row, chunk) workgroup's samples [s_lo, s_hi) of the row's len.  True where the workgroup has
+// nothing to do (its chunk lies past the row's last); part is set where the row has more than one
+// chunk and the block goes to its partial slot, else the block goes straight to grad.
+__device__ __forceinline__ bool gn_split_range(const GnSplit &sp, int64_t i, int c, int len, int cin,
+                                               int &s_lo, int &s_hi, float *&part) {
+    const int nch = len > sp.ch ? (len + sp.ch - 1) / sp.ch : 1;
+    if (c >= nch) return true;
+    if (nch > 1) {
+        s_lo = c * sp.ch;
+        s_hi = s_lo + sp.ch < len ? s_lo + sp.ch : len;
+        part = sp.part + (i * sp.nchm + c) * gn_split_floats(cin);
+    }
+    return false;
+}
+
 // Compiled without the packed fp32 VALU forms, as k_gnl_eval_mfma is: the kernel has no fp32 VALU
-// arithmetic of its own.
+// arithmetic of its own.  k_gnl_grad_wmfma<> is a workgroup per (row, unit) that walks the whole
+// batch; k_gnl_grad_wmfma<GnSplit> takes that one argument more and is a workgroup per (row, unit,
+// chunk), the chunk fastest, over the chunk's samples (a stage starts at the chunk's first sample).
+template <class... SP>
 __global__ __launch_bounds__(256, 2) NIIDMIX_GN_NO_PK void k_gnl_grad_wmfma(
         const int32_t *__restrict__ batch_len, int b_max, const int32_t *__restrict__ rows, int n_rows,
         int n_tiles, const GnShape g, const GnGradLay L, const float *__restrict__ scratch,
-        float *__restrict__ grad, int64_t ld_g) {
+        float *__restrict__ grad, int64_t ld_g, const SP... sp) {
     extern __shared__ __attribute__((aligned(16))) float gn_smem[];
+    constexpr bool SPLIT = sizeof...(SP) > 0;
     const int tid = threadIdx.x, wave = wave_id(), lane = tid & 63, half = lane >> 5, col = lane & 31;
-    // the unit: conv2 of row blockIdx.x, or a half of conv3's output channels
-    const bool c2 = (int)blockIdx.x < n_rows;
-    const int64_t i = c2 ? blockIdx.x : (blockIdx.x - n_rows) / 2;
-    const int co0 = c2 ? 0 : (int)((blockIdx.x - n_rows) % 2) * 32;
+    unsigned unit = blockIdx.x;
+    if constexpr (SPLIT) unit /= (unsigned)(sp, ...).nchm;
+    // the unit: conv2 of row `unit`, or a half of conv3's output channels
+    const bool c2 = (int)unit < n_rows;
+    const int64_t i = c2 ? unit : (unit - n_rows) / 2;
+    const int co0 = c2 ? 0 : (int)((unit - n_rows) % 2) * 32;
     const int CO = c2 ? 32 : 64, h = c2 ? g.h1 : g.h2, w = c2 ? g.w1 : g.w2;
     const int o_x = c2 ? L.x2 : L.x3, o_dy = c2 ? L.dy2 : L.dy3;
     const GnWmGeom q = gn_wm_geom(h, w);
     const int len = lin_len(batch_len, i, b_max);
+    int s_lo = 0, s_hi = len;
+    float *part = nullptr;
+    if constexpr (SPLIT)                         // block-uniform, before the first barrier
+        if (gn_split_range((sp, ...), i, (int)(blockIdx.x % (unsigned)(sp, ...).nchm), len, g.Cin, s_lo, s_hi, part))
+            return;
     float *xs = gn_smem, *as = gn_smem + q.ns * 32 * q.chanX + 4;
 
     // taps wave, wave + 4, ... < 25: 7 for wave 0, 6 for the others, whose seventh tile repeats
@@ -168,8 +206,8 @@ __global__ __launch_bounds__(256, 2) NIIDMIX_GN_NO_PK void k_gnl_grad_wmfma(
     const int lsh = w <= 8 ? 3 : w <= 16 ? 4 : 5;
     const float *T0 = scratch + i * n_tiles * L.tile;       // the row's first slot
 #pragma unroll 1
-    for (int s0 = 0; s0 < len; s0 += q.ns) {
-        const int ns = len - s0 < q.ns ? len - s0 : q.ns;
+    for (int s0 = s_lo; s0 < s_hi; s0 += q.ns) {
+        const int ns = s_hi - s0 < q.ns ? s_hi - s0 : q.ns;
 #pragma unroll 1
         for (int b = 0; b < q.nb; ++b) {
             gn_sync();                           // the zeros are written; the last stage has been read
@@ -185,6 +223,8 @@ __global__ __launch_bounds__(256, 2) NIIDMIX_GN_NO_PK void k_gnl_grad_wmfma(
     // write-out: acc[j][r] is output channel (r & 3) + 8 (r >> 2) + 4 half, input channel col, tap
     // wave + 4 j; registers 0..7 hold channels 0..15, registers 8..15 channels 16..31
     float *out = grad + (int64_t)rows[i] * ld_g + (c2 ? g.c2w : g.c3w) + co0 * 800;
+    if constexpr (SPLIT)
+        if (part) out = part + (c2 ? 0 : kGnSplitC3) + co0 * 800;
 #pragma unroll
     for (int hf = 0; hf < 2; ++hf) {
         gn_sync();                               // the stage, or the first half, has been read

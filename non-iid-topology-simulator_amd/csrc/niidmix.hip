@@ -52,6 +52,9 @@
 //                      data gradients on the matrix cores)
 //   model_gnlenet_grad_conv1_mfma.inc  k_gnl_grad_w1mfma (conv1's  niidmix_gnlenet_nll_grad_rows_mfma_conv1_f32
 //                      weight gradient on the matrix cores)
+//   model_gnlenet_grad_split_mfma.inc  k_gnl_grad_wsum (and the     niidmix_gnlenet_nll_grad_rows_mfma_split_f32
+//                      split instantiations of k_gnl_grad_wmfma /
+//                      _w1mfma: the batch cut over workgroups)
 //   sampling.inc       k_draw_batches, k_epoch_perm_chunks /       niidmix_draw_batches_i32, _epoch_perm_i32,
 //                      _global / _finish, k_take_batches           _take_batches_i32
 //                      k_torch_randperm                            niidmix_torch_randperm_i32
@@ -4962,6 +4965,7 @@ __global__ __launch_bounds__(256) void k_lin_eval_sum(const int32_t *__restrict_
 #include "model_gnlenet_grad_mfma.inc"
 #include "model_gnlenet_grad_sample_mfma.inc"
 #include "model_gnlenet_grad_conv1_mfma.inc"
+#include "model_gnlenet_grad_split_mfma.inc"
 
 #include "sampling.inc"
 
@@ -6509,12 +6513,31 @@ int64_t niidmix_gnlenet_nll_grad_rows_scratch_bytes(int64_t n_rows, int64_t b_ma
     return n_rows * gn_tiles(b_max) * gn_grad_lay(g).tile * 4;
 }
 
+int64_t niidmix_gnlenet_grad_split_chunk(int64_t Cin, int64_t H, int64_t W, int64_t C) {
+    if (Cin <= 0 || C <= 0 || C > kLinMaxC || Cin > kGnMaxCin || !gn_supported(Cin, H, W, C)) return 0;
+    return gn_split_chunk(gn_shape((int)Cin, (int)H, (int)W, (int)C));
+}
+
+// chunks of a batch of b_max samples under the split entry: 1 where nothing is cut
+static int64_t gn_split_chunks(int64_t b_max, int64_t ch) { return ch > 0 && b_max > ch ? (b_max + ch - 1) / ch : 1; }
+
+int64_t niidmix_gnlenet_nll_grad_rows_mfma_split_scratch_bytes(int64_t n_rows, int64_t b_max, int64_t Cin,
+                                                               int64_t H, int64_t W, int64_t C) {
+    const int64_t slots = niidmix_gnlenet_nll_grad_rows_scratch_bytes(n_rows, b_max, Cin, H, W, C);
+    const int64_t nchm = gn_split_chunks(b_max, niidmix_gnlenet_grad_split_chunk(Cin, H, W, C));
+    // the partials follow the slots: < 2^31 / 3 (row, chunk) blocks of < 2^19 bytes
+    return slots && nchm > 1 ? slots + n_rows * nchm * gn_split_floats((int)Cin) * 4 : slots;
+}
+
 // the GN-LeNet gradient entry points.  kGnGradWmfma takes conv2's and conv3's weight gradients out
 // of k_gnl_grad_conv and gives them to k_gnl_grad_wmfma; kGnGradSampleMfma does that and runs the
 // sample pass as k_gnl_grad_sample_mfma, at the shapes that kernel takes; kGnGradConv1Mfma does both
 // and gives conv1's weight gradient to k_gnl_grad_w1mfma; kGnGradFwd1Mfma is that with the sample
-// pass's conv1 on the matrix cores too (k_gnl_grad_sample_mfma<true>, LDS by gn_c1_geom)
-enum GnGradVariant { kGnGradPlain, kGnGradWmfma, kGnGradSampleMfma, kGnGradConv1Mfma, kGnGradFwd1Mfma };
+// pass's conv1 on the matrix cores too (k_gnl_grad_sample_mfma<true>, LDS by gn_c1_geom);
+// kGnGradSplitMfma is kGnGradConv1Mfma with the two GEMM kernels' batch cut in chunks over several
+// workgroups per row and k_gnl_grad_wsum after them, where b_max exceeds a chunk
+enum GnGradVariant { kGnGradPlain, kGnGradWmfma, kGnGradSampleMfma, kGnGradConv1Mfma, kGnGradFwd1Mfma,
+                     kGnGradSplitMfma };
 
 static int gn_grad_rows(GnGradVariant variant, const float *theta, int64_t ld_t, const float *data,
                         const int32_t *labels, const int32_t *batch_idx, const int32_t *batch_len,
@@ -6522,7 +6545,8 @@ static int gn_grad_rows(GnGradVariant variant, const float *theta, int64_t ld_t,
                         float *loss, int64_t Cin, int64_t H, int64_t W, int64_t C, void *scratch,
                         int64_t scratch_bytes, void *stream) {
     const bool mfma = variant != kGnGradPlain, fwd1 = variant == kGnGradFwd1Mfma;
-    const bool conv1 = variant == kGnGradConv1Mfma || fwd1;
+    const bool split = variant == kGnGradSplitMfma;
+    const bool conv1 = variant == kGnGradConv1Mfma || fwd1 || split;
     const bool sample = variant == kGnGradSampleMfma || conv1;
     if (!theta || !data || !labels || !batch_idx || !batch_len || !rows || !grad || !loss || !scratch)
         return set_error(NIIDMIX_EINVAL, "null pointer");
@@ -6548,11 +6572,14 @@ static int gn_grad_rows(GnGradVariant variant, const float *theta, int64_t ld_t,
         return set_error(NIIDMIX_EUNSUPPORTED, "b_max %lld > 2^24", (long long)b_max);
     const GnShape g = gn_shape((int)Cin, (int)H, (int)W, (int)C);
     const int64_t n_blk = (g.C * (int64_t)g.F + g.C + 255) / 256;
-    if (!gn_grad_fits(n_rows, b_max) || n_rows * n_blk > 0x7fffffff)
+    const int64_t nchm = split ? gn_split_chunks(b_max, gn_split_chunk(g)) : 1;
+    if (!gn_grad_fits(n_rows, b_max) || n_rows * n_blk > 0x7fffffff || n_rows * 3 * nchm > 0x7fffffff)
         return set_error(NIIDMIX_EUNSUPPORTED, "n_rows %lld x b_max %lld: too many blocks or scratch slots",
                          (long long)n_rows, (long long)b_max);
     if (int rc = check_ld(ld_t, ld_g, g.P, "P")) return rc;
-    const int64_t need = niidmix_gnlenet_nll_grad_rows_scratch_bytes(n_rows, b_max, Cin, H, W, C);
+    const int64_t slot_bytes = niidmix_gnlenet_nll_grad_rows_scratch_bytes(n_rows, b_max, Cin, H, W, C);
+    const int64_t need = split ? niidmix_gnlenet_nll_grad_rows_mfma_split_scratch_bytes(n_rows, b_max, Cin, H, W, C)
+                               : slot_bytes;
     if (scratch_bytes < need || (reinterpret_cast<uintptr_t>(scratch) & 7u))
         return set_error(NIIDMIX_EINVAL, "scratch of %lld bytes (8-B aligned), %lld needed",
                          (long long)scratch_bytes, (long long)need);
@@ -6583,24 +6610,48 @@ static int gn_grad_rows(GnGradVariant variant, const float *theta, int64_t ld_t,
                            g, L, sc);
         if (int rc = check_launch("k_gnl_grad_sample")) return rc;
     }
+    // the partials of the cut batch follow the slots; one chunk: the kernels without the cut
+    const GnSplit sp = {gn_split_chunk(g), (int)nchm, sc + slot_bytes / 4};
     if (mfma) {                                  // the units: n_rows of conv2, then 2 n_rows of conv3
         const GnWmGeom q2 = gn_wm_geom(g.h1, g.w1), q3 = gn_wm_geom(g.h2, g.w2);
         const size_t lds = 4 * (size_t)(gn_wm_lds_floats(q2) > gn_wm_lds_floats(q3) ? gn_wm_lds_floats(q2)
                                                                                     : gn_wm_lds_floats(q3));
-        if (lds > 64 * 1024)
-            if (int rc = lds_opt_in(k_gnl_grad_wmfma, lds, "k_gnl_grad_wmfma")) return rc;
-        hipLaunchKernelGGL(k_gnl_grad_wmfma, dim3((unsigned)(n_rows * 3)), dim3(256), lds, s, batch_len,
-                           (int)b_max, rows, (int)n_rows, (int)n_tiles, g, L, (const float *)sc, grad, ld_g);
+        if (nchm > 1) {                          // a workgroup per (unit, chunk)
+            if (lds > 64 * 1024)
+                if (int rc = lds_opt_in(k_gnl_grad_wmfma<GnSplit>, lds, "k_gnl_grad_wmfma")) return rc;
+            hipLaunchKernelGGL(k_gnl_grad_wmfma<GnSplit>, dim3((unsigned)(n_rows * 3 * nchm)), dim3(256), lds,
+                               s, batch_len, (int)b_max, rows, (int)n_rows, (int)n_tiles, g, L,
+                               (const float *)sc, grad, ld_g, sp);
+        } else {
+            if (lds > 64 * 1024)
+                if (int rc = lds_opt_in(k_gnl_grad_wmfma<>, lds, "k_gnl_grad_wmfma")) return rc;
+            hipLaunchKernelGGL(k_gnl_grad_wmfma<>, dim3((unsigned)(n_rows * 3)), dim3(256), lds, s, batch_len,
+                               (int)b_max, rows, (int)n_rows, (int)n_tiles, g, L, (const float *)sc, grad, ld_g);
+        }
         if (int rc = check_launch("k_gnl_grad_wmfma")) return rc;
     }
     if (conv1) {                                 // a workgroup per row
         const size_t lds = 4 * (size_t)gn_w1_lds_floats(g.Cin, g.W, gn_w1_geom(g.Cin, g.H, g.W));
-        auto k1 = pick<1, 2, 3, 4>((g.Cin * 25 + 31) / 32, [](auto NT) { return k_gnl_grad_w1mfma<NT()>; });
-        if (lds > 64 * 1024)
-            if (int rc = lds_opt_in(k1, lds, "k_gnl_grad_w1mfma")) return rc;
-        hipLaunchKernelGGL(k1, dim3((unsigned)n_rows), dim3(256), lds, s, data, batch_idx, batch_len,
-                           (int)b_max, rows, (int)n_tiles, g, L, (const float *)sc, grad, ld_g);
-        if (int rc = check_launch("k_gnl_grad_w1mfma")) return rc;
+        if (nchm > 1) {                          // a workgroup per (row, chunk), then the ordered sums
+            auto k1 = pick<1, 2, 3, 4>((g.Cin * 25 + 31) / 32,
+                                       [](auto NT) { return k_gnl_grad_w1mfma<NT(), GnSplit>; });
+            if (lds > 64 * 1024)
+                if (int rc = lds_opt_in(k1, lds, "k_gnl_grad_w1mfma")) return rc;
+            hipLaunchKernelGGL(k1, dim3((unsigned)(n_rows * nchm)), dim3(256), lds, s, data, batch_idx,
+                               batch_len, (int)b_max, rows, (int)n_tiles, g, L, (const float *)sc, grad, ld_g, sp);
+            if (int rc = check_launch("k_gnl_grad_w1mfma")) return rc;
+            const int n_sum = (gn_split_floats(g.Cin) + 256 * kGnWsumPer - 1) / (256 * kGnWsumPer);
+            hipLaunchKernelGGL(k_gnl_grad_wsum, dim3((unsigned)(n_rows * n_sum)), dim3(256), 0, s, batch_len,
+                               (int)b_max, rows, n_sum, g, sp, grad, ld_g);
+            if (int rc = check_launch("k_gnl_grad_wsum")) return rc;
+        } else {
+            auto k1 = pick<1, 2, 3, 4>((g.Cin * 25 + 31) / 32, [](auto NT) { return k_gnl_grad_w1mfma<NT()>; });
+            if (lds > 64 * 1024)
+                if (int rc = lds_opt_in(k1, lds, "k_gnl_grad_w1mfma")) return rc;
+            hipLaunchKernelGGL(k1, dim3((unsigned)n_rows), dim3(256), lds, s, data, batch_idx, batch_len,
+                               (int)b_max, rows, (int)n_tiles, g, L, (const float *)sc, grad, ld_g);
+            if (int rc = check_launch("k_gnl_grad_w1mfma")) return rc;
+        }
     }
     auto kc = conv1 ? k_gnl_grad_conv<false, false> : mfma ? k_gnl_grad_conv<false> : k_gnl_grad_conv<true>;
     hipLaunchKernelGGL(kc, dim3((unsigned)(n_rows * 128)), dim3(256), 0, s, data, batch_idx,
@@ -6650,6 +6701,17 @@ int niidmix_gnlenet_nll_grad_rows_mfma_conv1_f32(const float *theta, int64_t ld_
                                                  int64_t W, int64_t C, void *scratch,
                                                  int64_t scratch_bytes, void *stream) {
     return gn_grad_rows(kGnGradConv1Mfma, theta, ld_t, data, labels, batch_idx, batch_len, b_max, rows,
+                        n_rows, grad, ld_g, loss, Cin, H, W, C, scratch, scratch_bytes, stream);
+}
+
+int niidmix_gnlenet_nll_grad_rows_mfma_split_f32(const float *theta, int64_t ld_t, const float *data,
+                                                 const int32_t *labels, const int32_t *batch_idx,
+                                                 const int32_t *batch_len, int64_t b_max,
+                                                 const int32_t *rows, int64_t n_rows, float *grad,
+                                                 int64_t ld_g, float *loss, int64_t Cin, int64_t H,
+                                                 int64_t W, int64_t C, void *scratch,
+                                                 int64_t scratch_bytes, void *stream) {
+    return gn_grad_rows(kGnGradSplitMfma, theta, ld_t, data, labels, batch_idx, batch_len, b_max, rows,
                         n_rows, grad, ld_g, loss, Cin, H, W, C, scratch, scratch_bytes, stream);
 }
 

@@ -132,6 +132,11 @@ SIGNATURES = {
     "niidmix_gnlenet_nll_grad_rows_mfma_fwd1_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64,
                                                                    _vp, _i64, _vp, _i64, _vp, _i64, _i64,
                                                                    _i64, _i64, _vp, _i64, _vp]),
+    "niidmix_gnlenet_grad_split_chunk": (_i64, [_i64, _i64, _i64, _i64]),
+    "niidmix_gnlenet_nll_grad_rows_mfma_split_scratch_bytes": (_i64, [_i64, _i64, _i64, _i64, _i64, _i64]),
+    "niidmix_gnlenet_nll_grad_rows_mfma_split_f32": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64,
+                                                                    _vp, _i64, _vp, _i64, _vp, _i64, _i64,
+                                                                    _i64, _i64, _vp, _i64, _vp]),
     "niidmix_draw_batches_max_len": (_i64, []),
     "niidmix_draw_batches_i32": (ctypes.c_int, [ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, _i64, _i64,
                                                 _vp, _vp, _vp]),

@@ -25,8 +25,9 @@ training runs on the device too: gradient, step and mixing never leave HBM (niid
 it, takes two of its weight gradients from a matrix-core kernel, and
 --device-training-gn-lenet-mfma-sample, with both, its sample pass's convolutions too, and
 --device-training-gn-lenet-mfma-conv1, with all three, conv1's weight gradient, and
---device-training-gn-lenet-mfma-fwd1, with all four, the sample pass's conv1), and
---device-training-sample for
+--device-training-gn-lenet-mfma-fwd1, with all four, the sample pass's conv1;
+--device-training-gn-lenet-mfma-split, with -mfma-conv1, cuts the weight gradients' batch over
+several workgroups per row), and --device-training-sample for
 rounds of the 'sample' topology (the other two flags refuse it).  --device-sampling, with any of
 the three, draws the batches on the device too, from a sample stream of the plugin's own
 (niidmix.sampling) instead of one DataLoader per node; --device-sampling-cached keeps every epoch's
@@ -927,6 +928,7 @@ def init(nodes, topology, params):
             params["algorithm"].get("device-training-gn-lenet-mfma-sample") or \
             params["algorithm"].get("device-training-gn-lenet-mfma-conv1") or \
             params["algorithm"].get("device-training-gn-lenet-mfma-fwd1") or \
+            params["algorithm"].get("device-training-gn-lenet-mfma-split") or \
             params["algorithm"].get("device-sampling-torch-stream"):
         from . import train
         train.check_eligible(nodes, params, topology)     # refusals: ValueError naming the flag
@@ -1178,6 +1180,13 @@ def main(argv=None):
                          "the matrix cores as well (niidmix::gnlenet_nll_grad_rows_mfma_fwd1), at the "
                          "shapes it is measured faster at; the same bound, every tensor may differ in "
                          "the last bits")
+    ap.add_argument("--device-training-gn-lenet-mfma-split", action="store_const", const=True,
+                    default=False,
+                    help="with --device-training-gn-lenet-mfma-conv1: the three convolution weight "
+                         "gradients' batch is cut in chunks over several workgroups per row and summed "
+                         "in chunk order (niidmix::gnlenet_nll_grad_rows_mfma_split: few rows, long "
+                         "batches), at the shapes it is measured faster at; the same bound, other bits "
+                         "in those three tensors where a batch exceeds a chunk")
     ap.add_argument("--device-training-sample", action="store_const", const=True, default=False,
                     help="--device-training for runs of the 'sample' topology (sets both keys; "
                          "the other two flags refuse 'sample'): each round the sampled nodes train "
@@ -1251,6 +1260,8 @@ def main(argv=None):
         ap.error("--device-training-gn-lenet-mfma-conv1 needs --device-training-gn-lenet-mfma-sample")
     if args.device_training_gn_lenet_mfma_fwd1 and not args.device_training_gn_lenet_mfma_conv1:
         ap.error("--device-training-gn-lenet-mfma-fwd1 needs --device-training-gn-lenet-mfma-conv1")
+    if args.device_training_gn_lenet_mfma_split and not args.device_training_gn_lenet_mfma_conv1:
+        ap.error("--device-training-gn-lenet-mfma-split needs --device-training-gn-lenet-mfma-conv1")
     rundir = m.rundir(args)
     params = m.params(rundir)
     topology = load_topology(rundir)
@@ -1277,6 +1288,8 @@ def main(argv=None):
         **({"device-training-gn-lenet-mfma-conv1": True} if args.device_training_gn_lenet_mfma_conv1
            else {}),
         **({"device-training-gn-lenet-mfma-fwd1": True} if args.device_training_gn_lenet_mfma_fwd1
+           else {}),
+        **({"device-training-gn-lenet-mfma-split": True} if args.device_training_gn_lenet_mfma_split
            else {}),
         **({"device-training-sample": True} if args.device_training_sample else {}),
         **({"device-training-large-batch": True} if args.device_training_large_batch else {}),

@@ -2,7 +2,7 @@
 niidmix.evaluate evaluates, stated once.  LINEAR (setup/model/linear.py: one nn.Linear(K, C),
 log_softmax) and GN_LENET (setup/model/gn_lenet.py) have the same methods, apart from each one's own
 routing rule (LINEAR.sliced; GN_LENET.grad_mfma, grad_mfma_class, mfma; the module's
-grad_mfma_sample, grad_mfma_conv1 and grad_mfma_fwd1); family_of(model) picks one
+grad_mfma_sample, grad_mfma_conv1, grad_mfma_fwd1 and grad_mfma_split); family_of(model) picks one
 from the parameters' shapes.  A family knows its shape(model) -- (K, C) / (Cin, C, F), C is
 shape[1] in both -- and P(shape); the kernels' limits as refusals (the constants are niidmix.ops',
 which checks its arguments against the same ones); sizes(), the one sample check, giving the
@@ -12,13 +12,14 @@ ops.gnlenet_shapes, one table: the expected shapes, the offsets, the row splitte
 from it.  The float64 yardsticks of the probes and of the GPU tests live here as well.
 
 The kernel variant is bound once, in a plan: grad_plan(sizes, b_max, large=False, mfma=False,
-mfma_sample=False, mfma_conv1=False, mfma_fwd1=False) and eval_plan(sizes, mfma=False) apply the
-family's rule,
+mfma_sample=False, mfma_conv1=False, mfma_fwd1=False, mfma_split=False) and eval_plan(sizes,
+mfma=False) apply the family's rule,
 reading its table then, to the opt-in switches (`large`: --device-training-large-batch; `mfma`:
 --device-training-gn-lenet-mfma / --device-evaluation-mfma; `mfma_sample`:
 --device-training-gn-lenet-mfma-sample; `mfma_conv1`: --device-training-gn-lenet-mfma-conv1;
-`mfma_fwd1`: --device-training-gn-lenet-mfma-fwd1) and return a GradPlan / EvalPlan.  A family
-ignores a switch that is not its own (LINEAR `mfma`, `mfma_sample`, `mfma_conv1` and `mfma_fwd1`,
+`mfma_fwd1`: --device-training-gn-lenet-mfma-fwd1; `mfma_split`:
+--device-training-gn-lenet-mfma-split) and return a GradPlan / EvalPlan.  A family ignores a
+switch that is not its own (LINEAR `mfma`, `mfma_sample`, `mfma_conv1`, `mfma_fwd1` and `mfma_split`,
 GN_LENET `large`), so the callers pass every switch to either family.
 """
 import copy
@@ -244,7 +245,7 @@ class _Linear:
         return bool(large) and b_max * sizes[1] > MAX_BC
 
     def grad_plan(self, sizes, b_max, large=False, mfma=False, mfma_sample=False, mfma_conv1=False,
-                  mfma_fwd1=False):
+                  mfma_fwd1=False, mfma_split=False):
         if self.sliced(b_max, sizes, large):         # the scratch sizes are in fp32 elements
             op, dims = ops.linear_nll_grad_rows_sliced, sizes
             elems = lib.niidmix_linear_nll_grad_rows_sliced_scratch_elems
@@ -332,6 +333,24 @@ def grad_mfma_fwd1(sizes, mfma, mfma_sample, mfma_conv1, flag):
         GRAD_MFMA_FWD1_FASTER.get(ops.gn_mfma_tile(sizes[1], sizes[2]), False)
 
 
+# --device-training-gn-lenet-mfma-split's shape classes are the same tiles.  True where
+# tools/device_training_probe.py gn-kernel measured the call's median below
+# gnlenet_nll_grad_rows_mfma_conv1's by more than that call's own spread in the same run (DESIGN.md
+# section 5: tile 4 at 100 rows x 1 x 28 x 28 x batch 128, tile 2 at 1 row x 3 x 32 x 32 x batch
+# 2000; profiles/gnlenet_grad_split_mfma/).  A class that is not keeps the plan it had.  Batches of
+# at most ops.gnlenet_grad_split_chunk samples run the conv1 op's kernels under either.
+GRAD_MFMA_SPLIT_FASTER = {4: True, 2: True}
+
+
+def grad_mfma_split(sizes, mfma, mfma_sample, mfma_conv1, flag):
+    """Under the three flags and --device-training-gn-lenet-mfma-split (`flag`) a GN-LeNet call goes
+    to the op that cuts the weight gradients' batch over several workgroups per row exactly when
+    grad_mfma_conv1 routes the shape to its op (the new one is that op with other grids and a
+    reduction) and the new op is the measured faster one at the shape's class."""
+    return grad_mfma_conv1(sizes, mfma, mfma_sample, mfma_conv1) and bool(flag) and \
+        GRAD_MFMA_SPLIT_FASTER.get(ops.gn_mfma_tile(sizes[1], sizes[2]), False)
+
+
 class _GNLeNet:
     kind = "gn-lenet"
     cut = True           # a row's bits do not depend on the cut
@@ -387,16 +406,19 @@ class _GNLeNet:
         return bool(flag) and self.GRAD_MFMA_FASTER[self.grad_mfma_class(sizes)]
 
     def grad_plan(self, sizes, b_max, large=False, mfma=False, mfma_sample=False, mfma_conv1=False,
-                  mfma_fwd1=False):
+                  mfma_fwd1=False, mfma_split=False):
+        scratch = lib.niidmix_gnlenet_nll_grad_rows_scratch_bytes       # every op's but the split one's
         if grad_mfma_fwd1(sizes, mfma, mfma_sample, mfma_conv1, mfma_fwd1):
             op = ops.gnlenet_nll_grad_rows_mfma_fwd1
+        elif grad_mfma_split(sizes, mfma, mfma_sample, mfma_conv1, mfma_split):
+            op = ops.gnlenet_nll_grad_rows_mfma_split       # its partial blocks follow the slots
+            scratch = lib.niidmix_gnlenet_nll_grad_rows_mfma_split_scratch_bytes
         elif grad_mfma_conv1(sizes, mfma, mfma_sample, mfma_conv1):
             op = ops.gnlenet_nll_grad_rows_mfma_conv1
         elif grad_mfma_sample(sizes, mfma, mfma_sample):
             op = ops.gnlenet_nll_grad_rows_mfma_sample
         else:
             op = ops.gnlenet_nll_grad_rows_mfma if self.grad_mfma(sizes, mfma) else ops.gnlenet_nll_grad_rows
-        scratch = lib.niidmix_gnlenet_nll_grad_rows_scratch_bytes       # every op'
         return GradPlan(op, self.cut, sizes, b_max, lambda rows: int(scratch(rows, b_max, *sizes)))
 
     # --device-evaluation-mfma's shape classes are the matrix-core kernel's tiles (ops.gn_mfma_tile):

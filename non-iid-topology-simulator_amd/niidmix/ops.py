@@ -57,6 +57,11 @@ Ops (registered in the `niidmix` namespace, usable as torch.ops.niidmix.*):
                                                     the same with k_gnl_grad_sample_mfma<true> as the
                                                     sample pass (its conv1 on the matrix cores too,
                                                     --device-training-gn-lenet-mfma-fwd1)
+  gnlenet_nll_grad_rows_mfma_split(the same arguments)
+                                                    gnlenet_nll_grad_rows_mfma_conv1 with the batch of
+                                                    k_gnl_grad_wmfma / _w1mfma cut in chunks over
+                                                    several workgroups per row, then k_gnl_grad_wsum
+                                                    (--device-training-gn-lenet-mfma-split)
   gnlenet_eval_rows(theta, data, labels, rows, seg_start, seg_len, max_len, loss_sum, correct, pred,
                     logits, Cin, H, W, C)           k_gnl_eval + k_lin_eval_sum (the same for GN-LeNet)
   gnlenet_eval_rows_mfma(the same arguments)        k_gnl_eval_mfma + k_lin_eval_sum (conv2 / conv3 on
@@ -962,7 +967,9 @@ def _gnlenet_grad(name, theta, data, labels, batch_idx, batch_len, rows, grad, l
     if n == 0:
         return
     dev, b_max = theta.device, batch_idx.shape[1]
-    nbytes = max(16, int(_lib.lib.niidmix_gnlenet_nll_grad_rows_scratch_bytes(n, b_max, Cin, H, W, C)))
+    size = _lib.lib.niidmix_gnlenet_nll_grad_rows_mfma_split_scratch_bytes if name.endswith("_mfma_split") \
+        else _lib.lib.niidmix_gnlenet_nll_grad_rows_scratch_bytes
+    nbytes = max(16, int(size(n, b_max, Cin, H, W, C)))
     scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
     rc = getattr(_lib.lib, f"niidmix_{name}_f32")(
         theta.data_ptr(), _ld(theta), data.data_ptr(), labels.data_ptr(), batch_idx.data_ptr(),
@@ -1034,6 +1041,27 @@ def gnlenet_nll_grad_rows_mfma_fwd1(theta: torch.Tensor, data: torch.Tensor, lab
     (include/niidmix.h, niidmix_gnlenet_nll_grad_rows_mfma_fwd1_f32): the same arguments, checks,
     shapes, scratch and bound; every tensor and the loss may differ in the last bits."""
     _gnlenet_grad("gnlenet_nll_grad_rows_mfma_fwd1", theta, data, labels, batch_idx, batch_len, rows,
+                  grad, loss, Cin, H, W, C)
+
+
+def gnlenet_grad_split_chunk(Cin, H, W, C):
+    """The chunk length in samples by which niidmix::gnlenet_nll_grad_rows_mfma_split cuts a row's batch
+    (include/niidmix.h, niidmix_gnlenet_grad_split_chunk): a function of the shape alone; 0 where
+    the op refuses the shape."""
+    return int(_lib.lib.niidmix_gnlenet_grad_split_chunk(int(Cin), int(H), int(W), int(C)))
+
+
+@torch.library.custom_op("niidmix::gnlenet_nll_grad_rows_mfma_split", mutates_args=("grad", "loss"))
+def gnlenet_nll_grad_rows_mfma_split(theta: torch.Tensor, data: torch.Tensor, labels: torch.Tensor,
+                                     batch_idx: torch.Tensor, batch_len: torch.Tensor, rows: torch.Tensor,
+                                     grad: torch.Tensor, loss: torch.Tensor,
+                                     Cin: int, H: int, W: int, C: int) -> None:
+    """gnlenet_nll_grad_rows_mfma_conv1 with the three convolution weight gradients' batch cut in
+    chunks of gnlenet_grad_split_chunk samples over several workgroups per row (include/niidmix.h,
+    niidmix_gnlenet_nll_grad_rows_mfma_split_f32): the same arguments, checks, shapes and bound, a
+    longer scratch; rows of at most a chunk bit for bit, longer rows' conv1 / conv2 / conv3 weights
+    as the ordered sum of their chunks, everything else bit for bit."""
+    _gnlenet_grad("gnlenet_nll_grad_rows_mfma_split", theta, data, labels, batch_idx, batch_len, rows,
                   grad, loss, Cin, H, W, C)
 
 

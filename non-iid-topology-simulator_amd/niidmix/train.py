@@ -33,6 +33,9 @@ on the matrix cores too) under the same kind of rule, and `--device-training-gn-
 valid only with all three, for niidmix::gnlenet_nll_grad_rows_mfma_conv1 (conv1's weight gradient on
 the matrix cores as well), and `--device-training-gn-lenet-mfma-fwd1`, valid only with all four, for
 niidmix::gnlenet_nll_grad_rows_mfma_fwd1 (the sample pass's conv1 there too).
+`--device-training-gn-lenet-mfma-split`, valid only with `-mfma-conv1` and independent of
+`-mfma-fwd1`, swaps the conv1 op for niidmix::gnlenet_nll_grad_rows_mfma_split (the weight
+gradients' batch cut over several workgroups per row: few rows with long batches).
 
 What depends on the model family -- shapes, the kernels' limits, the sample check, the gradient op
 and its scratch, the forward probe -- is niidmix.family's; DeviceTrainer holds a family, its
@@ -135,6 +138,7 @@ FLAG_GN_MFMA = "--device-training-gn-lenet-mfma"
 FLAG_GN_MFMA_SAMPLE = "--device-training-gn-lenet-mfma-sample"
 FLAG_GN_MFMA_CONV1 = "--device-training-gn-lenet-mfma-conv1"
 FLAG_GN_MFMA_FWD1 = "--device-training-gn-lenet-mfma-fwd1"
+FLAG_GN_MFMA_SPLIT = "--device-training-gn-lenet-mfma-split"
 FLAG_SAMPLE = "--device-training-sample"
 FLAG_SAMPLING = "--device-sampling"
 FLAG_CACHED = "--device-sampling-cached"
@@ -185,6 +189,13 @@ def gn_mfma_fwd1_enabled(params):
     gradient goes to the op whose sample pass runs conv1 on the matrix cores as well, where
     niidmix.family's rule sends the shape."""
     return bool(params.get("algorithm", {}).get("device-training-gn-lenet-mfma-fwd1"))
+
+
+def gn_mfma_split_enabled(params):
+    """--device-training-gn-lenet-mfma-split: with --device-training-gn-lenet-mfma-conv1, the
+    gradient goes to the op that cuts the weight gradients' batch over several workgroups per row,
+    where niidmix.family's rule sends the shape."""
+    return bool(params.get("algorithm", {}).get("device-training-gn-lenet-mfma-split"))
 
 
 def sample_run(params):
@@ -377,6 +388,8 @@ def check_eligible(nodes, params, topology=None):
         raise ValueError(f"{FLAG_GN_MFMA_CONV1} needs {FLAG_GN_MFMA_SAMPLE}")
     if gn_mfma_fwd1_enabled(params) and not gn_mfma_conv1_enabled(params):
         raise ValueError(f"{FLAG_GN_MFMA_FWD1} needs {FLAG_GN_MFMA_CONV1}")
+    if gn_mfma_split_enabled(params) and not gn_mfma_conv1_enabled(params):
+        raise ValueError(f"{FLAG_GN_MFMA_SPLIT} needs {FLAG_GN_MFMA_CONV1}")
     flag = flag_of(params)
     sample = sample_run(params)
     large = large_enabled(params)
@@ -500,7 +513,7 @@ class DeviceTrainer:
         # the gradient call, its kernel variant bound for the trainer's life
         self.plan = self.family.grad_plan(self.sizes, self.b_max, self.large, gn_mfma_enabled(params),
                                           gn_mfma_sample_enabled(params), gn_mfma_conv1_enabled(params),
-                                          gn_mfma_fwd1_enabled(params))
+                                          gn_mfma_fwd1_enabled(params), gn_mfma_split_enabled(params))
         self._check_fit(xs)
         dev = self.device
         self.data = xs.to(dev)

@@ -120,7 +120,7 @@ def gn_kernel(a):
     import torch.nn.functional as F
     from niidmix import _lib, ops, train
     n, cin, h, w, c, b = GN_SHAPES[a.shape]
-    n = a.nodes or n
+    n, b = a.nodes or n, a.batch or b
     dev = torch.device("cuda:0")
     k = cin * h * w
     p = ops.gnlenet_sizes(cin, h, w, c)[1]
@@ -141,7 +141,9 @@ def gn_kernel(a):
     rows = torch.arange(n, dtype=torch.int32, device=dev)
     loss = torch.empty(n, device=dev)
     lib = _lib.lib
-    nbytes = int(lib.niidmix_gnlenet_nll_grad_rows_scratch_bytes(n, b, cin, h, w, c))
+    size = lib.niidmix_gnlenet_nll_grad_rows_mfma_split_scratch_bytes if a.gn_mfma_split \
+        else lib.niidmix_gnlenet_nll_grad_rows_scratch_bytes     # the first is never the smaller
+    nbytes = int(size(n, b, cin, h, w, c))
     scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
     strm = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     read = n * p + n * b * k                           # floats the call must read
@@ -176,6 +178,9 @@ def gn_kernel(a):
                  True)] if a.gn_mfma_fwd1 else []),
              ("device_autograd", lambda: loop(mdl_dev, xb, yb, n_dev), n / n_dev, True),
              ("cpu_loop", lambda: loop(mdl, xc, yc, n_cpu), n / n_cpu, False)]
+    if a.gn_mfma_split:                      # the two calls alone, alternating: few rows, long batches
+        cands = [cands[4], ("grad_mfma_split",
+                            lambda: grad_call(lib.niidmix_gnlenet_nll_grad_rows_mfma_split_f32), 1.0, True)]
     times = {name: [] for name, _, _, _ in cands}
     for rep_i in range(a.warmup + a.reps):
         for name, fn, scale, on_dev in cands:
@@ -198,6 +203,14 @@ def gn_kernel(a):
     for name, _, _, _ in cands:
         t = times[name]
         out[name] = {"median_ms": statistics.median(t) * 1e3, "min_ms": min(t) * 1e3, "max_ms": max(t) * 1e3}
+    if a.gn_mfma_split:                      # the rule of family.GRAD_MFMA_SPLIT_FASTER, against grad_mfma_conv1
+        out["split_chunk"] = int(lib.niidmix_gnlenet_grad_split_chunk(cin, h, w, c))
+        out["grad_mfma_split_over_grad_mfma_conv1"] = \
+            out["grad_mfma_split"]["median_ms"] / out["grad_mfma_conv1"]["median_ms"]
+        out["grad_mfma_split_faster"] = \
+            out["grad_mfma_conv1"]["median_ms"] - out["grad_mfma_split"]["median_ms"] > \
+            out["grad_mfma_conv1"]["max_ms"] - out["grad_mfma_conv1"]["min_ms"]
+        return print(json.dumps(out))
     for name in ("copy", "device_autograd", "cpu_loop"):
         out["grad_over_" + name] = out["grad"]["median_ms"] / out[name]["median_ms"]
     # the acceptance rule of family.GN_LENET.GRAD_MFMA_FASTER: below the plain call's median by more
@@ -372,7 +385,7 @@ def rounds(a):
         k = cin * h * w
     else:
         n, k, c, b = SHAPES[a.shape]
-    n = a.nodes or n
+    n, b = a.nodes or n, a.batch or b
     per_node = 2 * b
 
     class Net(torch.nn.Module):
@@ -401,6 +414,8 @@ def rounds(a):
                 family.GRAD_MFMA_CONV1_FASTER = dict.fromkeys(family.GRAD_MFMA_CONV1_FASTER, True)
                 if a.gn_mfma_fwd1:
                     family.GRAD_MFMA_FWD1_FASTER = dict.fromkeys(family.GRAD_MFMA_FWD1_FASTER, True)
+                if a.gn_mfma_split:
+                    family.GRAD_MFMA_SPLIT_FASTER = dict.fromkeys(family.GRAD_MFMA_SPLIT_FASTER, True)
     for flag in (False, True):
         torch.manual_seed(7)
         params = {"meta": {"log": "WARNING", "seed": 7}, "model": {"input-size": k},
@@ -421,6 +436,8 @@ def rounds(a):
                     params["algorithm"]["device-training-gn-lenet-mfma-conv1"] = True
                     if a.gn_mfma_fwd1:
                         params["algorithm"]["device-training-gn-lenet-mfma-fwd1"] = True
+                    if a.gn_mfma_split:
+                        params["algorithm"]["device-training-gn-lenet-mfma-split"] = True
         ts = [(x[j], int(y[j])) for j in range(per_node)]
         nodes = []
         for r in range(n):
@@ -444,6 +461,7 @@ def rounds(a):
            "gn_mfma_sample": bool(gn and a.gn_mfma and a.gn_mfma_sample),
            "gn_mfma_conv1": bool(gn and a.gn_mfma and a.gn_mfma_sample and a.gn_mfma_conv1),
            "gn_mfma_fwd1": bool(gn and a.gn_mfma and a.gn_mfma_sample and a.gn_mfma_conv1 and a.gn_mfma_fwd1),
+           "gn_mfma_split": bool(gn and a.gn_mfma and a.gn_mfma_sample and a.gn_mfma_conv1 and a.gn_mfma_split),
            "warmup": a.warmup, "rounds": a.rounds, "threads": torch.get_num_threads(),
            "device": torch.cuda.get_device_name(0)}
     for flag, key in ((False, "flag_off"), (True, "flag_on")):
@@ -654,6 +672,12 @@ def main():
     ap.add_argument("--gn-mfma-fwd1", action="store_true",
                     help="gn-kernel: time niidmix_gnlenet_nll_grad_rows_mfma_fwd1_f32 too; gn-rounds, "
                          "with all three: and --device-training-gn-lenet-mfma-fwd1")
+    ap.add_argument("--gn-mfma-split", action="store_true",
+                    help="gn-kernel: time niidmix_gnlenet_nll_grad_rows_mfma_split_f32 against the "
+                         "_mfma_conv1 entry, these two alone; gn-rounds, with the first three: and "
+                         "--device-training-gn-lenet-mfma-split")
+    ap.add_argument("--batch", type=int, default=0,
+                    help="gn-kernel, rounds / gn-rounds: override the shape's batch size")
     a = ap.parse_args()
     if a.step == "all":
         return run_all(a)
